@@ -11,10 +11,20 @@ in config.radiation (sweep_ms, amortised_ms_per_step) -- it is not part of `valu
     python bench.py --gpus 1 --steps 3 --warmup 1            # 400^3 = 64 M cells on one MI355X
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0) with the driver contract fields plus `roofline` (the pEqn PCG SpMV
-kernel against the 8 TB/s HBM peak, algorithmic bytes 24 N + 16 F; `traffic` = the PMC figure of
-profiles/spmv_traffic.json, quoted for the configuration it was measured on) and `cpu_baseline` (the
-oracle port on one host core, bounded sample, scaled by cell count).
+Prints ONE JSON line (rank 0) with the driver contract fields.  A plain run sets up, warms up, times --steps steps and
+prints the line; everything else is measured only with --full:
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full     # + roofline, DIC sweeps, fvDOM sweep cost, class layer, CPU baseline
+
+With --full the line also carries `roofline` (the pEqn PCG SpMV kernel against the 8 TB/s HBM peak, algorithmic bytes
+24 N + 16 F; `traffic` = the PMC figure of profiles/spmv_traffic.json, quoted for the configuration it was measured on),
+`roofline_dic_sweeps`, the fvDOM sweep cost in config.radiation, `class_layer` and `cpu_baseline` (the oracle port on the
+host, bounded sample, scaled by cell count); without it these keys are null.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed: the cell fields of the case
+(ffm_plume_get_field, natural cell order) as float64 DIR/<field>.npy -- every cell up to 262144 cells, above that the same
+fixed, seeded sample of cells in every run (DIR/cell_index.npy) -- and the solver performance of that step
+(DIR/solve_<quantity>.npy, one entry per solve in the order of the step).  The inputs depend on the arguments only.
 """
 import argparse
 import json
@@ -43,7 +53,13 @@ def main():
     ap.add_argument("--no-class-layer", action="store_true", help="skip the extra measurement of the same case through the reference's unchanged equation files")
     ap.add_argument("--transport", choices=["rccl", "host"], default="rccl",
                     help="rccl: one rank per GPU over xGMI (production); host: ranks share GPUs, halo through gloo (rehearsal)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the DIC sweeps, the fvDOM sweep cost, the class layer and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fields and solver performance of the last timed step to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     # stdout carries the ONE JSON line and nothing else: whatever a library prints there while the run is set up (gloo's "[Gloo] Rank 0 is
     # connected to ..." on the host transport) goes to stderr; the line itself is written to the saved descriptor at the end
@@ -106,13 +122,16 @@ def main():
         case = ffm.Plume(ctx, (n, n, n), h=0.05, deltaT=1e-3, lo=lo, hi=hi, nbrRank=nbr)
     if args.solvers == "steckler":
         case.set_solvers(steckler=True)
-    if args.radiation_freq > 0:
+    # the fvDOM stand-in has no coupling into the flow: a plain run whose timed steps hold no sweep (step numbers W .. W+N-1,
+    # counted from 0) skips its set-up and the sweep of warm-up step 0; --full keeps both and measures the sweep
+    sweep_timed = args.radiation_freq > 0 and any(k % args.radiation_freq == 0 for k in range(args.warmup, args.warmup + args.steps))
+    if args.radiation_freq > 0 and (args.full or sweep_timed):
         case.set_radiation(solverFreq=args.radiation_freq)
     setup_s = time.time() - t0
     # the start state of the case, kept on the host for the class-layer measurement at the end (the SAME case through the reference's
     # unchanged solver/*.H over include/ffmFoam.H); nothing of it is touched inside the timed region
     snap = None
-    if rank == 0 and world == 1 and not args.no_class_layer and ffm.snippets.load() is not None:
+    if args.full and rank == 0 and world == 1 and not args.no_class_layer and ffm.snippets.load() is not None:
         try:
             snap = ffm.snippets.FromPlume(case)
         except Exception as e:
@@ -143,6 +162,62 @@ def main():
         dt = float(t.item())
     solves = case.solves()
     pIters = [pf["nIterations"] for nm, pf in solves if nm == "p_rgh"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, case, solves, "" if world == 1 else "_rank%d" % rank)
+    roofline = sweeps = class_layer = cpu = None
+    radiation = "off" if args.radiation_freq <= 0 else {
+        "solverFreq": args.radiation_freq, "set_up": bool(args.full or sweep_timed),
+        "timed_steps_containing_a_sweep": len([k for k in range(args.warmup, args.warmup + args.steps) if k % args.radiation_freq == 0])}
+    if args.full:
+        roofline, sweeps, radiation, class_layer, cpu = full_measurements(args, ffm, ctx, case, snap, barrier, dt, rank, world, n, N, Nloc, Floc)
+    snap = None
+
+    if rank == 0:
+        out = {
+            "metric": "PIMPLE outer-iterations/sec on 64M-cell hex mesh; pEqn SpMV GB/s vs HBM peak",
+            "value": round(args.steps / dt, 4), "unit": "outer-iterations/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "synthetic %d^3 hex box (%d cells), buoyant plume + 5-species EDC-shaped source, "
+                                   "PIMPLE 1/2/0: rhoEqn + UEqn + YEEqn(4 Yi + h) + 2 pEqn per step" % (n, N),
+                       "cells": N, "faces": F, "deltaT": 1e-3, "parallelism": "1 GPU" if world == 1 else ("%dx%dx%d block decomposition, one block per GPU, " % grid)
+                                      + ("RCCL halo + all-reduce" if transport == "rccl" else "halo + all-reduce through the host (gloo)"),
+                       "radiation": radiation, "p_rgh_iterations_last_step": pIters, "setup_s": round(setup_s, 1),
+                       "transport_solvers": "PBiCGStab+DILU" if args.solvers == "krylov" else "smoothSolver+symGaussSeidel maxIter 10"},
+            "transport": used_transport, "transport_requested": "none" if world == 1 else requested_transport,
+            "transport_degraded": bool(world > 1 and used_transport != requested_transport),
+            "roofline": roofline, "roofline_dic_sweeps": sweeps, "class_layer": class_layer, "cpu_baseline": cpu,
+        }
+        sys.stdout.flush()
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
+    case.close()
+    ctx.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+DUMP_FIELDS = ("rho", "p", "p_rgh", "T", "h", "K", "Ux", "Uy", "Uz", "psi", "O2", "H2O", "C3H8", "CO2", "N2")
+DUMP_CELLS = 262144             # cells per field above which a fixed sample is written (15 fields x 2 MiB)
+
+
+def dump_outputs(path, case, solves, suffix=""):
+    """the state the last timed step left (the fields a caller of ffm_plume_step reads back) and that step's solver performance"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    N = case.nCells
+    idx = None
+    if N > DUMP_CELLS:
+        idx = np.unique(np.random.default_rng(20240531).integers(0, N, DUMP_CELLS))
+        np.save(os.path.join(path, "cell_index%s.npy" % suffix), idx.astype(np.float64))
+    for name in DUMP_FIELDS:
+        v = case.field(name)
+        np.save(os.path.join(path, "%s%s.npy" % (name, suffix)), np.ascontiguousarray(v if idx is None else v[idx], np.float64))
+    for key in ("initialResidual", "finalResidual", "nIterations"):
+        np.save(os.path.join(path, "solve_%s%s.npy" % (key, suffix)), np.array([pf[key] for _, pf in solves], np.float64))
+
+
+def full_measurements(args, ffm, ctx, case, snap, barrier, dt, rank, world, n, N, Nloc, Floc):
+    """--full: the figures beside the headline, each measured after the timed steps"""
 
     # ---- roofline: the PCG SpMV kernel (lduMatrix::Amul) on the p_rgh matrix left by the last corrector,
     # HIP events on the library's stream (ffm_bench_spmv), algorithmic bytes 24 N + 16 F (SURVEY 8d)
@@ -289,28 +364,7 @@ def main():
         except Exception as e:                            # the extra figures are informative; the contract fields above stand
             cpu["extra_error"] = repr(e)
 
-    if rank == 0:
-        out = {
-            "metric": "PIMPLE outer-iterations/sec on 64M-cell hex mesh; pEqn SpMV GB/s vs HBM peak",
-            "value": round(args.steps / dt, 4), "unit": "outer-iterations/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "synthetic %d^3 hex box (%d cells), buoyant plume + 5-species EDC-shaped source, "
-                                   "PIMPLE 1/2/0: rhoEqn + UEqn + YEEqn(4 Yi + h) + 2 pEqn per step" % (n, N),
-                       "cells": N, "faces": F, "deltaT": 1e-3, "parallelism": "1 GPU" if world == 1 else ("%dx%dx%d block decomposition, one block per GPU, " % grid)
-                                      + ("RCCL halo + all-reduce" if transport == "rccl" else "halo + all-reduce through the host (gloo)"),
-                       "radiation": radiation, "p_rgh_iterations_last_step": pIters, "setup_s": round(setup_s, 1),
-                       "transport_solvers": "PBiCGStab+DILU" if args.solvers == "krylov" else "smoothSolver+symGaussSeidel maxIter 10"},
-            "transport": used_transport, "transport_requested": "none" if world == 1 else requested_transport,
-            "transport_degraded": bool(world > 1 and used_transport != requested_transport),
-            "roofline": roofline, "roofline_dic_sweeps": sweeps, "class_layer": class_layer, "cpu_baseline": cpu,
-        }
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-    case.close()
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
+    return roofline, sweeps, radiation, class_layer, cpu
 
 
 if __name__ == "__main__":

@@ -8,8 +8,8 @@
   compiled against include/ffmFoam.H (the fvMesh / fvMatrix / fvm:: / fvc:: layer over the C ABI) and include/fireFoamHandles.H
   (the physics handles with the stand-ins of the synthetic plume case).  This file is what solver/createFields.H is to the
   reference: it declares the objects the snippets expect to find in scope.  Nothing of the reference is copied: the build
-  (firefoam-dev_amd/csrc/Makefile, target refsnippets; only where /root/reference exists) passes -I/root/reference/solver,
-  and the output libffm_refsnippets.so is git-ignored.
+  (oracle/Makefile, target ref; only where the reference can be read) passes -I$(REFDIR), the reference's solver/ directory,
+  and the output oracle/_ref/libffm_refsnippets.so is git-ignored.
 
   tests/test_reference_snippets_cpu.py builds it (the "compiles unchanged" check of SURVEY 8b B1);
   tests/test_reference_snippets_gpu.py runs the step on the device and compares the fields with the oracle.

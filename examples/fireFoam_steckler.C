@@ -16,7 +16,7 @@
   time step of cases/steckler/original/linux64/log.fireFoam:163-226 (tests/golden/steckler_first_step.json);
   tests/test_steckler_case_gpu.py runs it and compares every printed solve.
 
-  Built like fireFoam_snippets.C: only where /root/reference exists, with -I/root/reference/solver; nothing is copied.
+  Built like fireFoam_snippets.C (oracle/Makefile, target ref, into oracle/_ref/): only where the reference can be read; nothing is copied.
 \*---------------------------------------------------------------------------*/
 #include "fireFoamHandles.H"
 

@@ -24,7 +24,7 @@
 
 #include "ffm_mesh.hpp"
 
-template <class T> static int up(ffm_ctx *c, T **d, const std::vector<T> &v)
+template <class T, class Al> static int up(ffm_ctx *c, T **d, const std::vector<T, Al> &v)
 {
     return ffm_upload_vec(c, d, v);
 }
@@ -45,13 +45,12 @@ extern "C" int ffm_mesh_create(ffm_ldu *A, const double *V, const double *C, con
     const int B = m->B;
     // face geometry: caller (LDU) face order -> native
     // (one staging array for all six face fields: filled and scattered by the host threads, then uploaded)
-    std::vector<double> stage;
-    stage.reserve(std::max(nNat, 1));
+    ffm_hvec<double> stage;
     int rc = FFM_OK;
     auto upNative = [&](double **dst, const double *src, double fill) -> int {
         if (stage.empty()) stage.resize(std::max(nNat, 1));
         const int *c2n = A->h_callerToNative.data(); double *vp = stage.data();
-        ffm_parallel_for(nNat, [=](long lo, long hi) { for (long q = lo; q < hi; q++) vp[q] = fill; });
+        ffm_parallel_for((long)stage.size(), [=](long lo, long hi) { for (long q = lo; q < hi; q++) vp[q] = fill; });
         ffm_parallel_for(F, [=](long lo, long hi) { for (long f = lo; f < hi; f++) vp[c2n[f]] = src[f]; });      // (distinct destinations)
         return up(m->ctx, dst, stage);
     };
@@ -67,7 +66,7 @@ extern "C" int ffm_mesh_create(ffm_ldu *A, const double *V, const double *C, con
     if ((rc = upNative(&m->magSf, magSf, 0.0))) return rc;
     if ((rc = upNative(&m->delta, deltaCoeffs, 0.0))) return rc;
     if ((rc = upNative(&m->w, weights, 0.5))) return rc;
-    std::vector<double>().swap(stage);
+    ffm_hvec<double>().swap(stage);
     // boundary
     std::vector<int> bc(std::max(B, 1), 0);
     std::vector<double> bS[3], bM(std::max(B, 1), 0.0), bD(std::max(B, 1), 0.0);
@@ -95,7 +94,7 @@ extern "C" int ffm_mesh_create(ffm_ldu *A, const double *V, const double *C, con
     if ((rc = up(m->ctx, &m->bcStart, start))) return rc;
     if ((rc = up(m->ctx, &m->bcItem, order))) return rc;
     // inverse reconstruction tensor per cell (host, once): T = sum_f Sf (x) Sf / magSf over all faces of the cell
-    std::vector<double> T((size_t)6 * N, 0.0);   // xx xy xz yy yz zz
+    ffm_hvec<double> T = ffm_hvec_fill<double>((size_t)6 * N, 0.0);   // xx xy xz yy yz zz
     auto addT = [&](int c, const double s[3], double mag) {
         if (mag <= 0) return;
         T[0 * (size_t)N + c] += s[0] * s[0] / mag; T[1 * (size_t)N + c] += s[0] * s[1] / mag; T[2 * (size_t)N + c] += s[0] * s[2] / mag;
@@ -103,9 +102,9 @@ extern "C" int ffm_mesh_create(ffm_ldu *A, const double *V, const double *C, con
     };
     {
         // owner/neighbour of caller faces: recover from the native layout on the host
-        std::vector<int> nat2caller(nNat, -1);
+        ffm_hvec<int> nat2caller = ffm_hvec_fill<int>(nNat, -1);
         for (int f = 0; f < F; f++) nat2caller[A->h_callerToNative[f]] = f;
-        std::vector<int> hUpNbr(std::max(nNat, 1));
+        ffm_hvec<int> hUpNbr(std::max(nNat, 1));
         FFM_HIP(hipStreamSynchronize(A->ctx->stream));              // (the tables were uploaded on the context's non-blocking stream)
         FFM_TRY(ffm_d2h(A->ctx, hUpNbr.data(), A->upNbr, sizeof(int) * nNat));
         std::vector<int> hUpOff(A->nSlices + 1);
@@ -121,7 +120,7 @@ extern "C" int ffm_mesh_create(ffm_ldu *A, const double *V, const double *C, con
             }
         }
         for (int k = 0; k < B; k++) { const double sv[3] = {bS[0][k], bS[1][k], bS[2][k]}; addT(bc[k], sv, bM[k]); }
-        std::vector<double> inv((size_t)6 * N, 0.0);
+        ffm_hvec<double> inv = ffm_hvec_fill<double>((size_t)6 * N, 0.0);
         // 2-D / 1-D meshes (empty patches): the tensor has no entries in the missing directions.  As OpenFOAM's inv(tensorField)
         // does, the missing directions are found from the first cell (diagonal entry negligible against the tensor's magnitude),
         // 1 is added on those diagonals before the inversion and taken off again afterwards

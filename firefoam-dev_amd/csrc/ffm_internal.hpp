@@ -113,7 +113,7 @@ inline int ffm_dzero(ffm_ctx *c, void *dst_d, size_t bytes)
     FFM_HIP(hipMemsetAsync(dst_d, 0, bytes, c->stream));
     return FFM_OK;
 }
-template <class T> inline int ffm_upload_vec(ffm_ctx *c, T **d, const std::vector<T> &v, size_t minCount = 1)
+template <class T, class Al> inline int ffm_upload_vec(ffm_ctx *c, T **d, const std::vector<T, Al> &v, size_t minCount = 1)
 {
     FFM_HIP(hipMalloc((void **)d, sizeof(T) * std::max<size_t>(v.size(), minCount)));
     return ffm_h2d(c, *d, v.data(), sizeof(T) * v.size());
@@ -130,6 +130,24 @@ template <class Fn> inline void ffm_parallel_for(long n, Fn fn, long serialBelow
     const long chunk = (n + nT - 1) / nT;
     for (int t = 0; t < nT; t++) { const long lo = t * chunk, hi = std::min(n, lo + chunk); if (lo < hi) th.emplace_back([=] { fn(lo, hi); }); }
     for (auto &x : th) x.join();
+}
+
+// Host set-up arrays of many GB (geometry of a 400^3 box) whose elements are not value-initialised on allocation: they are filled
+// with ffm_parallel_for, so the first touch of their pages is spread over the host threads instead of falling on one
+template <class T> struct ffm_noinit_alloc : std::allocator<T> {
+    template <class U> struct rebind { using other = ffm_noinit_alloc<U>; };
+    ffm_noinit_alloc() = default;
+    template <class U> ffm_noinit_alloc(const ffm_noinit_alloc<U> &) {}
+    template <class U> void construct(U *p) { ::new ((void *)p) U; }
+    template <class U, class... A> void construct(U *p, A &&...a) { ::new ((void *)p) U(std::forward<A>(a)...); }
+};
+template <class T> using ffm_hvec = std::vector<T, ffm_noinit_alloc<T>>;
+template <class T> inline ffm_hvec<T> ffm_hvec_fill(size_t n, T v)
+{
+    ffm_hvec<T> a(n);
+    T *p = a.data();
+    ffm_parallel_for((long)n, [=](long lo, long hi) { for (long i = lo; i < hi; i++) p[i] = v; });
+    return a;
 }
 
 // key of a cached hipGraph of level-scheduled sweeps: EVERY device pointer the captured kernels bake in

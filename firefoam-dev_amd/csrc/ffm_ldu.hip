@@ -482,6 +482,33 @@ extern "C" int ffm_tile_hint_from_centres(int nCells, const double *C /* [3][nCe
     return FFM_OK;
 }
 
+// The analysis of the last ffm_renumber_hint, in its own new numbering.  A caller that renumbers its mesh with it and then creates the
+// matrix on the renumbered addressing with the renumbered hint (the plume driver) would run the same analysis a second time and get
+// identity permutations and the same levels, groups and orders; ldu_create takes it from here instead, after checking that the
+// addressing and the hint are exactly those of the new numbering.  One slot, emptied by its first use or by the next renumbering.
+struct AnalysisMemo { bool valid = false; int N = 0, nOwn = 0, F = 0, sweepMode = 0; LduAnalysis a; std::vector<int> hint; };
+static AnalysisMemo g_analysisMemo;
+
+static bool same_ints(const int *x, const int *y, long n)
+{
+    std::atomic<int> differ(0);
+    ffm_parallel_for(n, [&](long lo, long hi) { if (memcmp(x + lo, y + lo, sizeof(int) * (size_t)(hi - lo))) differ = 1; });
+    return !differ;
+}
+
+static bool take_analysis_memo(int N, int nOwn, int F, const int *l, const int *u, const int *groupHint, LduAnalysis &a)
+{
+    AnalysisMemo m;
+    std::swap(m, g_analysisMemo);
+    if (!m.valid || !groupHint || m.N != N || m.nOwn != nOwn || m.F != F || m.sweepMode != default_sweep_mode()) return false;
+    if (!same_ints(l, m.a.l.data(), F) || !same_ints(u, m.a.u.data(), F) || !same_ints(groupHint, m.hint.data(), nOwn)) return false;
+    a = std::move(m.a);
+    std::iota(a.newToOldCell.begin(), a.newToOldCell.end(), 0); a.oldToNewCell = a.newToOldCell;
+    std::iota(a.newToOldFace.begin(), a.newToOldFace.end(), 0);
+    a.identity = true;
+    return true;
+}
+
 extern "C" int ffm_renumber_levels_ext(int nOwned, int nGhost, int nFaces, const int *l, const int *u,
                                        int *newToOldCell, int *newToOldFace)
 { return ffm_renumber_hint(nOwned, nGhost, nFaces, l, u, nullptr, newToOldCell, newToOldFace); }
@@ -495,6 +522,16 @@ extern "C" int ffm_renumber_hint(int nOwned, int nGhost, int nFaces, const int *
     if (newToOldCell) std::copy(a.newToOldCell.begin(), a.newToOldCell.end(), newToOldCell);
     if (newToOldFace) std::copy(a.newToOldFace.begin(), a.newToOldFace.end(), newToOldFace);
     if (a.mode == 2) memo_put(nOwned + nGhost, nFaces, a.l.data(), a.u.data(), a.grpCell);
+    g_analysisMemo = AnalysisMemo();
+    if (a.mode == 2 && groupHint && nGhost == 0) {
+        AnalysisMemo &m = g_analysisMemo;
+        m.N = nOwned; m.nOwn = nOwned; m.F = nFaces; m.sweepMode = default_sweep_mode();
+        m.hint.resize(nOwned);
+        { int *hp = m.hint.data(); const int *n2o = a.newToOldCell.data();
+          ffm_parallel_for(nOwned, [=](long lo, long hi) { for (long c = lo; c < hi; c++) hp[c] = groupHint[n2o[c]]; }); }
+        m.a = std::move(a);
+        m.valid = true;
+    }
     return FFM_OK;
 }
 
@@ -549,7 +586,8 @@ static int ldu_create_impl(ffm_ctx *ctx, int nOwn, int nGhost, int F, const int 
 {
     const int N = nOwn + nGhost;
     LduAnalysis a;
-    { FfmStageTimer tm_("ldu_create: analyse"); FFM_TRY(analyse(N, nOwn, F, l, u, true, false, a, groupHint, forceMode)); }
+    { FfmStageTimer tm_("ldu_create: analyse");
+      if (forceMode >= 0 || nGhost != 0 || !take_analysis_memo(N, nOwn, F, l, u, groupHint, a)) FFM_TRY(analyse(N, nOwn, F, l, u, true, false, a, groupHint, forceMode)); }
     FfmStageTimer tmRest_("ldu_create: layout+upload+tile");
     ffm_ldu *A = new ffm_ldu();
     A->ctx = ctx; A->nCells = N; A->nOwned = nOwn; A->nFaces = F; A->globalCells = nOwn;

@@ -926,7 +926,8 @@ extern "C" int ffm_plume_create_block(ffm_ctx *ctx, int gx, int gy, int gz, cons
     P->nNat = P->A->upTotal;
     tmS_ = new FfmStageTimer("plume_create: geometry + patches");
     // ---- geometry (global coordinates)
-    std::vector<double> V(N, h * h * h), C(3 * N), Sf(3 * (size_t)F, 0.0), magSf(F, h * h), wgt(F, 0.5), del(F, 1.0 / h), Cfy(F);
+    ffm_hvec<double> V = ffm_hvec_fill<double>(N, h * h * h), C(3 * N), Sf = ffm_hvec_fill<double>(3 * (size_t)F, 0.0), magSf = ffm_hvec_fill<double>(F, h * h),
+                     wgt = ffm_hvec_fill<double>(F, 0.5), del = ffm_hvec_fill<double>(F, 1.0 / h), Cfy(F);      // C, Cfy: every entry written below
     {
         double *Cp = C.data(), *Sfp = Sf.data(), *Cfyp = Cfy.data(); const int *c2p = c2.data(), *l2p = l2.data(); const signed char *fd2p = fd2.data(), *sg2p = sg2.data();
         const int lo0 = lo[0], lo1 = lo[1], lo2 = lo[2]; int gO[7]; for (int q = 0; q < 7; q++) gO[q] = gOff[q];
@@ -988,7 +989,7 @@ extern "C" int ffm_plume_create_block(ffm_ctx *ctx, int gx, int gy, int gz, cons
     tmS_ = new FfmStageTimer("plume_create: face centres");
     {
         // face centres (LUST correction): owner's centre + half a cell towards the neighbour
-        std::vector<double> Cf(3 * (size_t)F);
+        ffm_hvec<double> Cf(3 * (size_t)F);                // every entry written below
         { double *Cfp = Cf.data(); const double *Cp = C.data(); const int *l2p = l2.data(); const signed char *fd2p = fd2.data(), *sg2p = sg2.data();
           ffm_parallel_for(F, [=](long a, long b) { for (long f = a; f < b; f++) for (int d = 0; d < 3; d++) Cfp[(size_t)d * F + f] = Cp[(size_t)d * N + l2p[f]] + (fd2p[f] == d ? sg2p[f] * 0.5 * h : 0.0); }); }
         FFM_TRY(ffm_mesh_set_face_centres(P->mesh, Cf.data()));

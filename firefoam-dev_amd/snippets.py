@@ -42,8 +42,13 @@ NU = np.array([-3.6282945, 4 * 18.0153 / 44.0962, -1.0, 3 * 44.01 / 44.0962, 0.0
 SPECIES = ["O2", "H2O", "C3H8", "CO2", "N2"]
 
 
+def refpath(name):
+    """a library built from the reference's own files (oracle/Makefile, target ref): oracle/_ref/<name>"""
+    return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", name)
+
+
 def libpath():
-    return os.path.join(os.path.dirname(B.libpath()), "libffm_refsnippets.so")
+    return refpath("libffm_refsnippets.so")
 
 
 def load():

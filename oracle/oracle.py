@@ -24,6 +24,12 @@ def build(force=False):
     return _SO
 
 
+def build_ref():
+    """oracle/_ref/: the drivers compiled from the reference's own equation files (where the reference can be read; needs
+    firefoam-dev_amd/lib/libffm.so).  Elsewhere this keeps whatever _ref/ already holds."""
+    subprocess.check_call(["make", "-C", _HERE, "-s", "ref"])
+
+
 class Perf(C.Structure):
     _fields_ = [("initialResidual", C.c_double), ("finalResidual", C.c_double),
                 ("nIterations", C.c_int), ("converged", C.c_int), ("singular", C.c_int)]

@@ -12,7 +12,7 @@ from test_reference_snippets_gpu import SnippetCase
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 ctx = ffm.Context(0)
-lib = C.CDLL(os.path.join(os.path.dirname(ffm.libpath()), "libffm_refsnippets.so"))
+lib = C.CDLL(ffm.snippets.refpath("libffm_refsnippets.so"))
 lib.firefoam_snippets_step.restype = C.c_int
 lib.firefoam_snippets_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SnippetCase)]
 t0 = time.time()

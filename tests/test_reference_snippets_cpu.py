@@ -43,8 +43,8 @@ def test_the_library_built_from_them_exports_the_step():
     import torch  # noqa: F401
     from ffm_import import ffm
     ffm.lib()
-    so = os.path.join(os.path.dirname(ffm.libpath()), "libffm_refsnippets.so")
-    assert os.path.exists(so), "run firefoam-dev_amd/csrc/Makefile (or __graft_entry__.build())"
+    so = ffm.snippets.refpath("libffm_refsnippets.so")
+    assert os.path.exists(so), "run make -C oracle ref (or __graft_entry__.build())"
     lib = ctypes.CDLL(so)
     assert hasattr(lib, "firefoam_snippets_step") and hasattr(lib, "firefoam_snippets_hydrostatic")
 
@@ -62,7 +62,7 @@ def test_the_steckler_case_driver_uses_the_references_files_too():
     import torch  # noqa: F401
     from ffm_import import ffm
     ffm.lib()
-    so = os.path.join(os.path.dirname(ffm.libpath()), "libffm_steckler.so")
-    assert os.path.exists(so), "run firefoam-dev_amd/csrc/Makefile (or __graft_entry__.build())"
+    so = ffm.snippets.refpath("libffm_steckler.so")
+    assert os.path.exists(so), "run make -C oracle ref (or __graft_entry__.build())"
     lib = ctypes.CDLL(so)
     assert hasattr(lib, "firefoam_steckler_create") and hasattr(lib, "firefoam_steckler_advance") and hasattr(lib, "firefoam_steckler_destroy")

@@ -44,7 +44,7 @@ def test_reference_equation_files_run_a_time_step(O, ffm, ctx, shape, empty):
     """second case: a 2-D mesh, one cell thick with `empty` x-patches (the shape of cases/wallFireSpread2D, BASELINE config 5)"""
     from oracle import plume
     newPlume = lambda: plume.Plume(shape, mesh=plume.make_mesh(shape, empty=empty))
-    so = os.path.join(os.path.dirname(ffm.libpath()), "libffm_refsnippets.so")
+    so = ffm.snippets.refpath("libffm_refsnippets.so")
     if not os.path.exists(so):
         pytest.skip("libffm_refsnippets.so not built (needs /root/reference at build time)")
     lib = C.CDLL(so)
@@ -259,7 +259,7 @@ def test_reference_phrghEqn_reproduces_the_golden_log_on_the_device(O, ffm, ctx,
     29, 32, 7, 0, 0 and every printed residual and gMax-gMin to 1e-6."""
     import json
     from oracle import plume, steckler
-    so = os.path.join(os.path.dirname(ffm.libpath()), "libffm_refsnippets.so")
+    so = ffm.snippets.refpath("libffm_refsnippets.so")
     if not os.path.exists(so):
         pytest.skip("libffm_refsnippets.so not built (needs /root/reference at build time)")
     gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "steckler_ph_rgh.json")))["solves"]
@@ -383,7 +383,7 @@ def test_reference_equation_files_hold_1e8_over_six_steps_on_the_conditioned_cas
     no exact zeros, inflow and ambient values distinct: the limiter is well-conditioned on every face), every field within 1e-8
     rel-L2 of the oracle's after EVERY step with identical iteration counts."""
     from oracle import plume
-    so = os.path.join(os.path.dirname(ffm.libpath()), "libffm_refsnippets.so")
+    so = ffm.snippets.refpath("libffm_refsnippets.so")
     if not os.path.exists(so):
         pytest.skip("libffm_refsnippets.so not built (needs /root/reference at build time)")
     lib = C.CDLL(so)

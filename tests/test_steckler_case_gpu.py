@@ -53,7 +53,7 @@ def sig(x, n):
 def _case(ffm, ctx, tiled, refine=1, tileCells=8):
     """the library, the device mesh and the case data (cases/steckler/0/*, constant/*) of the room refined `refine` times per direction"""
     from oracle import plume, steckler_case as SC, thermo as TH
-    so = os.path.join(os.path.dirname(ffm.libpath()), "libffm_steckler.so")
+    so = ffm.snippets.refpath("libffm_steckler.so")
     if not os.path.exists(so):
         pytest.skip("libffm_steckler.so not built (needs /root/reference at build time)")
     lib = C.CDLL(so)

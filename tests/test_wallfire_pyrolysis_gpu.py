@@ -82,7 +82,7 @@ def _run(O, ffm, ctx, shape, empty, sel, nSteps, compare=True, h=0.05):
     def stage(what):
         if not compare:
             print("  [%7.1f s] %s" % (time.time() - t00, what), flush=True)
-    so = os.path.join(os.path.dirname(ffm.libpath()), "libffm_refsnippets.so")
+    so = ffm.snippets.refpath("libffm_refsnippets.so")
     if not os.path.exists(so):
         pytest.skip("libffm_refsnippets.so not built (needs /root/reference at build time)")
     lib = C.CDLL(so)
