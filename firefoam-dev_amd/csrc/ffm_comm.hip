@@ -165,8 +165,6 @@ extern "C" int ffm_ldu_set_interfaces(ffm_ldu *A, int nPatches, const int *patch
     A->ifFaceCells = nullptr; A->ifBou = A->ifInt = A->haloSend = A->haloRecv = nullptr;
     A->ifCell = A->ifCellStart = A->ifItem = nullptr;
     A->ifaces.clear(); A->ifaceTags.clear(); A->haloTotal = 0; A->nIfCells = 0;
-    for (auto &kv : A->graphs) hipGraphExecDestroy(kv.second);   // halo buffers are baked into no graph, but be safe
-    A->graphs.clear();
     if (!nPatches) return FFM_OK;
     // old -> new cell map
     std::vector<int> oldToNew(A->nCells);

@@ -7,7 +7,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -150,17 +149,6 @@ template <class T> inline ffm_hvec<T> ffm_hvec_fill(size_t n, T v)
     return a;
 }
 
-// key of a cached hipGraph of level-scheduled sweeps: EVERY device pointer the captured kernels bake in
-struct SweepGraphKey {
-    int kind; const void *p[6];
-    bool operator<(const SweepGraphKey &o) const {
-        if (kind != o.kind) return kind < o.kind;
-        for (int i = 0; i < 6; i++) if (p[i] != o.p[i]) return p[i] < o.p[i];
-        return false;
-    }
-};
-constexpr size_t FFM_MAX_SWEEP_GRAPHS = 24;     // cap of the per-matrix graph cache (oldest entries are dropped first)
-
 struct ffm_iface {
     int size = 0, nbrRank = -1;
     int offset = 0;                 // offset into the packed halo buffers
@@ -174,14 +162,10 @@ struct ffm_ldu {
     std::vector<int> h_ghSendCaller;        // the send cells of the ghost exchange in the caller's cell labels (GAMG: agglomerated per level)
     bool identity = true;           // caller numbering == internal numbering
     bool symmetric = true;
-    bool bwdContig = true;          // backward levels are contiguous cell ranges
 
     // host copies of the analysis (internal numbering)
     std::vector<int> h_newToOldCell, h_newToOldFace;
-    std::vector<int> h_fwdLevelStart;   // [nLevels+1] cell ranges (level-major)
-    std::vector<int> h_bwdLevelStart;   // [nBwdLevels+1] ranges into bwdOrder
-    std::vector<int> h_bwdFirstCell;    // [nBwdLevels] first cell of each level (bwdContig)
-    int nLevels = 0, nBwdLevels = 0;
+    int nLevels = 0;                    // forward dependency levels
 
     // device addressing (internal cell numbering): sliced owner-ELL.
     // Cells are grouped in slices of 64 (one wavefront).  Slice sl stores its faces slot-major:
@@ -201,12 +185,7 @@ struct ffm_ldu {
     int *upOff = nullptr, *loOff = nullptr;      // [nSlices+1]
     int *upNbr = nullptr;                        // [upTotal]
     int *loEnt = nullptr;                        // [loTotal]
-    int *bwdOrder = nullptr;                     // [N] (only when !bwdContig)
-    int *smallFwdStart = nullptr;                // [nLevels+1] device copy of h_fwdLevelStart (single-workgroup sweeps, ffm_solve.hip)
-    int *smallBwdRange = nullptr;                // [2*nBwdLevels] {p0, p1} of every backward level
-    int smallState = 0;                          // 0 not decided, 1 usable, -1 not (too large / switched off)
-    int *flowOrder = nullptr;                    // [nOwned] cells by backward level (dataflow sweeps, ffm_solve.hip)
-    int flowState = 0;                           // 0 not decided, 1 usable, -1 not
+    int *flowOrder = nullptr;                    // [nOwned] cells by backward level (dataflow sweeps, ffm_solve.hip; level-scheduled mode)
     int *cellPerm = nullptr;                     // [N] new->old (only when !identity)
     int *faceSrc = nullptr;                      // [upTotal] native face -> caller face id (-1 padding)
     std::vector<int> h_callerToNative;           // [F] caller face id -> native face index
@@ -258,17 +237,12 @@ struct ffm_ldu {
 
     // ---- tiled sweep plan (sweepMode == 2): cells are numbered group-major, level-major inside a group;
     // group g = cells [grpCell[g], grpCell[g+1]); one workgroup sweeps one group level by level (ffm_tile.hip)
-    int sweepMode = 0;              // 0: one launch per level (level-major numbering); 2: tiled wavefront sweeps
+    int sweepMode = 0;              // 0: dataflow sweeps (level-major numbering); 2: tiled wavefront sweeps
     int nGroups = 0;
     bool bwdIsReverse = false;      // inside every group the backward order is the exact reverse of the forward order
     int *grpCell = nullptr;         // [G+1]
-    int *bwdCells = nullptr;        // [nOwned] cells in (group, backward level) order
     unsigned int *sweepTicket = nullptr;          // [2]: ticket counter (zeroed on the stream before every sweep), abort flag
     ffm_tile_plan *tile = nullptr;                // tiled wavefront plan (sweepMode == 2)
-
-    // cached hipGraphs of level-scheduled sweeps
-    std::map<SweepGraphKey, hipGraphExec_t> graphs;
-    std::vector<SweepGraphKey> graphOrder;         // insertion order, for the cap
 };
 
 // FFM_TIMING=1: wall time of the host-side set-up stages to stderr
@@ -311,12 +285,10 @@ int ffm_allreduce_minmax(ffm_ctx *ctx, int slot, int isMax);
 void ffm_comm_finalize_i(ffm_ctx *ctx);
 int ffm_precond_setup_i(ffm_ldu *A, int precond);
 int ffm_precond_apply_i(ffm_ldu *A, int precond, bool transpose, const double *r, double *w);
-int ffm_tile_build(ffm_ldu *A, const std::vector<int> &lev, const std::vector<int> &bl, const std::vector<int> &grpCell,
-                   const std::vector<int> *bwdCells /* null: the backward order mirrors the forward order */);
+int ffm_tile_build(ffm_ldu *A, const std::vector<int> &lev, const std::vector<int> &bl, const std::vector<int> &grpCell);
 bool ffm_tile_feasible(int nOwn, int F, const int *l, const int *u);
 int ffm_tile_calc_rD(ffm_ldu *A);
-int ffm_flow_check_abort(ffm_ldu *A);                    // dataflow sweeps of level-scheduled matrices (ffm_solve.hip)
-bool ffm_tile_gs_usable(const ffm_ldu *A);
+int ffm_sweep_check_abort(ffm_ldu *A);                   // abort word of the tiled and the dataflow sweeps (ffm_solve.hip)
 int ffm_tile_gs_ghost_terms(ffm_ldu *A, const double *psi, double *bP);
 int ffm_ghost_exchange(ffm_ldu *A, double *x);
 int ffm_ghost_exchange_begin(ffm_ldu *A, double *x);     // starts the refresh of x[nOwned..nCells); may return with it in flight
@@ -342,7 +314,6 @@ bool ffm_tile_multi_usable(const ffm_ldu *A);
 int ffm_tile_precond_multi(ffm_ldu *A, int precond, int n, const double *const *rD, const double *const *r, double *const *w);
 int ffm_tile_calc_rD_multi(ffm_ldu *A, int n, const double *const *diag, double *const *D);
 int ffm_k_spmv_multi(ffm_ldu *A, int n, const double *const *diag, const double *const *x, double *const *y, double *const *sumA);
-int ffm_tile_check_abort(ffm_ldu *A);
 int ffm_gs_smooth_i(ffm_ldu *A, bool sym, int nSweeps, double *psi, const double *b);
 int ffm_halo_exchange(ffm_ldu *A, const double *x);
 int ffm_ghost_exchange(ffm_ldu *A, double *x);                 // refresh x[nOwned..nCells) from the neighbour ranks          // pack x[faceCells], exchange into haloRecv

@@ -42,15 +42,15 @@ struct LduAnalysis {
     std::vector<int> l, u;                 // new numbering, upper-triangular order
     std::vector<int> fwdLevelStart;        // [nLevels+1]
     std::vector<int> bwdLevelStart;        // [nBwd+1] into bwdOrder
-    std::vector<int> bwdOrder;             // cells sorted by backward level
-    bool identity = true, bwdContig = true;
+    std::vector<int> bwdOrder;             // cells sorted by backward level (the order of the dataflow sweeps' backward chunks)
+    bool identity = true;
     // group plan of the tiled sweeps (mode 2)
     int mode = 0, nGroups = 0; bool bwdIsReverse = false;
     std::vector<int> levNew, blNew;         // forward / backward level of every owned cell (new numbering)
-    std::vector<int> grpCell, bwdCells;
+    std::vector<int> grpCell;
 };
 
-// Sweep modes.  0 "levels": one launch per dependency level (level-major numbering).  2 "tile": tiled wavefront sweep
+// Sweep modes.  0 "levels": dataflow sweeps (level-major numbering, ffm_solve.hip).  2 "tile": tiled wavefront sweep
 // (ffm_tile.hip).  Default (FFM_SWEEP unset or "auto"): tile when the caller gives a group hint or the mesh is a
 // blockMesh-numbered box and the plan is feasible, levels otherwise.  FFM_SWEEP=tile also tiles un-hinted meshes (chunks of
 // the cell order; tests).
@@ -373,11 +373,6 @@ static int analyse(int N, int nOwn, int F, const int *l, const int *u, bool renu
         if (!nB) pos.clear();
         for (int c = 0; c < nOwn; c++) a.bwdOrder[pos[bl[c]]++] = c;
     }
-    a.bwdContig = true;
-    for (int b = 0; b < nB && a.bwdContig; b++) {
-        int s = a.bwdLevelStart[b], e = a.bwdLevelStart[b + 1];
-        if (e > s && a.bwdOrder[e - 1] - a.bwdOrder[s] != e - s - 1) a.bwdContig = false;
-    }
     lap_.lap("backward levels");
     if (a.mode >= 1) {
         const int G = a.nGroups;
@@ -392,29 +387,12 @@ static int analyse(int N, int nOwn, int F, const int *l, const int *u, bool renu
             for (long f = lo; f < hi; f++) if (a.u[f] < nOwn && grpOfNew[a.l[f]] > grpOfNew[a.u[f]]) cyclic = 1;
         });
         if (cyclic) { ffm_set_error("internal: group graph not acyclic"); return FFM_ERR_ADDR; }
-        // backward order inside each group: by backward level, then descending cell index (a counting sort per group; groups in parallel)
-        a.bwdCells.resize(nOwn);
+        // the backward order inside each group (by backward level, then descending cell index) is the exact reverse of the forward
+        // order when the backward level never falls from one cell of a group to the cell before it
         std::atomic<int> notReverse(0);
-        auto groups = [&](long g0, long g1) {
-            std::vector<int> cntB;
-            for (long g = g0; g < g1; g++) {
-                const int c0 = a.grpCell[g], c1 = a.grpCell[g + 1];
-                if (c1 <= c0) continue;
-                int bMin = bl[c0], bMax = bl[c0];
-                for (int c = c0 + 1; c < c1; c++) { bMin = std::min(bMin, bl[c]); bMax = std::max(bMax, bl[c]); }
-                cntB.assign((size_t)(bMax - bMin) + 2, 0);
-                for (int c = c0; c < c1; c++) cntB[bl[c] - bMin + 1]++;
-                for (size_t i = 1; i < cntB.size(); i++) cntB[i] += cntB[i - 1];
-                for (int c = c1 - 1; c >= c0; c--) a.bwdCells[c0 + cntB[bl[c] - bMin]++] = c;      // descending cell index inside a level
-                for (int p = c0; p < c1; p++) if (a.bwdCells[p] != c1 - 1 - (p - c0)) { notReverse = 1; break; }
-            }
-        };
-        if (G >= 8 && nOwn >= (1 << 20)) {
-            static const int nT = [] { const char *e = getenv("FFM_HOST_THREADS"); int t = e ? atoi(e) : (int)std::thread::hardware_concurrency(); return std::max(1, std::min(t, 16)); }();
-            std::vector<std::thread> th;
-            for (int t = 0; t < nT; t++) th.emplace_back([&, t] { groups((long)G * t / nT, (long)G * (t + 1) / nT); });
-            for (auto &x : th) x.join();
-        } else groups(0, G);
+        ffm_parallel_for(nOwn, [&](long lo, long hi) {
+            for (long c = std::max(lo, 1L); c < hi; c++) if (grpOfNew[c - 1] == grpOfNew[c] && bl[c - 1] < bl[c]) notReverse = 1;
+        });
         a.bwdIsReverse = !notReverse;
     }
     lap_.lap("group checks + backward order");
@@ -591,11 +569,9 @@ static int ldu_create_impl(ffm_ctx *ctx, int nOwn, int nGhost, int F, const int 
     FfmStageTimer tmRest_("ldu_create: layout+upload+tile");
     ffm_ldu *A = new ffm_ldu();
     A->ctx = ctx; A->nCells = N; A->nOwned = nOwn; A->nFaces = F; A->globalCells = nOwn;
-    A->identity = a.identity; A->bwdContig = a.bwdContig;
+    A->identity = a.identity;
     A->sweepMode = a.mode; A->nGroups = a.nGroups; A->bwdIsReverse = a.bwdIsReverse;
     A->nLevels = (int)a.fwdLevelStart.size() - 1; if (A->nLevels < 0) A->nLevels = 0;
-    A->nBwdLevels = (int)a.bwdLevelStart.size() - 1; if (A->nBwdLevels < 0) A->nBwdLevels = 0;
-    A->h_fwdLevelStart = a.fwdLevelStart; A->h_bwdLevelStart = a.bwdLevelStart;
     A->h_newToOldCell = a.newToOldCell; A->h_newToOldFace = a.newToOldFace;
     // derived addressing: sliced owner-ELL
     const int nSl = (nOwn + 63) / 64;                 // rows exist for owned cells only
@@ -648,14 +624,6 @@ static int ldu_create_impl(ffm_ctx *ctx, int nOwn, int nGhost, int F, const int 
             loEnt[q] = (a.l[f] << 4) | slotOfFace[f];
         }
     }
-    if (A->sweepMode == 0 && A->bwdContig) {
-        // keep only the first cell of every backward level: ranges are [first, first+count)
-        A->h_bwdFirstCell.resize(A->nBwdLevels);
-        for (int b = 0; b < A->nBwdLevels; b++) {
-            int s = a.bwdLevelStart[b];
-            A->h_bwdFirstCell[b] = (a.bwdLevelStart[b + 1] > s) ? a.bwdOrder[s] : 0;
-        }
-    }
     int rc = FFM_OK;
     do {
         if ((rc = upload(ctx, &A->upOff, upOff))) break;
@@ -663,13 +631,10 @@ static int ldu_create_impl(ffm_ctx *ctx, int nOwn, int nGhost, int F, const int 
         if ((rc = upload(ctx, &A->upNbr, upNbr))) break;
         if ((rc = upload(ctx, &A->loEnt, loEnt))) break;
         if ((rc = upload(ctx, &A->faceSrc, faceSrc))) break;
-        if (A->sweepMode == 0 && !A->bwdContig && (rc = upload(ctx, &A->bwdOrder, a.bwdOrder))) break;
-        if (A->sweepMode >= 1) {
-            if ((rc = upload(ctx, &A->grpCell, a.grpCell))) break;
-            if ((rc = upload(ctx, &A->bwdCells, a.bwdCells))) break;
-            if (hipMalloc((void **)&A->sweepTicket, 2 * sizeof(unsigned int)) != hipSuccess) { rc = FFM_ERR_HIP; break; }
-            hipMemsetAsync(A->sweepTicket, 0, 2 * sizeof(unsigned int), ctx->stream);
-        }
+        if (A->sweepMode == 0 && (rc = upload(ctx, &A->flowOrder, a.bwdOrder))) break;
+        if (A->sweepMode == 2 && (rc = upload(ctx, &A->grpCell, a.grpCell))) break;
+        if (hipMalloc((void **)&A->sweepTicket, 2 * sizeof(unsigned int)) != hipSuccess) { rc = FFM_ERR_HIP; break; }
+        hipMemsetAsync(A->sweepTicket, 0, 2 * sizeof(unsigned int), ctx->stream);
         if (!A->identity && (rc = upload(ctx, &A->cellPerm, a.newToOldCell))) break;
         if (A->sweepMode == 2) {
             A->h_loEnt = loEnt; A->h_upNbr = upNbr;
@@ -677,17 +642,14 @@ static int ldu_create_impl(ffm_ctx *ctx, int nOwn, int nGhost, int F, const int 
             // the backward sweep walks the forward entries in reverse.  Where they are not (internal walls, unstructured graphs) it STILL
             // can: the reverse of a topological order is a topological order of the reversed graph, and the cells of one forward level are
             // never neighbours, so they form a valid backward entry as well -- neighbours that are then far away in the numbering go
-            // through the mailboxes like any other external.  The sweeps of such meshes therefore take the mirror kernels (fused PCG
-            // iteration, multi-system sweeps, no permutation passes); FFM_TILE_POS_BACKWARD=1 keeps the separate backward-level order in
-            // "position space" (round 2's form).
-            static const bool posBackward = getenv("FFM_TILE_POS_BACKWARD") && atoi(getenv("FFM_TILE_POS_BACKWARD")) != 0;
-            if (a.bwdIsReverse || posBackward) rc = ffm_tile_build(A, a.levNew, a.blNew, a.grpCell, a.bwdIsReverse ? nullptr : &a.bwdCells);
+            // through the mailboxes like any other external.  Such meshes take the backward levels mirrored from the forward ones.
+            if (a.bwdIsReverse) rc = ffm_tile_build(A, a.levNew, a.blNew, a.grpCell);
             else {
                 int maxLev = 0;
                 for (int c = 0; c < nOwn; c++) maxLev = std::max(maxLev, a.levNew[c]);
                 std::vector<int> blSym(nOwn);
                 for (int c = 0; c < nOwn; c++) blSym[c] = maxLev - a.levNew[c];
-                rc = ffm_tile_build(A, a.levNew, blSym, a.grpCell, nullptr);
+                rc = ffm_tile_build(A, a.levNew, blSym, a.grpCell);
             }
             A->h_loEnt.clear(); A->h_loEnt.shrink_to_fit(); A->h_upNbr.clear(); A->h_upNbr.shrink_to_fit();
             if (rc) break;
@@ -734,13 +696,12 @@ extern "C" int ffm_ldu_destroy(ffm_ldu *A)
     if (!A) return FFM_OK;
     hipSetDevice(A->ctx->device);
     hipStreamSynchronize(A->ctx->stream);
-    for (auto &kv : A->graphs) hipGraphExecDestroy(kv.second);
     for (double *w : A->work) hipFree(w);
     hipFree(A->gsProd);
     for (int i = 0; i < 3; i++) hipFree(A->permIn[i]);
     hipFree(A->upOff); hipFree(A->loOff); hipFree(A->upNbr); hipFree(A->loEnt); hipFree(A->faceSrc);
-    hipFree(A->bwdOrder); hipFree(A->cellPerm); hipFree(A->callerToNative); hipFree(A->smallFwdStart); hipFree(A->smallBwdRange); hipFree(A->flowOrder);
-    hipFree(A->grpCell); hipFree(A->bwdCells); hipFree(A->sweepTicket); hipFree(A->rowSched);
+    hipFree(A->cellPerm); hipFree(A->callerToNative); hipFree(A->flowOrder);
+    hipFree(A->grpCell); hipFree(A->sweepTicket); hipFree(A->rowSched);
     ffm_tile_free(A);
     hipFree(A->ghSendCells); hipFree(A->ghSendBuf); if (A->ghSendBuf_h) hipHostFree(A->ghSendBuf_h); if (A->ghRecvBuf_h) hipHostFree(A->ghRecvBuf_h);
     hipFree(A->diagBuf); hipFree(A->upperBuf); hipFree(A->lowerBuf); hipFree(A->rD);

@@ -1,4 +1,4 @@
-// ffm_solve.hip -- level-scheduled DIC / DILU / Gauss-Seidel sweeps and the
+// ffm_solve.hip -- DIC / DILU / Gauss-Seidel sweeps of level-scheduled matrices and the
 // PCG / PBiCGStab / PBiCG / smoothSolver / diagonalSolver drivers.
 //
 // Replaces (OpenFOAM-dev @940e28f, not vendored in the reference):
@@ -10,12 +10,15 @@
 // solver/pEqn.H:39, solver/UEqn.H:19, solver/YEEqn.H:60,111, solver/rhoEqn.H:43.
 //
 // Exactness: the serial face-order sweeps of the reference carry a dependency
-// DAG (owner -> neighbour).  Cells are stored level-major, one kernel launch
-// per dependency level, all launches of one sweep pair captured once in a
-// hipGraph.  Inside a level every row is accumulated in the reference's face
-// order, and the library is compiled with -ffp-contract=off, so the sweeps are
-// bitwise equal to the serial loops; only the dot products (two-stage tree
-// sums instead of one serial sum) differ, in the last bits.
+// DAG (owner -> neighbour).  Every sweep has one form per sweep mode: matrices
+// with a tile plan (sweepMode 2) take the tiled wavefront sweeps of
+// ffm_tile.hip; all others -- unstructured meshes, GAMG coarse levels,
+// FFM_SWEEP=levels -- the dataflow sweeps below: cells stored level-major, ONE
+// launch per sweep (pair) in which every cell waits for the values it needs.
+// Every row is accumulated in the reference's face order, and the library is
+// compiled with -ffp-contract=off, so the sweeps are bitwise equal to the
+// serial loops; only the dot products (two-stage tree sums instead of one
+// serial sum) differ, in the last bits.
 //
 // Scalars (alpha, beta, residual norms) stay on the device; the host reads the
 // residual back once per iteration (twice for PBiCGStab) to take the
@@ -249,243 +252,9 @@ static int partial_sum_to(ffm_ctx *c, int nb, int slot, int nSums = 1)
     return FFM_OK;
 }
 
-// ------------------------------------------------------------ level kernels ---
-// A launch covers the cells [c0,c1) of one dependency level (contiguous in the level-major
-// numbering).  c0 need not be slice-aligned: thread t handles cell (c0 & ~63) + t so that a
-// wave still maps onto one slice and every index load stays unit-stride.
-
-// calcReciprocalD, forward part:  rD[c] = diag[c] - sum_k upper*lower/rD[l]   (not yet inverted)
-template <int W>
-__global__ void k_rD_level(int c0, int c1, LduView v, const double *__restrict__ upper,
-                           const double *__restrict__ lower, const double *__restrict__ diag, double *__restrict__ rD)
-{
-    const int c = (c0 & ~63) + blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < c0 || c >= c1) return;
-    RowEnt<W> L; load_lower<W>(v, c, L);
-    double au[W], al[W], rn[W];
-#pragma unroll
-    for (int s = 0; s < W; s++) { au[s] = upper[L.f[s]]; al[s] = lower[L.f[s]]; rn[s] = L.on[s] ? rD[L.nb[s]] : 1.0; }
-    double d = diag[c];
-#pragma unroll
-    for (int s = 0; s < W; s++) if (L.on[s]) d -= au[s] * al[s] / rn[s];
-    rD[c] = d;
-}
-
-// forward sweep of one level:  w[c] = rD[c]*r[c] - sum_k rD[c]*coef[f]*w[l]
-template <int W>
-__global__ void k_fwd_level(int c0, int c1, LduView v, const double *__restrict__ coef,
-                            const double *__restrict__ rD, const double *__restrict__ r, double *__restrict__ w)
-{
-    const int c = (c0 & ~63) + blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < c0 || c >= c1) return;
-    RowEnt<W> L; load_lower<W>(v, c, L);
-    const double rd = rD[c], rc = r[c];
-    double a[W], wn[W];
-#pragma unroll
-    for (int s = 0; s < W; s++) { a[s] = coef[L.f[s]]; wn[s] = L.on[s] ? w[L.nb[s]] : 0.0; }
-    double wc = rd * rc;
-#pragma unroll
-    for (int s = 0; s < W; s++) if (L.on[s]) wc -= rd * a[s] * wn[s];
-    w[c] = wc;
-}
-
-// backward sweep of one level: w[c] -= rD[c]*coef[f]*w[u], faces of c in descending order
-template <int W>
-__global__ void k_bwd_level(int p0, int p1, const int *__restrict__ order, LduView v, const double *__restrict__ coef,
-                            const double *__restrict__ rD, double *__restrict__ w)
-{
-    int c;
-    if (order) { const int p = p0 + blockIdx.x * blockDim.x + threadIdx.x; if (p >= p1) return; c = order[p]; }
-    else { c = (p0 & ~63) + blockIdx.x * blockDim.x + threadIdx.x; if (c < p0 || c >= p1) return; }
-    RowEnt<W> U; load_upper<W, true>(v, c, U);          // block-Jacobi: ghost neighbours are ignored
-    const double rd = rD[c];
-    double wc = w[c];
-    double a[W], wn[W];
-#pragma unroll
-    for (int s = 0; s < W; s++) { a[s] = coef[U.f[s]]; wn[s] = U.on[s] ? w[U.nb[s]] : 0.0; }
-#pragma unroll
-    for (int s = W - 1; s >= 0; s--) if (U.on[s]) wc -= rd * a[s] * wn[s];
-    w[c] = wc;
-}
-
-// Gauss-Seidel forward level: psi_c = (bP_c - sum_lower lower*psi_l - sum_upper upper*psi_u)/diag_c;
-// the value after the lower sum is kept in bSave for the reverse sweep of symGaussSeidel
-template <int W>
-__global__ void k_gs_fwd_level(int c0, int c1, LduView v, const double *__restrict__ upper,
-                               const double *__restrict__ lower, const double *__restrict__ diag,
-                               const double *__restrict__ bP, double *__restrict__ bSave, double *__restrict__ psi)
-{
-    const int c = (c0 & ~63) + blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < c0 || c >= c1) return;
-    RowEnt<W> L, U; load_lower<W>(v, c, L); load_upper<W>(v, c, U);
-    double al[W], au[W], pl[W], pu[W];
-#pragma unroll
-    for (int s = 0; s < W; s++) {
-        al[s] = lower[L.f[s]]; au[s] = upper[U.f[s]];
-        pl[s] = L.on[s] ? psi[L.nb[s]] : 0.0; pu[s] = U.on[s] ? psi[U.nb[s]] : 0.0;
-    }
-    double val = bP[c];
-#pragma unroll
-    for (int s = 0; s < W; s++) if (L.on[s]) val -= al[s] * pl[s];
-    bSave[c] = val;
-#pragma unroll
-    for (int s = 0; s < W; s++) if (U.on[s]) val -= au[s] * pu[s];
-    psi[c] = val / diag[c];
-}
-
-template <int W>
-__global__ void k_gs_bwd_level(int p0, int p1, const int *__restrict__ order, LduView v, const double *__restrict__ upper,
-                               const double *__restrict__ diag, const double *__restrict__ bSave, double *__restrict__ psi)
-{
-    int c;
-    if (order) { const int p = p0 + blockIdx.x * blockDim.x + threadIdx.x; if (p >= p1) return; c = order[p]; }
-    else { c = (p0 & ~63) + blockIdx.x * blockDim.x + threadIdx.x; if (c < p0 || c >= p1) return; }
-    RowEnt<W> U; load_upper<W>(v, c, U);
-    double au[W], pu[W];
-#pragma unroll
-    for (int s = 0; s < W; s++) { au[s] = upper[U.f[s]]; pu[s] = U.on[s] ? psi[U.nb[s]] : 0.0; }
-    double val = bSave[c];
-#pragma unroll
-    for (int s = 0; s < W; s++) if (U.on[s]) val -= au[s] * pu[s];
-    psi[c] = val / diag[c];
-}
-
-// ------------------------------------------------- single-workgroup sweeps ---
-// Small matrices (the coarse levels of a GAMG hierarchy, small unstructured meshes): one launch per dependency level costs ~3.6 us
-// each and these have hundreds of levels with a handful of cells.  Here ONE workgroup of 1024 threads walks all levels of a sweep
-// (and of the sweep pair of a preconditioner application / symGaussSeidel), one workgroup barrier per level.  Values written in an
-// earlier level are read with agent-scope loads (they bypass the CU's L1, where a line fetched for a neighbouring cell may hold the
-// old value); the barrier's release waits for the stores.  Per-cell arithmetic is that of the level kernels above, bit for bit.
-constexpr int SMALL_T = 1024;
-constexpr long FFM_SMALL_SWEEP_DEFAULT = 131072L;
-__device__ __forceinline__ double s_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-enum { SM_RD = 0, SM_PRECOND = 1, SM_GS = 2, SM_SYMGS = 3 };
-struct SmallArgs {
-    LduView v;
-    int nLevels, nBwd, N;
-    const int *fwdStart, *bwdRange, *order;
-    const double *upper, *lower, *diag, *cf, *cb, *r, *bP;
-    double *rD, *w, *bSave, *psi;
-};
-template <int MODE, int W>
-__global__ __launch_bounds__(SMALL_T) void k_small_sweep(SmallArgs a)
-{
-    const int tid = threadIdx.x;
-    // ---- forward levels
-    for (int Lv = 0; Lv < a.nLevels; Lv++) {
-        const int c0 = a.fwdStart[Lv], c1 = a.fwdStart[Lv + 1];
-        for (int c = c0 + tid; c < c1; c += SMALL_T) {
-            if (MODE == SM_RD) {
-                RowEnt<W> L; load_lower<W>(a.v, c, L);
-                double au[W], al[W], rn[W];
-#pragma unroll
-                for (int s = 0; s < W; s++) { au[s] = a.upper[L.f[s]]; al[s] = a.lower[L.f[s]]; rn[s] = L.on[s] ? s_ld(&a.rD[L.nb[s]]) : 1.0; }
-                double d = a.diag[c];
-#pragma unroll
-                for (int s = 0; s < W; s++) if (L.on[s]) d -= au[s] * al[s] / rn[s];
-                a.rD[c] = d;
-            } else if (MODE == SM_PRECOND) {
-                RowEnt<W> L; load_lower<W>(a.v, c, L);
-                const double rd = a.rD[c], rc = a.r[c];
-                double q[W], wn[W];
-#pragma unroll
-                for (int s = 0; s < W; s++) { q[s] = a.cf[L.f[s]]; wn[s] = L.on[s] ? s_ld(&a.w[L.nb[s]]) : 0.0; }
-                double wc = rd * rc;
-#pragma unroll
-                for (int s = 0; s < W; s++) if (L.on[s]) wc -= rd * q[s] * wn[s];
-                a.w[c] = wc;
-            } else {
-                RowEnt<W> L, U; load_lower<W>(a.v, c, L); load_upper<W>(a.v, c, U);
-                double al[W], au[W], pl[W], pu[W];
-#pragma unroll
-                for (int s = 0; s < W; s++) {
-                    al[s] = a.lower[L.f[s]]; au[s] = a.upper[U.f[s]];
-                    pl[s] = L.on[s] ? s_ld(&a.psi[L.nb[s]]) : 0.0; pu[s] = U.on[s] ? s_ld(&a.psi[U.nb[s]]) : 0.0;
-                }
-                double val = a.bP[c];
-#pragma unroll
-                for (int s = 0; s < W; s++) if (L.on[s]) val -= al[s] * pl[s];
-                a.bSave[c] = val;
-#pragma unroll
-                for (int s = 0; s < W; s++) if (U.on[s]) val -= au[s] * pu[s];
-                a.psi[c] = val / a.diag[c];
-            }
-        }
-        __syncthreads();
-    }
-    if (MODE == SM_RD) {            // rD = 1/rD (k_recip)
-        for (int c = tid; c < a.N; c += SMALL_T) a.rD[c] = 1.0 / s_ld(&a.rD[c]);
-        return;
-    }
-    if (MODE == SM_GS) return;
-    // ---- backward levels (preconditioner: level 0 = cells without owned faces, nothing to do there)
-    for (int b = (MODE == SM_PRECOND ? 1 : 0); b < a.nBwd; b++) {
-        const int p0 = a.bwdRange[2 * b], p1 = a.bwdRange[2 * b + 1];
-        for (int p = p0 + tid; p < p1; p += SMALL_T) {
-            const int c = a.order ? a.order[p] : p;
-            if (MODE == SM_PRECOND) {
-                RowEnt<W> U; load_upper<W, true>(a.v, c, U);          // block-Jacobi: ghost neighbours are ignored
-                const double rd = a.rD[c];
-                double wc = s_ld(&a.w[c]);
-                double q[W], wn[W];
-#pragma unroll
-                for (int s = 0; s < W; s++) { q[s] = a.cb[U.f[s]]; wn[s] = U.on[s] ? s_ld(&a.w[U.nb[s]]) : 0.0; }
-#pragma unroll
-                for (int s = W - 1; s >= 0; s--) if (U.on[s]) wc -= rd * q[s] * wn[s];
-                a.w[c] = wc;
-            } else {
-                RowEnt<W> U; load_upper<W>(a.v, c, U);
-                double au[W], pu[W];
-#pragma unroll
-                for (int s = 0; s < W; s++) { au[s] = a.upper[U.f[s]]; pu[s] = U.on[s] ? s_ld(&a.psi[U.nb[s]]) : 0.0; }
-                double val = s_ld(&a.bSave[c]);
-#pragma unroll
-                for (int s = 0; s < W; s++) if (U.on[s]) val -= au[s] * pu[s];
-                a.psi[c] = val / a.diag[c];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// usable for this matrix?  (level-scheduled mode, at most FFM_SMALL_SWEEP_CELLS owned cells -- 0 switches it off; default 0, or
-// 131072 when the dataflow sweeps are switched off)
-static bool small_usable(ffm_ldu *A)
-{
-    if (A->smallState) return A->smallState > 0;
-    const char *e = getenv("FFM_SMALL_SWEEP_CELLS");            // read per matrix: tests switch between the paths
-    const char *f = getenv("FFM_FLOW_SWEEP");
-    // measured (GAMG V-cycle at 96^3 and 200^3): the dataflow sweeps below beat this form at every size, so it is only the default
-    // where they are switched off
-    const long limit = e ? atol(e) : ((f && !strcmp(f, "0")) ? FFM_SMALL_SWEEP_DEFAULT : 0L);
-    A->smallState = -1;
-    if (A->sweepMode == 2 || A->nOwned > limit || A->nLevels < 1) return false;
-    std::vector<int> br(2 * (size_t)std::max(A->nBwdLevels, 1), 0);
-    for (int b = 0; b < A->nBwdLevels; b++) {
-        const int s = A->h_bwdLevelStart[b], e = A->h_bwdLevelStart[b + 1];
-        if (A->bwdContig) { br[2 * b] = A->h_bwdFirstCell[b]; br[2 * b + 1] = A->h_bwdFirstCell[b] + (e - s); }
-        else { br[2 * b] = s; br[2 * b + 1] = e; }
-    }
-    if (hipMalloc((void **)&A->smallFwdStart, sizeof(int) * (A->nLevels + 1)) != hipSuccess) return false;
-    if (hipMalloc((void **)&A->smallBwdRange, sizeof(int) * br.size()) != hipSuccess) return false;
-    if (ffm_h2d(A->ctx, A->smallFwdStart, A->h_fwdLevelStart.data(), sizeof(int) * (A->nLevels + 1)) != FFM_OK) return false;
-    if (ffm_h2d(A->ctx, A->smallBwdRange, br.data(), sizeof(int) * br.size()) != FFM_OK) return false;
-    A->smallState = 1;
-    return true;
-}
-static SmallArgs small_args(ffm_ldu *A)
-{
-    SmallArgs a{};
-    a.v = ffm_view(A); a.nLevels = A->nLevels; a.nBwd = A->nBwdLevels; a.N = A->nOwned;
-    a.fwdStart = A->smallFwdStart; a.bwdRange = A->smallBwdRange; a.order = A->bwdContig ? nullptr : A->bwdOrder;
-    a.upper = A->upper; a.lower = A->lower; a.diag = A->diag; a.rD = A->rD;
-    return a;
-}
-#define SMALL_LAUNCH(MODE, a) FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_small_sweep<MODE, W>), dim3(1), dim3(SMALL_T), 0, A->ctx->stream, a))
-
 // --------------------------------------------------------- dataflow sweeps ---
-// Level-scheduled matrices too large for one workgroup (unstructured meshes, the upper coarse levels of a GAMG hierarchy): instead of
-// one launch -- or one device-wide barrier -- per dependency level, ONE launch in which every cell waits for the values it needs.
+// Level-scheduled matrices (unstructured meshes, the coarse levels of a GAMG hierarchy): instead of one launch -- or one device-wide
+// barrier -- per dependency level, ONE launch in which every cell waits for the values it needs.
 // Workgroups take chunks of 256 cells by an atomic ticket, forward chunks in the level-major cell order, then backward chunks in
 // backward-level order: every value a cell waits for belongs to a chunk with a lower ticket, i.e. to a workgroup that is running or
 // has finished, so the grid drains whatever the dispatch order or the residency (the scheme of the tiled sweeps, ffm_tile.hip).
@@ -493,12 +262,18 @@ static SmallArgs small_args(ffm_ldu *A)
 // flag.  A lane never blocks in front of its store: the wait is a retry loop with the store inside and a wave-uniform exit (a ballot
 // over the lanes not yet done -- with a per-lane exit the compiler may sink the store behind the loop, where a finished lane would
 // wait for the lanes that wait for it), so a chain of dependent cells in one wavefront advances one link per trip.  Every wait is bounded and raises the abort word (reported when the solve ends).
-// Per-cell arithmetic is that of the level kernels above, term for term in the same order: results are bitwise equal.
+// Per-cell arithmetic is that of the serial face loops, term for term in the same order: results are bitwise equal.
+// Measured on one MI355X against one launch per dependency level (the form this replaced): a DIC application (two sweeps) in
+// level-major numbering 4.30 -> 2.36 ms at 200^3 (598 levels: 2.0 us per level and sweep, the store -> poll round trip between
+// workgroups on different XCDs; the poll's s_sleep makes no difference), 1.66 -> 1.05 ms at 100^3; a GAMG V-cycle 29.0 -> 15.5 ms at
+// 200^3 and 8.6 -> 5.8 ms at 96^3 (profiles/README.md)
 constexpr int FLOW_T = 256;            // measured: 64 is slower at 200^3 (3.6 against 2.36 ms per DIC application), 1024 equal there and slower on the GAMG levels
 constexpr unsigned FLOW_SPIN_LIMIT = 1u << 21;
 constexpr unsigned long long FLOW_SENT = 0xFFF8C0DEFEEDF10Full;       // a NaN no computation produces
 __device__ __forceinline__ bool f_pending(double v) { return (unsigned long long)__double_as_longlong(v) == FLOW_SENT; }
 __device__ __forceinline__ void f_st(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double s_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+enum { SM_RD = 0, SM_PRECOND = 1, SM_GS = 2, SM_SYMGS = 3 };
 struct FlowArgs {
     LduView v;
     int N, nChunkF, nChunkB, nap;
@@ -653,43 +428,6 @@ __global__ __launch_bounds__(FLOW_T) void k_flow_sweep(FlowArgs a)
     }
 }
 
-// usable for this matrix?  level-scheduled mode, not taken by the single-workgroup sweeps; FFM_FLOW_SWEEP=0 switches it off (one
-// launch per level, the round-1 path), FFM_FLOW_SWEEP=all takes every matrix whatever FFM_SMALL_SWEEP_CELLS says.
-// Measured on one MI355X: a DIC application (two sweeps) in level-major numbering 4.30 -> 2.36 ms at 200^3 (598 levels: 2.0 us per
-// level and sweep, the store -> poll round trip between workgroups on different XCDs; the poll's s_sleep makes no difference),
-// 1.66 -> 1.05 ms at 100^3; a GAMG V-cycle 29.0 -> 15.5 ms at 200^3 and 8.6 -> 5.8 ms at 96^3 (profiles/README.md)
-static bool flow_usable(ffm_ldu *A)
-{
-    if (A->flowState) return A->flowState > 0;
-    const char *e = getenv("FFM_FLOW_SWEEP");                   // read per matrix: tests switch between the paths
-    A->flowState = -1;
-    if (A->sweepMode == 2 || A->nLevels < 1 || A->nOwned < 1 || (e && !strcmp(e, "0"))) return false;
-    std::vector<int> ord((size_t)A->nOwned);
-    if (A->bwdContig) {
-        size_t k = 0;
-        for (int b = 0; b < A->nBwdLevels; b++)
-            for (int i = 0, n = A->h_bwdLevelStart[b + 1] - A->h_bwdLevelStart[b]; i < n; i++) ord[k++] = A->h_bwdFirstCell[b] + i;
-        if (k != ord.size()) return false;
-    } else {
-        if (hipStreamSynchronize(A->ctx->stream) != hipSuccess) return false;        // (uploaded on the context's non-blocking stream)
-        if (ffm_d2h(A->ctx, ord.data(), A->bwdOrder, sizeof(int) * ord.size()) != FFM_OK) return false;
-    }
-    if (hipMalloc((void **)&A->flowOrder, sizeof(int) * ord.size()) != hipSuccess) return false;
-    if (ffm_h2d(A->ctx, A->flowOrder, ord.data(), sizeof(int) * ord.size()) != FFM_OK) return false;
-    if (!A->sweepTicket) {
-        if (hipMalloc((void **)&A->sweepTicket, 2 * sizeof(unsigned int)) != hipSuccess) return false;
-        // on the context's stream: a null-stream hipMemset returns before it has run and is not ordered against that (non-blocking)
-        // stream -- it could zero the ticket counter in the middle of the first sweep
-        if (hipMemsetAsync(A->sweepTicket, 0, 2 * sizeof(unsigned int), A->ctx->stream) != hipSuccess) return false;
-    }
-    A->flowState = 1;
-    return true;
-}
-static bool flow_preferred(ffm_ldu *A)
-{
-    const char *e = getenv("FFM_FLOW_SWEEP");
-    return e && !strcmp(e, "all") && flow_usable(A);
-}
 static int flow_args(ffm_ldu *A, int mode, FlowArgs &a)
 {
     a = FlowArgs{};
@@ -704,17 +442,18 @@ static int flow_args(ffm_ldu *A, int mode, FlowArgs &a)
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
-#define FLOW_LAUNCH(MODE, a) FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_flow_sweep<MODE, W>), dim3((a).nChunkF + (a).nChunkB), dim3(FLOW_T), 0, A->ctx->stream, a))
+// (a matrix without owned cells has nothing to sweep: no launch)
+#define FLOW_LAUNCH(MODE, a) do { if ((a).nChunkF > 0) FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_flow_sweep<MODE, W>), dim3((a).nChunkF + (a).nChunkB), dim3(FLOW_T), 0, A->ctx->stream, a)); } while (0)
 
-// the abort word of the dataflow sweeps (a bounded wait ran out): reported when a solve ends
-int ffm_flow_check_abort(ffm_ldu *A)
+// the abort word of the tiled and the dataflow sweeps (a bounded wait ran out): reported when a solve ends
+int ffm_sweep_check_abort(ffm_ldu *A)
 {
-    if (A->flowState <= 0 || !A->sweepTicket) return FFM_OK;
     unsigned int h[2] = {0, 0};
     FFM_HIP(hipMemcpyAsync(h, A->sweepTicket, sizeof(h), hipMemcpyDeviceToHost, A->ctx->stream));
     FFM_HIP(hipStreamSynchronize(A->ctx->stream));
     if (h[1]) {
-        ffm_set_error("dataflow sweep timed out waiting for the value of a predecessor cell (abort word set)");
+        ffm_set_error(A->sweepMode == 2 ? "tiled sweep timed out waiting for a value of a predecessor group (abort word set)"
+                                        : "dataflow sweep timed out waiting for the value of a predecessor cell (abort word set)");
         unsigned int z = 0;
         ffm_h2d(A->ctx, A->sweepTicket + 1, &z, sizeof(z));
         return FFM_ERR_HIP;
@@ -722,82 +461,18 @@ int ffm_flow_check_abort(ffm_ldu *A)
     return FFM_OK;
 }
 
-// blocks needed to cover cells [c0,c1) when thread 0 of block 0 sits on the slice start of c0
-static inline int level_grid(int c0, int c1) { return ffm_grid(c1 - (c0 & ~63), 256); }
-
-// ------------------------------------------------------ level-sweep drivers ---
-enum { SW_RD = 1, SW_PRECOND = 2, SW_GS = 3, SW_SYMGS = 4 };
-
-template <class Body>
-static int run_graphed(ffm_ldu *A, const SweepGraphKey &key, Body body)
-{
-    static const bool noGraph = getenv("FFM_NO_GRAPH") != nullptr;
-    hipStream_t s = A->ctx->stream;
-    if (noGraph) return body();
-    auto it = A->graphs.find(key);
-    if (it == A->graphs.end()) {
-        hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
-        FFM_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int rc = body();
-        hipError_t e = hipStreamEndCapture(s, &g);
-        if (rc) { if (g) hipGraphDestroy(g); return rc; }
-        if (e != hipSuccess) { ffm_set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); return FFM_ERR_HIP; }
-        e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-        hipGraphDestroy(g);
-        if (e != hipSuccess) { ffm_set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); return FFM_ERR_HIP; }
-        if (A->graphs.size() >= FFM_MAX_SWEEP_GRAPHS) {        // bounded cache: drop the oldest graph
-            auto old = A->graphs.find(A->graphOrder.front());
-            if (old != A->graphs.end()) { hipGraphExecDestroy(old->second); A->graphs.erase(old); }
-            A->graphOrder.erase(A->graphOrder.begin());
-        }
-        it = A->graphs.emplace(key, ge).first;
-        A->graphOrder.push_back(key);
-    }
-    FFM_HIP(hipGraphLaunch(it->second, s));
-    return FFM_OK;
-}
-
-static inline void bwd_range(const ffm_ldu *A, int b, int &p0, int &p1, const int *&order)
-{
-    const int s = A->h_bwdLevelStart[b], e = A->h_bwdLevelStart[b + 1];
-    if (A->bwdContig) { p0 = A->h_bwdFirstCell[b]; p1 = p0 + (e - s); order = nullptr; }
-    else { p0 = s; p1 = e; order = A->bwdOrder; }
-}
-
 // rD = 1/(diag - sum upper*lower/rD[l]) in face order (DIC: lower == upper)
 static int calc_rD(ffm_ldu *A)
 {
-    hipStream_t s = A->ctx->stream;
     if (A->sweepMode == 2) {
         FFM_TRY(ffm_tile_calc_rD(A));
-        hipLaunchKernelGGL(k_recip, dim3(sgrid(A->nOwned)), dim3(256), 0, s, (long)A->nOwned, A->rD, A->rD);
+        hipLaunchKernelGGL(k_recip, dim3(sgrid(A->nOwned)), dim3(256), 0, A->ctx->stream, (long)A->nOwned, A->rD, A->rD);
         FFM_HIP(hipGetLastError());
         return FFM_OK;
     }
-    if (!flow_preferred(A) && small_usable(A)) {
-        SmallArgs a = small_args(A);
-        SMALL_LAUNCH(SM_RD, a);
-        FFM_HIP(hipGetLastError());
-        return FFM_OK;
-    }
-    if (flow_usable(A)) {
-        FlowArgs a; FFM_TRY(flow_args(A, SM_RD, a));
-        FLOW_LAUNCH(SM_RD, a);
-        FFM_HIP(hipGetLastError());
-        return FFM_OK;
-    }
-    SweepGraphKey key{SW_RD, {A->lower, A->upper, A->diag, A->rD, nullptr, nullptr}};
-    FFM_TRY(run_graphed(A, key, [&]() -> int {
-        for (int L = 0; L < A->nLevels; L++) {
-            const int c0 = A->h_fwdLevelStart[L], c1 = A->h_fwdLevelStart[L + 1];
-            if (c1 == c0) continue;
-            FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_rD_level<W>, dim3(level_grid(c0, c1)), dim3(256), 0, s, c0, c1, ffm_view(A),
-                               A->upper, A->lower, A->diag, A->rD));
-        }
-        hipLaunchKernelGGL(k_recip, dim3(sgrid(A->nOwned)), dim3(256), 0, s, (long)A->nOwned, A->rD, A->rD);
-        FFM_HIP(hipGetLastError());
-        return FFM_OK;
-    }));
+    FlowArgs a; FFM_TRY(flow_args(A, SM_RD, a));
+    FLOW_LAUNCH(SM_RD, a);
+    FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
 
@@ -827,41 +502,15 @@ int ffm_precond_apply_i(ffm_ldu *A, int precond, bool transpose, const double *r
     const long N = A->nOwned;
     if (precond == FFM_NONE) { hipLaunchKernelGGL(k_copy, dim3(sgrid(N)), dim3(256), 0, s, N, w, r); FFM_HIP(hipGetLastError()); return FFM_OK; }
     if (precond == FFM_DIAGONALP) { hipLaunchKernelGGL(k_mul, dim3(sgrid(N)), dim3(256), 0, s, N, w, A->rD, r); FFM_HIP(hipGetLastError()); return FFM_OK; }
-    // DIC: fwd upper / bwd upper.  DILU: fwd lower / bwd upper.  DILU^T: fwd upper / bwd lower.
-    const double *cf = (precond == FFM_DIC) ? A->upper : (transpose ? A->upper : A->lower);
-    const double *cb = (precond == FFM_DIC) ? A->upper : (transpose ? A->lower : A->upper);
     if (A->sweepMode == 2) return ffm_tile_precond(A, precond, transpose, r, w);
-    if (!flow_preferred(A) && small_usable(A)) {
-        SmallArgs a = small_args(A);
-        a.cf = cf; a.cb = cb; a.r = r; a.w = w;
-        SMALL_LAUNCH(SM_PRECOND, a);
-        FFM_HIP(hipGetLastError());
-        return FFM_OK;
-    }
-    if (flow_usable(A)) {
-        FlowArgs a; FFM_TRY(flow_args(A, SM_PRECOND, a));
-        a.cf = cf; a.cb = cb; a.r = r; a.w = w;
-        FLOW_LAUNCH(SM_PRECOND, a);
-        FFM_HIP(hipGetLastError());
-        return FFM_OK;
-    }
-    SweepGraphKey key{SW_PRECOND + 16 * (transpose ? 1 : 0) + 32 * precond, {r, w, cf, cb, A->rD, nullptr}};
-    return run_graphed(A, key, [&]() -> int {
-        for (int L = 0; L < A->nLevels; L++) {
-            const int c0 = A->h_fwdLevelStart[L], c1 = A->h_fwdLevelStart[L + 1];
-            if (c1 == c0) continue;
-            FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_fwd_level<W>, dim3(level_grid(c0, c1)), dim3(256), 0, s, c0, c1, ffm_view(A), cf, A->rD, r, w));
-        }
-        // backward level 0 = cells without owned faces: nothing to do
-        for (int b = 1; b < A->nBwdLevels; b++) {
-            int p0, p1; const int *order; bwd_range(A, b, p0, p1, order);
-            if (p1 == p0) continue;
-            FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_bwd_level<W>, dim3(order ? ffm_grid(p1 - p0, 256) : level_grid(p0, p1)), dim3(256), 0, s,
-                                                       p0, p1, order, ffm_view(A), cb, A->rD, w));
-        }
-        FFM_HIP(hipGetLastError());
-        return FFM_OK;
-    });
+    // DIC: fwd upper / bwd upper.  DILU: fwd lower / bwd upper.  DILU^T: fwd upper / bwd lower.
+    FlowArgs a; FFM_TRY(flow_args(A, SM_PRECOND, a));
+    a.cf = (precond == FFM_DIC) ? A->upper : (transpose ? A->upper : A->lower);
+    a.cb = (precond == FFM_DIC) ? A->upper : (transpose ? A->lower : A->upper);
+    a.r = r; a.w = w;
+    FLOW_LAUNCH(SM_PRECOND, a);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
 }
 
 // GaussSeidelSmoother::smooth / symGaussSeidelSmoother::smooth
@@ -880,9 +529,9 @@ int ffm_gs_smooth_i(ffm_ldu *A, bool sym, int nSweeps, double *psi, const double
         }
         // decomposed block: every sweep starts from the neighbour ranks' current values, whatever form the sweep takes (the
         // reference's smoothers update the interfaces before every sweep: GaussSeidelSmoother.C, initMatrixInterfaces /
-        // updateMatrixInterfaces inside the sweep loop) -- the single-workgroup, dataflow and per-level forms read psi of the ghost cells
+        // updateMatrixInterfaces inside the sweep loop) -- the dataflow sweeps read psi of the ghost cells
         if (!A->ghNbrRank.empty()) FFM_TRY(ffm_ghost_exchange(A, psi));
-        if (A->sweepMode == 2 && ffm_tile_gs_usable(A)) {
+        if (A->sweepMode == 2) {
             if (!A->ghNbrRank.empty()) {        // move the ghost cells' terms into bPrime
                 if (bUse == b) { hipLaunchKernelGGL(k_copy, dim3(sgrid(N)), dim3(256), 0, s, N, bP, b); bUse = bP; }
                 FFM_TRY(ffm_tile_gs_ghost_terms(A, psi, bP));
@@ -891,37 +540,10 @@ int ffm_gs_smooth_i(ffm_ldu *A, bool sym, int nSweeps, double *psi, const double
             FFM_TRY(ffm_tile_gs(A, sym, psi, bUse, bSave, A->gsProd));
             continue;
         }
-        if (!flow_preferred(A) && small_usable(A)) {
-            SmallArgs a = small_args(A);
-            a.bP = bUse; a.bSave = bSave; a.psi = psi;
-            if (sym) SMALL_LAUNCH(SM_SYMGS, a); else SMALL_LAUNCH(SM_GS, a);
-            FFM_HIP(hipGetLastError());
-            continue;
-        }
-        if (flow_usable(A)) {
-            FlowArgs a; FFM_TRY(flow_args(A, sym ? SM_SYMGS : SM_GS, a));
-            a.bP = bUse; a.psi = psi;
-            if (sym) FLOW_LAUNCH(SM_SYMGS, a); else FLOW_LAUNCH(SM_GS, a);
-            FFM_HIP(hipGetLastError());
-            continue;
-        }
-        SweepGraphKey key{sym ? SW_SYMGS : SW_GS, {psi, bUse, A->lower, A->upper, A->diag, bSave}};
-        FFM_TRY(run_graphed(A, key, [&]() -> int {
-            for (int L = 0; L < A->nLevels; L++) {
-                const int c0 = A->h_fwdLevelStart[L], c1 = A->h_fwdLevelStart[L + 1];
-                if (c1 == c0) continue;
-                FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_gs_fwd_level<W>, dim3(level_grid(c0, c1)), dim3(256), 0, s, c0, c1, ffm_view(A),
-                                                           A->upper, A->lower, A->diag, bUse, bSave, psi));
-            }
-            if (sym) for (int bl = 0; bl < A->nBwdLevels; bl++) {
-                int p0, p1; const int *order; bwd_range(A, bl, p0, p1, order);
-                if (p1 == p0) continue;
-                FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_gs_bwd_level<W>, dim3(order ? ffm_grid(p1 - p0, 256) : level_grid(p0, p1)), dim3(256),
-                                                           0, s, p0, p1, order, ffm_view(A), A->upper, A->diag, bSave, psi));
-            }
-            FFM_HIP(hipGetLastError());
-            return FFM_OK;
-        }));
+        FlowArgs a; FFM_TRY(flow_args(A, sym ? SM_SYMGS : SM_GS, a));
+        a.bP = bUse; a.psi = psi;
+        if (sym) FLOW_LAUNCH(SM_SYMGS, a); else FLOW_LAUNCH(SM_GS, a);
+        FFM_HIP(hipGetLastError());
     }
     return FFM_OK;
 }
@@ -1190,7 +812,7 @@ extern "C" int ffm_solve_d(ffm_ldu *A, int solver, int precond, double tol, doub
         FFM_TRY(ffm_from_internal(A, pi, psi_d));
     }
     FFM_HIP(hipStreamSynchronize(A->ctx->stream));
-    if (A->sweepMode == 2) FFM_TRY(ffm_tile_check_abort(A)); else FFM_TRY(ffm_flow_check_abort(A));
+    FFM_TRY(ffm_sweep_check_abort(A));
     return FFM_OK;
 }
 
@@ -1354,7 +976,7 @@ extern "C" int ffm_solve_multi_d(ffm_ldu *A, int nSys, int solver, int precond, 
     }
     FFM_TRY(pbicgstab_multi(A, precond, k, nSys, L));
     FFM_HIP(hipStreamSynchronize(c->stream));
-    FFM_TRY(ffm_tile_check_abort(A));
+    FFM_TRY(ffm_sweep_check_abort(A));
     return FFM_OK;
 }
 
@@ -1380,7 +1002,7 @@ extern "C" int ffm_precond_setup(ffm_ldu *A, int precond, double *rD_out_d)
     FFM_TRY(ffm_precond_setup_i(A, precond));
     if (rD_out_d) FFM_TRY(ffm_from_internal(A, A->rD, rD_out_d));
     FFM_HIP(hipStreamSynchronize(A->ctx->stream));
-    if (A->sweepMode == 2) FFM_TRY(ffm_tile_check_abort(A)); else FFM_TRY(ffm_flow_check_abort(A));
+    FFM_TRY(ffm_sweep_check_abort(A));
     return FFM_OK;
 }
 
@@ -1417,7 +1039,7 @@ extern "C" int ffm_precond_apply(ffm_ldu *A, int precond, int transpose, const d
         FFM_TRY(ffm_from_internal(A, wi, w_d));
     }
     FFM_HIP(hipStreamSynchronize(A->ctx->stream));
-    if (A->sweepMode == 2) FFM_TRY(ffm_tile_check_abort(A)); else FFM_TRY(ffm_flow_check_abort(A));
+    FFM_TRY(ffm_sweep_check_abort(A));
     return FFM_OK;
 }
 
@@ -1432,6 +1054,6 @@ extern "C" int ffm_gs_smooth(ffm_ldu *A, int symmetric_sweep, int nSweeps, doubl
         FFM_TRY(ffm_from_internal(A, A->permIn[2], psi_d));
     }
     FFM_HIP(hipStreamSynchronize(A->ctx->stream));
-    if (A->sweepMode == 2) FFM_TRY(ffm_tile_check_abort(A)); else FFM_TRY(ffm_flow_check_abort(A));
+    FFM_TRY(ffm_sweep_check_abort(A));
     return FFM_OK;
 }

@@ -21,7 +21,7 @@
 //     FMAs, one LDS write and one barrier;
 //   * groups are handed out by an atomic ticket in topological order, so a workgroup only waits for groups that are
 //     already running or finished (no residency assumption, no deadlock); every spin is bounded and raises the abort word
-//     that ffm_tile_check_abort() reports when the solve ends.
+//     that ffm_sweep_check_abort() reports when the solve ends.
 #include "ffm_internal.hpp"
 #include "ffm_device.hpp"
 #include <algorithm>
@@ -54,7 +54,6 @@ struct TileDir {            // one sweep direction (device arrays)
     unsigned short *code = nullptr;   // [4*nOwn] per cell: 3 neighbour codes = the LDS slot holding the neighbour's value when the cell is computed
                                       // (ring slot (nb - group start) mod T_RING, or T_RING + parity(entry)*T_XMAX + external index; T_NONE: no neighbour), publish slot | T_NONE
     int *src = nullptr;         // [3*nOwn] native coefficient index of each neighbour slot (-1: none)
-    int *nbrCell = nullptr;     // [3*nOwn] the neighbour cell of each slot (-1: none)
     double *coefU = nullptr, *coefL = nullptr;        // [3*nOwn] gathered upper / lower coefficients (lazily allocated)
     unsigned long epochU = ~0ul, epochL = ~0ul;
     double *mail = nullptr;     // [nPub + 1] (inside ffm_tile_plan::mailAll)
@@ -68,26 +67,15 @@ struct ffm_tile_plan {
     long nMail = 0;
     double *mailMulti = nullptr;    // [FFM_TILE_MAXSYS][nMail]: the mailboxes of the multi-system sweeps (k_tile_m), allocated on first use
     unsigned long long *trace = nullptr;    // diagnostics (ffm_debug_tile_trace): per group {start, first entry done, end, re-loads} of the last launch
-    // ---- general backward order: when the backward dependency order inside a group is not the mirror image of the forward
-    // one (baffles, unstructured meshes), the backward sweep runs in "position space": position q holds cell cellOf[q]
-    // (cells of a group sorted by backward level), all backward streams are indexed by position, and the vectors of a
-    // sweep are permuted into / out of position space by a gather / scatter pass around the kernel
-    bool mirror = true;
-    const int *cellOf = nullptr;    // [nOwn] (= ffm_ldu::bwdCells, not owned)
-    double *wp = nullptr, *rDp = nullptr;
-    unsigned long rDpEpoch = ~0ul; int rDpKind = -1;
     // ---- tiled Amul (symmetric matrices): same groups and entries as the forward sweep
     bool amulUsable = false;
-    bool gsTables = false;          // the cell-space upper-neighbour tables below exist (Gauss-Seidel sweeps, Amul tail)
+    bool gsTables = false;          // the upper-neighbour and tail tables below exist (Gauss-Seidel sweeps, Amul tail)
     std::vector<int> grpEntHost;    // forward entries of each group (host copy)
     int4 *arec = nullptr;           // [nEnt + pad] {first cell, cells | externals << 16, first index into aext, 0}
     uint4 *acode = nullptr;         // [nOwn] 8 x 16 bit: 3 lower codes, 3 upper codes (A_* encoding below), 2 spare
     int2 *aext = nullptr;           // per external reference {cell whose x is needed, native index of the coefficient or -1}
-    // owned upper neighbours of every cell in CELL space (the backward direction's tables are in position space when
-    // !mirror): native coefficient index and neighbour cell of slot k, and the upper coefficients gathered through them
-    int *upSrcCell = nullptr, *upNbrCell = nullptr;
-    double *upCoefCell = nullptr, *diagp = nullptr;
-    unsigned long upCoefEpoch = ~0ul, diagpEpoch = ~0ul;
+    // owned upper neighbours of every cell: the neighbour cell of slot k (the upper coefficients are the backward direction's)
+    int *upNbrCell = nullptr;
     int nSeg = 0;                   // workgroups of the tiled Amul: a segment = a run of entries of one group
     int4 *aseg = nullptr;           // [nSeg] {group, first entry, end entry, end entry of the group}
     double *amulPartials = nullptr; // [nSeg]
@@ -116,16 +104,16 @@ bool ffm_tile_fv_segments(ffm_ldu *A, int runLength, FfmFvSegs *out)
 
 static void free_dir(TileDir &d)
 {
-    hipFree(d.grpEnt); hipFree(d.rec); hipFree(d.extSrc); hipFree(d.code); hipFree(d.src); hipFree(d.nbrCell); hipFree(d.coefU); hipFree(d.coefL);
+    hipFree(d.grpEnt); hipFree(d.rec); hipFree(d.extSrc); hipFree(d.code); hipFree(d.src); hipFree(d.coefU); hipFree(d.coefL);
     d = TileDir();
 }
 void ffm_tile_free(ffm_ldu *A)
 {
     if (!A->tile) return;
     free_dir(A->tile->f); free_dir(A->tile->b);
-    hipFree(A->tile->mailAll); hipFree(A->tile->mailMulti); hipFree(A->tile->trace); hipFree(A->tile->wp); hipFree(A->tile->rDp);
+    hipFree(A->tile->mailAll); hipFree(A->tile->mailMulti); hipFree(A->tile->trace);
     hipFree(A->tile->arec); hipFree(A->tile->acode); hipFree(A->tile->aext); hipFree(A->tile->aseg); hipFree(A->tile->amulPartials);
-    hipFree(A->tile->fvSeg); hipFree(A->tile->upSrcCell); hipFree(A->tile->upNbrCell); hipFree(A->tile->upCoefCell); hipFree(A->tile->diagp);
+    hipFree(A->tile->fvSeg); hipFree(A->tile->upNbrCell);
     hipFree(A->tile->tailCell); hipFree(A->tile->tailStart); hipFree(A->tile->tailFace); hipFree(A->tile->tailNbr);
     delete A->tile; A->tile = nullptr;
 }
@@ -241,79 +229,6 @@ static int build_dir(ffm_ldu *A, bool fwd, const std::vector<int> &lvl, const st
     for (int k = 0; k < 2 * T_PF + 2; k++) rec.push_back(make_int4(0, 0, 0, 0));      // read-ahead padding
     for (int k = 0; k < T_THREADS; k++) extSrc.push_back(0);
     FFM_TRY(upv(A->ctx, &D.grpEnt, grpEnt)); FFM_TRY(upv(A->ctx, &D.rec, rec)); FFM_TRY(upv(A->ctx, &D.extSrc, extSrc)); FFM_TRY(upv(A->ctx, &D.code, code)); FFM_TRY(upv(A->ctx, &D.src, src));
-    if (!fwd) FFM_TRY(upv(A->ctx, &D.nbrCell, nbr));
-    return FFM_OK;
-}
-
-
-// Backward direction in position space (see ffm_tile_plan::mirror): position q of the group-major array bwdCells holds the
-// cell processed q-th; neighbours = the owned upper neighbours of that cell, referred to by their positions (always smaller
-// inside the group).  Same outputs as build_dir, every per-cell array indexed by position.
-static int build_dir_pos(ffm_ldu *A, const std::vector<int> &bl, const std::vector<int> &grpCell, const std::vector<int> &grpOfCell,
-                         const std::vector<int> &bwdCells, TileDir &D, bool &ok)
-{
-    const int G = (int)grpCell.size() - 1, nOwn = A->nOwned, W = T_W;
-    std::vector<int> posOf(nOwn);
-    for (int q = 0; q < nOwn; q++) posOf[bwdCells[q]] = q;
-    std::vector<int> nbr((size_t)W * nOwn, -1), src((size_t)W * nOwn, -1);        // neighbour POSITIONS
-    std::vector<unsigned char> exposed(nOwn, 0);                                   // by position
-    auto isExt = [&](int q, int nq) { return grpOfCell[bwdCells[nq]] != grpOfCell[bwdCells[q]] || std::abs(q - nq) > T_RINGD; };
-    for (int q = 0; q < nOwn; q++) {
-        const int c = bwdCells[q], sl = c >> 6, lane = c & 63, wdt = (A->h_upOff[sl + 1] - A->h_upOff[sl]) / 64;
-        int k = 0;
-        for (int s = 0; s < wdt; s++) {
-            const int e = A->h_upOff[sl] + s * 64 + lane, nb = A->h_upNbr[e];
-            if (nb < 0 || nb >= nOwn) continue;
-            if (k >= W) { ok = false; return FFM_OK; }
-            const int nq = posOf[nb];
-            if (grpOfCell[nb] == grpOfCell[c] && nq >= q) { ok = false; return FFM_OK; }      // must have been processed earlier
-            nbr[(size_t)W * q + k] = nq; src[(size_t)W * q + k] = e;
-            if (isExt(q, nq)) exposed[nq] = 1;
-            k++;
-        }
-    }
-    std::vector<unsigned short> code((size_t)4 * nOwn, (unsigned short)T_NONE);
-    std::vector<int> grpEnt(G + 1, 0), mailIdx(nOwn, -1);                          // mailIdx by position
-    std::vector<int4> rec;
-    int nPub = 0;
-    auto extRefs = [&](int q) { int n = 0; for (int k = 0; k < W; k++) { const int nq = nbr[(size_t)W * q + k]; if (nq >= 0 && isExt(q, nq)) n++; } return n; };
-    for (int g = 0; g < G; g++) {
-        const int gs = grpCell[g], ge = grpCell[g + 1];
-        int prevLevel = -1;
-        for (int q = gs; q < ge;) {
-            int e = q, nx = 0;
-            while (e < ge && bl[bwdCells[e]] == bl[bwdCells[q]] && e - q < T_ENT) { const int x = extRefs(e); if (e > q && nx + x > T_XMAX) break; nx += x; e++; }
-            if (bl[bwdCells[q]] < prevLevel) { ok = false; return FFM_OK; }
-            prevLevel = bl[bwdCells[q]];
-            int slot = 0;
-            for (int p = q; p < e; p++) if (exposed[p]) { code[(size_t)4 * p + 3] = (unsigned short)slot; mailIdx[p] = nPub + slot; slot++; }
-            rec.push_back(make_int4(q, (e - q) | (nx << 16), nPub, 0));
-            nPub += slot;
-            q = e;
-        }
-        grpEnt[g + 1] = (int)rec.size();
-    }
-    std::vector<int> extSrc;
-    for (size_t ei = 0; ei < rec.size(); ei++) {
-        int4 &R = rec[ei];
-        const int q0 = R.x, cnt = R.y & 0xFFFF;
-        const int gs = cnt ? grpCell[grpOfCell[bwdCells[q0]]] : 0;
-        R.w = (int)extSrc.size();
-        int t = 0;
-        for (int q = q0; q < q0 + cnt; q++) for (int k = 0; k < W; k++) {
-            const int nq = nbr[(size_t)W * q + k];
-            if (nq < 0) continue;
-            if (isExt(q, nq)) {
-                if (mailIdx[nq] < 0) { ffm_set_error("internal: tile plan references an unpublished cell"); return FFM_ERR_ADDR; }
-                code[(size_t)4 * q + k] = (unsigned short)(T_RING + (int)(ei & 1) * T_XMAX + t); extSrc.push_back(mailIdx[nq]); t++;
-            } else code[(size_t)4 * q + k] = (unsigned short)((nq - gs) & (T_RING - 1));
-        }
-        if (t != (R.y >> 16)) { ffm_set_error("internal: tile plan external count mismatch"); return FFM_ERR_ADDR; }
-    }
-    D.nEnt = (int)rec.size(); D.nPub = nPub;
-    for (int k = 0; k < 2 * T_PF + 2; k++) rec.push_back(make_int4(0, 0, 0, 0));
-    for (int k = 0; k < T_THREADS; k++) extSrc.push_back(0);
-    FFM_TRY(upv(A->ctx, &D.grpEnt, grpEnt)); FFM_TRY(upv(A->ctx, &D.rec, rec)); FFM_TRY(upv(A->ctx, &D.extSrc, extSrc)); FFM_TRY(upv(A->ctx, &D.code, code)); FFM_TRY(upv(A->ctx, &D.src, src));
     return FFM_OK;
 }
 
@@ -336,10 +251,10 @@ static int build_amul(ffm_ldu *A, const std::vector<int> &grpOfCell, const std::
 {
     ffm_tile_plan *T = A->tile;
     const int nOwn = A->nOwned, nEnt = (int)recF.size();
-    // ---- cell-space tables of the owned upper neighbours + the faces towards ghost cells (Gauss-Seidel sweeps, Amul tail):
+    // ---- tables of the owned upper neighbours + the faces towards ghost cells (Gauss-Seidel sweeps, Amul tail):
     // structural requirements only (<= 3 owned upper neighbours, ghost neighbours after the owned ones in slot order)
     std::vector<int> tailCell, tailStart(1, 0), tailFace, tailNbr;
-    std::vector<int> upSrc((size_t)3 * nOwn, -1), upNb((size_t)3 * nOwn, -1);
+    std::vector<int> upNb((size_t)3 * nOwn, -1);
     for (int c = 0; c < nOwn; c++) {
         const int sl = c >> 6, lane = c & 63;
         const int uw = (A->h_upOff[sl + 1] - A->h_upOff[sl]) / 64;
@@ -353,13 +268,13 @@ static int build_amul(ffm_ldu *A, const std::vector<int> &grpOfCell, const std::
                 tailFace.push_back(idx); tailNbr.push_back(nb);
                 continue;
             }
-            if (ghostSeen || k >= 3) return FFM_OK;                      // owned after ghost, or too many: no cell-space tables
-            upSrc[(size_t)3 * c + k] = idx; upNb[(size_t)3 * c + k] = nb;
+            if (ghostSeen || k >= 3) return FFM_OK;                      // owned after ghost, or too many: no tables
+            upNb[(size_t)3 * c + k] = nb;
             k++;
         }
         if (ghostSeen) tailStart.push_back((int)tailFace.size());
     }
-    FFM_TRY(upv(A->ctx, &T->upSrcCell, upSrc)); FFM_TRY(upv(A->ctx, &T->upNbrCell, upNb));
+    FFM_TRY(upv(A->ctx, &T->upNbrCell, upNb));
     T->nTail = (int)tailCell.size();
     FFM_TRY(upv(A->ctx, &T->tailCell, tailCell)); FFM_TRY(upv(A->ctx, &T->tailStart, tailStart)); FFM_TRY(upv(A->ctx, &T->tailFace, tailFace)); FFM_TRY(upv(A->ctx, &T->tailNbr, tailNbr));
     T->gsTables = true;
@@ -393,7 +308,7 @@ static int build_amul(ffm_ldu *A, const std::vector<int> &grpOfCell, const std::
                 }
                 k++;
             }
-            // owned upper neighbours in slot order (cell-space tables above)
+            // owned upper neighbours in slot order (tables above)
             for (k = 0; k < 3; k++) {
                 const int nb = upNb[(size_t)3 * c + k];
                 if (nb < 0) break;
@@ -429,8 +344,7 @@ static int build_amul(ffm_ldu *A, const std::vector<int> &grpOfCell, const std::
     return FFM_OK;
 }
 
-int ffm_tile_build(ffm_ldu *A, const std::vector<int> &lev, const std::vector<int> &bl, const std::vector<int> &grpCell,
-                   const std::vector<int> *bwdCells)
+int ffm_tile_build(ffm_ldu *A, const std::vector<int> &lev, const std::vector<int> &bl, const std::vector<int> &grpCell)
 {
     A->tile = new ffm_tile_plan();
     ffm_tile_plan *T = A->tile;
@@ -443,12 +357,7 @@ int ffm_tile_build(ffm_ldu *A, const std::vector<int> &lev, const std::vector<in
     bool ok = true;
     std::vector<int4> recF;
     { FfmStageTimer tm_("tile: forward plan"); FFM_TRY(build_dir(A, true, lev, grpCell, grpOfCell, T->f, ok, &recF, &T->grpEntHost)); }
-    T->mirror = bwdCells == nullptr;
-    if (ok) {
-        FfmStageTimer tm_("tile: backward plan");
-        if (T->mirror) FFM_TRY(build_dir(A, false, bl, grpCell, grpOfCell, T->b, ok));
-        else { FFM_TRY(build_dir_pos(A, bl, grpCell, grpOfCell, *bwdCells, T->b, ok)); T->cellOf = A->bwdCells; }
-    }
+    if (ok) { FfmStageTimer tm_("tile: backward plan"); FFM_TRY(build_dir(A, false, bl, grpCell, grpOfCell, T->b, ok)); }
     T->usable = ok;
     if (ok) {
         T->nMail = (long)T->f.nPub + T->b.nPub + 2;
@@ -456,7 +365,7 @@ int ffm_tile_build(ffm_ldu *A, const std::vector<int> &lev, const std::vector<in
         T->f.mail = T->mailAll; T->b.mail = T->mailAll + T->f.nPub + 1;
         FfmStageTimer tm_("tile: amul plan");
         FFM_TRY(build_amul(A, grpOfCell, recF));
-        // the Gauss-Seidel sweeps need the cell-space tables: without them the matrix gets level-scheduled sweeps
+        // the Gauss-Seidel sweeps need the upper-neighbour tables: without them the matrix gets level-scheduled sweeps
         if (!T->gsTables) T->usable = false;
     }
     return FFM_OK;
@@ -520,7 +429,7 @@ __device__ __noinline__ double t_wait_value(const double *addr, unsigned int *ti
 //           partials[group] = sum |rA| (the residual norm of the iteration that just ended);
 //   TM_BWD: partials[group] = sum wA*rA of the finished preconditioned residual (PCG.C wArA = gSumProd(wA, rA)).
 // The per-cell arithmetic is that of k_pcg_xr / the unfused sweep; only the order of the two sums differs (as in any reduction).
-template <int MODE, bool TRACE, bool POSB = false, bool FUSE = false>
+template <int MODE, bool TRACE, bool FUSE = false>
 __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const double *__restrict__ ca, const double *__restrict__ cb,
                                                          const double *__restrict__ dg, const double *__restrict__ r, double *w, double *aux,
                                                          const double *__restrict__ scal = nullptr, double *__restrict__ partials = nullptr)
@@ -605,7 +514,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const doubl
 #define T_FETCH(k, e, R_) {                                                                             \
         const unsigned cnt_ = ((e) < e1) ? ((unsigned)R_.y & 0xFFFFu) : 0u;                              \
         const bool ok_ = tid < cnt_;                                                                     \
-        const unsigned cc_ = ok_ ? ((ASC || POSB) ? (unsigned)R_.x + tid : (unsigned)R_.x + cnt_ - 1u - tid) : gs; \
+        const unsigned cc_ = ok_ ? (ASC ? (unsigned)R_.x + tid : (unsigned)R_.x + cnt_ - 1u - tid) : gs; \
         const unsigned o8_ = cc_ * 8u, o24_ = cc_ * 24u;        /* 32-bit byte offsets: arrays < 4 GiB (host check) */  \
         pq[k] = *(const uint2 *)((const char *)t.code + o8_);                                            \
         { const T3 v_ = *(const T3 *)((const char *)ca + o24_); pa[k][0] = v_.a; pa[k][1] = v_.b; pa[k][2] = v_.c; }     \
@@ -701,15 +610,6 @@ __global__ void k_tile_fill(long n, unsigned long long *p, unsigned long long v,
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
 }
 
-// GATHER: out[q] = in[cellOf[q]]; else scatter: out[cellOf[q]] = in[q]
-template <bool GATHER>
-__global__ void k_tile_permute(long n, const int *__restrict__ cellOf, const double *__restrict__ in, double *__restrict__ out)
-{
-    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
-        if (GATHER) out[q] = in[cellOf[q]]; else out[cellOf[q]] = in[q];
-    }
-}
-
 static TileView tview(const ffm_ldu *A, const TileDir &d)
 {
     TileView t; t.G = A->tile->G; t.grpCell = A->grpCell; t.grpEnt = d.grpEnt; t.extSrc = d.extSrc; t.rec = d.rec;
@@ -739,23 +639,6 @@ static void tile_fill(ffm_ldu *A, double *p, long n)
     hipLaunchKernelGGL(k_tile_fill, dim3(g), dim3(256), 0, A->ctx->stream, n, (unsigned long long *)p, T_SENT, A->sweepTicket);
 }
 
-// upper coefficients of the owned upper neighbours in cell space: the backward direction's gathered array on mirror-ordered
-// meshes, a gather of its own otherwise
-static int tile_up_coef_cell(ffm_ldu *A, const double **out)
-{
-    ffm_tile_plan *T = A->tile;
-    if (T->mirror) return tile_coef(A, T->b, true, out);
-    const long n = (long)T_W * A->nOwned;
-    if (!T->upCoefCell) { FFM_HIP(hipMalloc((void **)&T->upCoefCell, sizeof(double) * std::max<long>(n, 1))); T->upCoefEpoch = ~0ul; }
-    if (T->upCoefEpoch != A->offDiagEpoch) {
-        hipLaunchKernelGGL(k_tile_gather, dim3(std::max(1, std::min(ffm_grid(n, 256), 8 * RED_BLOCKS))), dim3(256), 0, A->ctx->stream, n,
-                           (const int *)T->upSrcCell, (const double *)A->upper, T->upCoefCell);
-        T->upCoefEpoch = A->offDiagEpoch;
-    }
-    *out = T->upCoefCell;
-    return FFM_OK;
-}
-
 int ffm_tile_precond(ffm_ldu *A, int precond, bool transpose, const double *r, double *w)
 {
     ffm_tile_plan *T = A->tile;
@@ -767,22 +650,6 @@ int ffm_tile_precond(ffm_ldu *A, int precond, bool transpose, const double *r, d
     FFM_TRY(tile_coef(A, T->f, fwdUpper, &cf));
     FFM_TRY(tile_coef(A, T->b, bwdUpper, &cb));
     tile_fill(A, T->mailAll, T->nMail);
-    if (!T->mirror) {
-        // backward sweep in position space: rD and the forward result are gathered to positions, the result scattered back
-        const long n = A->nOwned;
-        const int g = std::max(1, std::min(ffm_grid(n, 256), 8 * RED_BLOCKS));
-        if (!T->wp) { FFM_HIP(hipMalloc((void **)&T->wp, sizeof(double) * std::max<long>(n, 1))); FFM_HIP(hipMalloc((void **)&T->rDp, sizeof(double) * std::max<long>(n, 1))); }
-        if (T->rDpEpoch != A->rDEpoch || T->rDpKind != A->rDKind) {
-            hipLaunchKernelGGL(k_tile_permute<true>, dim3(g), dim3(256), 0, s, n, T->cellOf, (const double *)A->rD, T->rDp);
-            T->rDpEpoch = A->rDEpoch; T->rDpKind = A->rDKind;
-        }
-        hipLaunchKernelGGL((k_tile<TM_FWD, false>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
-        hipLaunchKernelGGL(k_tile_permute<true>, dim3(g), dim3(256), 0, s, n, T->cellOf, (const double *)w, T->wp);
-        hipLaunchKernelGGL((k_tile<TM_BWD, false, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr, (const double *)T->rDp, r, T->wp, (double *)nullptr);
-        hipLaunchKernelGGL(k_tile_permute<false>, dim3(g), dim3(256), 0, s, n, T->cellOf, (const double *)T->wp, w);
-        FFM_HIP(hipGetLastError());
-        return FFM_OK;
-    }
     if (T->trace) {
         hipLaunchKernelGGL((k_tile<TM_FWD, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
         hipLaunchKernelGGL((k_tile<TM_BWD, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
@@ -795,14 +662,14 @@ int ffm_tile_precond(ffm_ldu *A, int precond, bool transpose, const double *r, d
 }
 
 __global__ void k_tile_sum_partials(int n, const double *__restrict__ partials, double *__restrict__ scal, int slot);
-// PCG with DIC on a mirror-ordered tile plan: the two halves of the preconditioner application with the neighbouring vector
+// PCG with DIC on a tile plan: the two halves of the preconditioner application with the neighbouring vector
 // updates fused in (k_tile<.., FUSE>).  Forward: rA -= scal[S_ALPHA]*wA, scal[slot] = sum |rA| (local), wA = forward sweep of rA.
 // Backward: finishes wA, scal[slot] = sum wA*rA (local).
 bool ffm_tile_pcg_fusable(const ffm_ldu *A)
 {
     const char *e = getenv("FFM_PCG_UNFUSED");
     const bool off = e && atoi(e) != 0;
-    return !off && ffm_tile_usable(A) && A->tile->mirror && !A->tile->trace && A->tile->G <= 4 * RED_BLOCKS;
+    return !off && ffm_tile_usable(A) && !A->tile->trace && A->tile->G <= 4 * RED_BLOCKS;
 }
 int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double *qA)
 {
@@ -812,7 +679,7 @@ int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double 
     FFM_TRY(tile_coef(A, T->f, true, &cf));
     FFM_TRY(tile_coef(A, T->b, true, &cb));
     tile_fill(A, T->mailAll, T->nMail);
-    hipLaunchKernelGGL((k_tile<TM_FWD, false, false, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr,
+    hipLaunchKernelGGL((k_tile<TM_FWD, false, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr,
                        (const double *)A->rD, qA, wA, rA, (const double *)A->ctx->scal_d, A->ctx->partials_d);
     hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
     FFM_HIP(hipGetLastError());
@@ -824,7 +691,7 @@ int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot)
     hipStream_t s = A->ctx->stream;
     const double *cb;
     FFM_TRY(tile_coef(A, T->b, true, &cb));
-    hipLaunchKernelGGL((k_tile<TM_BWD, false, false, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr,
+    hipLaunchKernelGGL((k_tile<TM_BWD, false, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr,
                        (const double *)A->rD, rA, wA, (double *)nullptr, (const double *)A->ctx->scal_d, A->ctx->partials_d);
     hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
     FFM_HIP(hipGetLastError());
@@ -841,56 +708,23 @@ __global__ void k_tile_gs_products(long n3, const int *__restrict__ nbrCell, con
     }
 }
 
-bool ffm_tile_gs_usable(const ffm_ldu *A) { return ffm_tile_usable(A) && A->tile->gsTables; }
-
-// the abort word of the sweep kernels (a bounded mailbox wait ran out): reported when a solve ends
-int ffm_tile_check_abort(ffm_ldu *A)
-{
-    unsigned int h[2] = {0, 0};
-    FFM_HIP(hipMemcpyAsync(h, A->sweepTicket, sizeof(h), hipMemcpyDeviceToHost, A->ctx->stream));
-    FFM_HIP(hipStreamSynchronize(A->ctx->stream));
-    if (h[1]) {
-        ffm_set_error("tiled sweep timed out waiting for a value of a predecessor group (abort word set)");
-        unsigned int z = 0;
-        ffm_h2d(A->ctx, A->sweepTicket + 1, &z, sizeof(z));
-        return FFM_ERR_HIP;
-    }
-    return FFM_OK;
-}
-
 // One GaussSeidelSmoother / symGaussSeidelSmoother sweep (forward rows, then reverse rows when sym): psi in place, bP = bPrime
 // (source with the lagged interface terms), bSave = scratch [nCells].  prod = scratch [3*nCells].
 int ffm_tile_gs(ffm_ldu *A, bool sym, double *psi, const double *bP, double *bSave, double *prod)
 {
     ffm_tile_plan *T = A->tile;
     hipStream_t s = A->ctx->stream;
-    const double *cl, *cuCell, *cuB;
+    const double *cl, *cu;
     FFM_TRY(tile_coef(A, T->f, A->lower == A->upper, &cl));        // lower coefficients, lower-neighbour layout
-    FFM_TRY(tile_up_coef_cell(A, &cuCell));                         // upper coefficients, cell space
-    FFM_TRY(tile_coef(A, T->b, true, &cuB));                        // upper coefficients in the backward direction's layout
-    const long n = A->nOwned, n3 = (long)T_W * n;
-    const int g1 = std::max(1, std::min(ffm_grid(n, 256), 8 * RED_BLOCKS));
+    FFM_TRY(tile_coef(A, T->b, true, &cu));                         // upper coefficients, upper-neighbour layout
+    const long n3 = (long)T_W * A->nOwned;
     hipLaunchKernelGGL(k_tile_gs_products, dim3(std::max(1, std::min(ffm_grid(n3, 256), 8 * RED_BLOCKS))), dim3(256), 0, s, n3,
-                       (const int *)T->upNbrCell, cuCell, (const double *)psi, prod);
+                       (const int *)T->upNbrCell, cu, (const double *)psi, prod);
     tile_fill(A, T->mailAll, T->nMail);
     hipLaunchKernelGGL((k_tile<TM_GSF, false>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cl, (const double *)prod, (const double *)A->diag, bP, psi, bSave);
-    if (sym && T->mirror)
-        hipLaunchKernelGGL((k_tile<TM_GSB, false>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cuB, (const double *)nullptr, (const double *)A->diag,
+    if (sym)
+        hipLaunchKernelGGL((k_tile<TM_GSB, false>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cu, (const double *)nullptr, (const double *)A->diag,
                            (const double *)bSave, psi, (double *)nullptr);
-    else if (sym) {
-        // reverse sweep in position space: bSave and diag gathered to positions, psi scattered back
-        if (!T->wp) { FFM_HIP(hipMalloc((void **)&T->wp, sizeof(double) * std::max<long>(n, 1))); FFM_HIP(hipMalloc((void **)&T->rDp, sizeof(double) * std::max<long>(n, 1))); T->rDpEpoch = ~0ul; }
-        if (!T->diagp) { FFM_HIP(hipMalloc((void **)&T->diagp, sizeof(double) * std::max<long>(n, 1))); T->diagpEpoch = ~0ul; }
-        if (T->diagpEpoch != A->coeffEpoch) {
-            hipLaunchKernelGGL(k_tile_permute<true>, dim3(g1), dim3(256), 0, s, n, T->cellOf, (const double *)A->diag, T->diagp);
-            T->diagpEpoch = A->coeffEpoch;
-        }
-        double *bSp = prod;                                         // the products are consumed: reuse their first n doubles
-        hipLaunchKernelGGL(k_tile_permute<true>, dim3(g1), dim3(256), 0, s, n, T->cellOf, (const double *)bSave, bSp);
-        hipLaunchKernelGGL((k_tile<TM_GSB, false, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cuB, (const double *)nullptr, (const double *)T->diagp,
-                           (const double *)bSp, T->wp, (double *)nullptr);
-        hipLaunchKernelGGL(k_tile_permute<false>, dim3(g1), dim3(256), 0, s, n, T->cellOf, (const double *)T->wp, psi);
-    }
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
@@ -1058,11 +892,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
 }
 
 
-bool ffm_tile_multi_usable(const ffm_ldu *A)
-{
-    const char *e = getenv("FFM_NO_MULTI_SWEEP");
-    return !(e && atoi(e) != 0) && ffm_tile_usable(A) && A->tile->mirror && !A->tile->trace;
-}
+bool ffm_tile_multi_usable(const ffm_ldu *A) { return ffm_tile_usable(A) && !A->tile->trace; }
 static int tile_multi_mail(ffm_ldu *A)
 {
     ffm_tile_plan *T = A->tile;
@@ -1080,7 +910,7 @@ static void tile_multi_launch(ffm_ldu *A, const TileDir &d, const double *ca, co
 #define TILE_MULTI(MODE, n, ...) switch (n) { case 2: tile_multi_launch<MODE, 2>(__VA_ARGS__); break; case 3: tile_multi_launch<MODE, 3>(__VA_ARGS__); break; \
                                              default: tile_multi_launch<MODE, 4>(__VA_ARGS__); break; }
 // DILU / DIC application (not transposed) of n = 2 .. FFM_TILE_MAXSYS systems with the matrix's off-diagonal coefficients and their
-// own reciprocal diagonals: w[i] = precondition(r[i]).  Mirror-ordered tile plans (ffm_tile_multi_usable).
+// own reciprocal diagonals: w[i] = precondition(r[i]).
 int ffm_tile_precond_multi(ffm_ldu *A, int precond, int n, const double *const *rD, const double *const *r, double *const *w)
 {
     ffm_tile_plan *T = A->tile;
@@ -1310,8 +1140,8 @@ __global__ __launch_bounds__(1024) void k_tile_sum_partials(int n, const double 
 
 bool ffm_tile_amul_usable(const ffm_ldu *A) { return ffm_tile_usable(A) && A->tile->amulUsable && A->symmetric && A->ifaces.empty(); }
 
-// y = A x for an asymmetric matrix on the tile plan (transport equations): upper coefficients from the cell-space upper table,
-// lower coefficients from the forward sweep's gathered array; ghost faces by the tail kernel as in the symmetric case
+// y = A x for an asymmetric matrix on the tile plan (transport equations): upper coefficients from the backward sweep's gathered
+// array, lower coefficients from the forward sweep's; ghost faces by the tail kernel as in the symmetric case
 bool ffm_tile_amul_asym_usable(const ffm_ldu *A)
 {
     return ffm_tile_usable(A) && A->tile->amulUsable && !A->symmetric && A->ifaces.empty() && !getenv("FFM_NO_TILE_AMUL_ASYM");
@@ -1321,7 +1151,7 @@ int ffm_tile_amul_asym(ffm_ldu *A, const double *x, double *y)
     ffm_tile_plan *T = A->tile;
     hipStream_t s = A->ctx->stream;
     const double *bcoef, *lcoef;
-    FFM_TRY(tile_up_coef_cell(A, &bcoef));
+    FFM_TRY(tile_coef(A, T->b, true, &bcoef));
     FFM_TRY(tile_coef(A, T->f, false, &lcoef));
     AmulView v; v.G = T->G; v.grpCell = A->grpCell; v.grpEnt = T->f.grpEnt; v.rec = T->arec; v.seg = T->aseg; v.code = T->acode; v.ext = T->aext;
     hipLaunchKernelGGL((k_tile_amul<false, false, true>), dim3(T->nSeg), dim3(T_THREADS + 64), 0, s, v, bcoef, (const double *)A->upper, (const double *)A->diag, x, y,
@@ -1344,7 +1174,7 @@ int ffm_tile_amul_pcg(ffm_ldu *A, const double *w, const double *pin, double *po
     ffm_tile_plan *T = A->tile;
     hipStream_t s = A->ctx->stream;
     const double *bcoef;
-    FFM_TRY(tile_up_coef_cell(A, &bcoef));
+    FFM_TRY(tile_coef(A, T->b, true, &bcoef));
     AmulView v; v.G = T->G; v.grpCell = A->grpCell; v.grpEnt = T->f.grpEnt; v.rec = T->arec; v.seg = T->aseg; v.code = T->acode; v.ext = T->aext;
     hipLaunchKernelGGL((k_tile_amul<true, true>), dim3(T->nSeg), dim3(T_THREADS + 64), 0, s, v, bcoef, (const double *)A->upper, (const double *)A->diag, w, y,
                        T->amulPartials, pin, pout, psi, (const double *)A->ctx->scal_d);
@@ -1359,7 +1189,7 @@ int ffm_tile_amul(ffm_ldu *A, const double *x, double *y, int dotSlot)
     ffm_tile_plan *T = A->tile;
     hipStream_t s = A->ctx->stream;
     const double *bcoef;
-    FFM_TRY(tile_up_coef_cell(A, &bcoef));
+    FFM_TRY(tile_coef(A, T->b, true, &bcoef));
     AmulView v; v.G = T->G; v.grpCell = A->grpCell; v.grpEnt = T->f.grpEnt; v.rec = T->arec; v.seg = T->aseg; v.code = T->acode; v.ext = T->aext;
     const bool fusedDot = dotSlot >= 0 && T->nTail == 0;
     if (fusedDot) {
@@ -1405,8 +1235,8 @@ extern "C" int ffm_debug_set_sweep_ticket(ffm_ldu *A, unsigned int value)
 extern "C" int ffm_debug_tile_occupancy(int *out3)
 {
     if (!out3) return FFM_ERR_ARG;
-    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[0], k_tile<TM_FWD, false, false>, T_THREADS + 64, 0));
-    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[1], k_tile<TM_BWD, false, false>, T_THREADS + 64, 0));
+    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[0], k_tile<TM_FWD, false>, T_THREADS + 64, 0));
+    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[1], k_tile<TM_BWD, false>, T_THREADS + 64, 0));
     FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[2], k_tile_amul<true>, T_THREADS + 64, 0));
     return FFM_OK;
 }

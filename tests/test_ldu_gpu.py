@@ -106,11 +106,9 @@ def test_dic_bit_exact(O, ctx, case):
 
 
 def test_sweep_ticket_counter_cannot_wrap(O, ctx, case):
-    """the 32-bit group ticket of the tiled sweeps is zeroed on the stream before every sweep, so a counter left
-    close to 2^32 (what ~7 million launches would have reached) changes nothing: DIC stays bitwise the serial face loops."""
+    """the 32-bit ticket of the tiled and the dataflow sweeps is zeroed on the stream before every sweep, so a counter
+    left close to 2^32 (what ~7 million launches would have reached) changes nothing: DIC stays bitwise the serial face loops."""
     N, A, Ao = _both(O, ctx, case, 0.0)
-    if A.sweep_mode != 2:
-        pytest.skip("level-scheduled sweeps have no ticket")
     r = 2 * O.hash_u(21, np.arange(N)) - 1
     rD = Ao.dic_rD()
     for preset in (2 ** 32 - 1, 2 ** 32 - 3, 2 ** 31 + 5):
@@ -224,23 +222,12 @@ def test_reductions(O, ctx):
     assert ctx.gSum(xd) == ctx.gSum(xd)      # deterministic (no atomics)
 
 
-@pytest.mark.parametrize("smallLimit,flow", [("0", "0"), ("1000000", None), ("0", None), ("1000000", "all"), (None, None), (None, "0")])
-def test_one_launch_per_level_and_single_workgroup_sweeps_agree(O, ffm, ctx, monkeypatch, smallLimit, flow):
-    """Level-scheduled sweeps have three forms: one launch per dependency level (FFM_FLOW_SWEEP=0; the round-1 path); for matrices of
-    at most FFM_SMALL_SWEEP_CELLS cells ONE workgroup that walks all levels with a barrier per level (csrc/ffm_solve.hip:
-    k_small_sweep); and -- the default for every level-scheduled matrix: unstructured meshes, GAMG's coarse levels -- ONE launch in
-    which every cell waits for the values it needs (k_flow_sweep: chunks of 256 cells by ticket, values published in sentinel-filled
-    arrays).  All must be the
-    serial face loops bit for bit: DIC and DILU (calcReciprocalD, precondition, transposed), GaussSeidel and symGaussSeidel, on a
-    randomly relabelled DAG mesh (non-contiguous backward levels), a hex box, and larger ones of both (hundreds of chunks)."""
-    if smallLimit is None:                      # the defaults: dataflow sweeps for every size; with them off, single-workgroup sweeps up to 131072 cells
-        monkeypatch.delenv("FFM_SMALL_SWEEP_CELLS", raising=False)
-    else:
-        monkeypatch.setenv("FFM_SMALL_SWEEP_CELLS", smallLimit)
-    if flow is None:
-        monkeypatch.delenv("FFM_FLOW_SWEEP", raising=False)
-    else:
-        monkeypatch.setenv("FFM_FLOW_SWEEP", flow)
+def test_dataflow_sweeps_bit_exact(O, ffm, ctx, monkeypatch):
+    """Level-scheduled matrices -- unstructured meshes, GAMG's coarse levels, FFM_SWEEP=levels -- take the dataflow sweeps: ONE
+    launch in which every cell waits for the values it needs (csrc/ffm_solve.hip: k_flow_sweep; chunks of 256 cells by ticket,
+    values published in sentinel-filled arrays).  They must be the serial face loops bit for bit: DIC and DILU (calcReciprocalD,
+    precondition, transposed), GaussSeidel and symGaussSeidel, on a randomly relabelled DAG mesh (non-contiguous backward levels),
+    a hex box, and larger ones of both (hundreds of chunks)."""
     monkeypatch.setenv("FFM_SWEEP", "levels")
     H = ffm.hexmesh
     for name in ("dag", "hex", "dag-large", "hex-large"):
