@@ -16,7 +16,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
-_SO = os.environ.get("FFM_LIB") or os.path.join(_HERE, "lib", "libffm.so")      # FFM_LIB: kernel experiments only
+_SO = os.path.join(_HERE, "lib", "libffm.so")
 _HDR = os.path.join(_ROOT, "include", "ffm.h")
 
 SOLVERS = {"PCG": 0, "PBiCGStab": 1, "PBiCG": 2, "diagonal": 3, "smoothSolver": 4}
@@ -123,7 +123,6 @@ def lib():
         "ffm_ldu_unbind_coeffs": ([vp], C.c_int),
         "ffm_bench_spmv": ([vp, dp, dp, C.c_int, hp], C.c_int),
         "ffm_bench_precond": ([vp, C.c_int, dp, dp, C.c_int, hp], C.c_int),
-        "ffm_debug_tile_trace": ([vp, C.c_void_p, C.c_int], C.c_int),
         "ffm_debug_set_sweep_ticket": ([vp, C.c_uint], C.c_int),
         "ffm_ldu_set_exchange_tags": ([vp, C.c_int, C.c_int, ip], C.c_int),
         "ffm_field_binary": ([vp, C.c_int, C.c_long, dp, dp, dp], C.c_int),

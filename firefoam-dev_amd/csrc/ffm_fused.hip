@@ -418,7 +418,7 @@ extern "C" int ffm_fv_multivariate_weights_tiled(ffm_mesh *m, int nf, const int 
     CHECK_M(m);
     if (nf < 1 || !schemes || !phi_f || !vf || !vb || !out_w) return FFM_ERR_ARG;
     FfmFvSegs sg;
-    if (nf > MVT_FLD || m->A->maxW > 3 || getenv("FFM_NO_TILE_FV") || !ffm_tile_fv_segments(m->A, MVT_RUN, &sg)) return FFM_ERR_UNSUPPORTED;
+    if (nf > MVT_FLD || m->A->maxW > 3 || !ffm_tile_fv_segments(m->A, MVT_RUN, &sg)) return FFM_ERR_UNSUPPORTED;
     MvTile a;
     for (int i = 0; i < MVT_FLD; i++) {
         const int qq = i < nf ? i : 0;

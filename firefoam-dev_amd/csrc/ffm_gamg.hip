@@ -306,21 +306,17 @@ extern "C" int ffm_gamg_create(ffm_ctx *ctx, ffm_ldu *finest, int nCells, int nF
     // (group) of its first fine cell.  On a hex box the pairs of the first few agglomerations lie inside the tiles, the coarse
     // levels keep <= 3 lower / upper neighbours per cell and an acyclic tile graph, and their smoother sweeps run as tiled
     // wavefronts instead of the dataflow sweeps (2 us per dependency level); wherever the planner cannot use the inherited groups
-    // ffm_ldu_create_hint falls back to the level-scheduled form by itself.  FFM_GAMG_TILES=0 switches the inheritance off.
+    // ffm_ldu_create_hint falls back to the level-scheduled form by itself.
     std::vector<int> hint;                  // group label per cell of the current level (caller order); empty: no inheritance
-    {
-        const char *e = getenv("FFM_GAMG_TILES");
-        if (!decomposed && finest->sweepMode == 2 && finest->grpCell && finest->nGroups > 0 && !(e && atoi(e) == 0)) {
-            std::vector<int> gc((size_t)finest->nGroups + 1);
-            FFM_HIP(hipStreamSynchronize(ctx->stream));              // the table was uploaded on the context's (non-blocking) stream
-            FFM_TRY(ffm_d2h(ctx, gc.data(), finest->grpCell, sizeof(int) * gc.size()));
-            hint.assign(nCells, 0);
-            for (int g = 0; g < finest->nGroups; g++)
-                for (int n = gc[g]; n < gc[g + 1] && n < nCells; n++) hint[finest->identity ? n : finest->h_newToOldCell[n]] = g;
-        }
+    if (!decomposed && finest->sweepMode == 2 && finest->grpCell && finest->nGroups > 0) {
+        std::vector<int> gc((size_t)finest->nGroups + 1);
+        FFM_HIP(hipStreamSynchronize(ctx->stream));              // the table was uploaded on the context's (non-blocking) stream
+        FFM_TRY(ffm_d2h(ctx, gc.data(), finest->grpCell, sizeof(int) * gc.size()));
+        hint.assign(nCells, 0);
+        for (int g = 0; g < finest->nGroups; g++)
+            for (int n = gc[g]; n < gc[g + 1] && n < nCells; n++) hint[finest->identity ? n : finest->h_newToOldCell[n]] = g;
     }
-    long tileMinCells = 2048;               // below this a level is a handful of tiles (measured: 2048 ... 8192 equal, 32768 slower)
-    if (const char *e = getenv("FFM_GAMG_TILE_MIN_CELLS")) tileMinCells = atol(e);
+    constexpr int TILE_MIN_CELLS = 2048;    // below this a level is a handful of tiles (measured: 2048 ... 8192 equal, 32768 slower)
     bool forward = ctx->gamgForward;        // pairGAMGAgglomeration::forward_: static upstream, here kept per context (= per run)
     const int maxLevels = 50;
     while ((int)G->lev.size() - 1 < maxLevels - 1) {
@@ -396,7 +392,7 @@ extern "C" int ffm_gamg_create(ffm_ctx *ctx, ffm_ldu *finest, int nCells, int nF
             std::vector<int> ch(nCoarse, -1);
             for (int c = 0; c < nFine; c++) if (ch[cmap[c]] < 0) ch[cmap[c]] = hint[c];          // the first fine cell's tile
             hint.swap(ch);
-            if (nCoarse < tileMinCells) hint.clear();
+            if (nCoarse < TILE_MIN_CELLS) hint.clear();
         }
         if (decomposed) {
             rc = ffm_ldu_create_ext(ctx, nCoarse, nCoarseGhost, nCF, cl.data(), cu.data(), &Ac);

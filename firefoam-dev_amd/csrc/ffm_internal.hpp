@@ -258,14 +258,14 @@ struct FfmLapTimer {
     explicit FfmLapTimer(const char *w) : what(w), t0(FfmStageTimer::now()), on(getenv("FFM_TIMING") != nullptr && atoi(getenv("FFM_TIMING")) >= 2) {}
     void lap(const char *stage) { if (!on) return; const double t = FfmStageTimer::now(); fprintf(stderr, "ffm timing:   %s: %-30s %.2f s\n", what, stage, t - t0); t0 = t; }
 };
+// edge of the 2-D tiles of cell columns, in cells: detected blockMesh boxes, the plume's group hint, ffm_tile_hint_from_centres
+constexpr int TILE_EDGE = 16;
 // label of the 2-D tile (a, b) of cell columns.  Ties between tiles that are ready at the same time are broken by label
 // (ffm_ldu.hip: topological ranking), so the label orders the tickets: anti-diagonal major = the order of the sweep's wavefront
-// (FFM_TILE_ROW_ORDER=1: row-major, the round-1 order)
 static inline int ffm_tile_label(int a, int b)
 {
-    static const bool row = getenv("FFM_TILE_ROW_ORDER") && atoi(getenv("FFM_TILE_ROW_ORDER")) != 0;
     a = a < 2047 ? a : 2047; b = b < 2047 ? b : 2047;
-    return row ? a + 32768 * b : (a + b) * 4096 + b;
+    return (a + b) * 4096 + b;
 }
 struct LduView;
 LduView ffm_view(const ffm_ldu *A);

@@ -98,13 +98,6 @@ static bool detect_box(int N, int F, const int *l, const int *u, int &nx, int &n
     return q == F;
 }
 
-static int tile_edge()
-{
-    int t = 16;
-    if (const char *e = getenv("FFM_TILE")) t = std::max(1, atoi(e));
-    return t;
-}
-
 // ffm_renumber_* and ffm_ldu_create* are separate calls: the groups chosen by a renumbering (contiguous cell ranges of the
 // new numbering) are remembered under a fingerprint of the renumbered addressing, so that creating the matrix from that
 // addressing without a hint finds them again.
@@ -151,9 +144,8 @@ static int analyse(int N, int nOwn, int F, const int *l, const int *u, bool renu
                 for (int g = 0; g + 1 < (int)gc->size(); g++) for (int c = (*gc)[g]; c < (*gc)[g + 1] && c < nOwn; c++) autoHint[c] = g;
                 groupHint = autoHint.data(); a.mode = 2;
             } else if (N == nOwn && detect_box(N, F, l, u, bx, by, bz)) {
-                const int T = tile_edge();
                 autoHint.resize(nOwn);
-                for (int c = 0; c < nOwn; c++) autoHint[c] = ffm_tile_label(((c / bx) % by) / T, (c / (bx * by)) / T);
+                for (int c = 0; c < nOwn; c++) autoHint[c] = ffm_tile_label(((c / bx) % by) / TILE_EDGE, (c / (bx * by)) / TILE_EDGE);
                 groupHint = autoHint.data(); a.mode = 2;
             }
         }
@@ -210,8 +202,7 @@ static int analyse(int N, int nOwn, int F, const int *l, const int *u, bool renu
             // planes, is split over several entries, and the neighbours of a cell are no longer in the entries next to its own (the
             // ring window of the tiled Amul; the sweeps' LDS ring).  Every connected component of a class becomes a group of its own:
             // no new edges, so the group graph stays acyclic; classes in one piece (every tile of a box) are unchanged.
-            static const bool splitComponents = !(getenv("FFM_TILE_SPLIT_COMPONENTS") && atoi(getenv("FFM_TILE_SPLIT_COMPONENTS")) == 0);
-            if (splitComponents) {
+            {
                 std::vector<int> parent(nOwn);
                 std::iota(parent.begin(), parent.end(), 0);
                 auto find = [&](int x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
@@ -282,8 +273,7 @@ static int analyse(int N, int nOwn, int F, const int *l, const int *u, bool renu
         {
             std::vector<int> first(nOwn);
             std::iota(first.begin(), first.end(), 0);
-            static const bool edgeOrder = !(getenv("FFM_TILE_EDGE_ORDER") && atoi(getenv("FFM_TILE_EDGE_ORDER")) == 0);
-            if (edgeOrder && G > 1) {
+            if (G > 1) {
                 std::vector<int> key(nOwn, G), cntK(G + 2, 0);
                 for (int f = 0; f < F; f++) {
                     if (u[f] >= nOwn) continue;
@@ -416,7 +406,7 @@ extern "C" int ffm_tile_hint_from_centres(int nCells, const double *C /* [3][nCe
 {
     if (nCells < 0 || (nCells && (!C || !hint))) return FFM_ERR_ARG;
     if (nCells == 0) return FFM_OK;
-    if (tileCells <= 0) tileCells = tile_edge();
+    if (tileCells <= 0) tileCells = TILE_EDGE;
     double lo[3], hi[3];
     for (int d = 0; d < 3; d++) { lo[d] = hi[d] = C[(size_t)d * nCells]; }
     long votes[3] = {0, 0, 0};
@@ -954,20 +944,30 @@ static inline int rows_grid(const ffm_ldu *A)
     // Fewer workgroups in flight on very large meshes: the rows in flight per XCD (grid/8 chunks of 256 rows, ~110 B each)
     // should not exceed the 4 MB L2 by much, or the neighbour gathers miss it (measured at 64 M rows: 1.16 ms with 1024
     // workgroups, 1.37 ms with 2048; below 10 M rows 2048 is marginally better)
-    static const int cap = getenv("FFM_ROWS_GRID") ? std::min(atoi(getenv("FFM_ROWS_GRID")), RED_BLOCKS) : 0;
-    int g = std::min(A->nSched, cap ? cap : (A->nOwned >= (32 << 20) ? 1024 : RED_BLOCKS)); g = (g + 7) & ~7; return std::max(g, 8);
+    int g = std::min(A->nSched, A->nOwned >= (32 << 20) ? 1024 : RED_BLOCKS); g = (g + 7) & ~7; return std::max(g, 8);
+}
+
+// The Amul form of a matrix: the tiled kernel of a symmetric matrix, the tiled kernel of an asymmetric one (not for Tmul),
+// or the row kernel.  FFM_NO_TILE_AMUL is read on every call: tests switch it between two Amuls of the same matrix.
+enum AmulForm { AMUL_ROWS, AMUL_TILE_SYM, AMUL_TILE_ASYM };
+static AmulForm amul_form(const ffm_ldu *A, bool transpose)
+{
+    if (ffm_tile_amul_usable(A) && !getenv("FFM_NO_TILE_AMUL")) return AMUL_TILE_SYM;
+    if (!transpose && ffm_tile_amul_asym_usable(A)) return AMUL_TILE_ASYM;
+    return AMUL_ROWS;
 }
 
 int ffm_k_spmv(ffm_ldu *A, const double *x, double *y, bool transpose)
 {
     const double *up = transpose ? A->lower : A->upper, *lo = transpose ? A->upper : A->lower;
-    if (ffm_tile_amul_usable(A) && !getenv("FFM_NO_TILE_AMUL")) {
+    const AmulForm form = amul_form(A, transpose);
+    if (form == AMUL_TILE_SYM) {
         // the tiled kernel computes the rows without their ghost faces: the ghost refresh overlaps it and is waited for by the tail
         if (!A->ghNbrRank.empty()) FFM_TRY(ffm_ghost_exchange_begin(A, const_cast<double *>(x)));
         FFM_TRY(ffm_tile_amul(A, x, y, -1));
         return FFM_OK;
     }
-    if (!transpose && ffm_tile_amul_asym_usable(A)) {
+    if (form == AMUL_TILE_ASYM) {
         if (!A->ghNbrRank.empty()) FFM_TRY(ffm_ghost_exchange_begin(A, const_cast<double *>(x)));
         return ffm_tile_amul_asym(A, x, y);
     }
@@ -1037,7 +1037,7 @@ int ffm_k_spmv_dot(ffm_ldu *A, const double *x, double *y, int slot)
         FFM_TRY(ffm_k_spmv(A, x, y, false));
         return ffm_k_dot(A->ctx, y, x, A->nOwned, slot);
     }
-    if (ffm_tile_amul_usable(A) && !getenv("FFM_NO_TILE_AMUL")) {
+    if (amul_form(A, false) == AMUL_TILE_SYM) {
         if (!A->ghNbrRank.empty()) FFM_TRY(ffm_ghost_exchange_begin(A, const_cast<double *>(x)));
         const int rc = ffm_tile_amul(A, x, y, slot);
         if (rc == 1) return ffm_k_dot(A->ctx, y, x, A->nOwned, slot);      // ghost faces were added after the tiled kernel
@@ -1065,7 +1065,7 @@ int ffm_k_residual(ffm_ldu *A, const double *x, const double *b, double *r)
 // y = A x and s = sumA of the same matrix: one pass where the row kernel does the Amul, two where the tiled kernel does
 int ffm_k_spmv_sumA(ffm_ldu *A, const double *x, double *y, double *s)
 {
-    if ((ffm_tile_amul_usable(A) && !getenv("FFM_NO_TILE_AMUL")) || getenv("FFM_NO_FUSED_SUMA")) {
+    if (amul_form(A, false) == AMUL_TILE_SYM) {
         FFM_TRY(ffm_k_spmv(A, x, y, false));
         return ffm_k_sumA(A, s);
     }

@@ -658,7 +658,6 @@ extern "C" int ffm_plume_step(ffm_plume *P)
         double *K = P->K; const double *U0 = P->U[0], *U1 = P->U[1], *U2 = P->U[2];
         forN(P, N, [=] __device__(long i) { K[i] = 0.5 * ((U0[i] * U0[i] + U1[i] * U1[i]) + U2[i] * U2[i]); });
     }
-    { const char *st = getenv("FFM_PLUME_STOP"); if (st && atoi(st) == 1) { PL_HIP(hipStreamSynchronize(P->ctx->stream)); return FFM_OK; } }
     // ---------------- YEEqn.H
     double *af = P->wF[0], *afb = P->wB[4];
     forN(P, nNat, [=] __device__(long e) { af[e] = 0.5 * (MU / PR) + (1.0 - 0.5) * (MU / PR); });
@@ -831,10 +830,8 @@ extern "C" int ffm_plume_step(ffm_plume *P)
         FFM_TRY(scalar_transport(P, "h", 2, P->hs, P->hs0, P->fH, P->refH, af, afb, Qdot, expl, 1e-8, shSu, shSp, P->mvSelection ? P->wMv : nullptr));
     }
     standin_thermo(P);
-    { const char *st = getenv("FFM_PLUME_STOP"); if (st && atoi(st) == 2) { PL_HIP(hipStreamSynchronize(P->ctx->stream)); return FFM_OK; } }
     // ---------------- pEqn.H x 2
     FFM_TRY(p_corrector(P, false));
-    { const char *st = getenv("FFM_PLUME_STOP"); if (st && atoi(st) == 3) { PL_HIP(hipStreamSynchronize(P->ctx->stream)); return FFM_OK; } }
     FFM_TRY(p_corrector(P, true));
     mul(P, P->rho, P->psi, P->p, N);
     P->time += P->dt; P->stepNo++;
@@ -898,11 +895,9 @@ extern "C" int ffm_plume_create_block(ffm_ctx *ctx, int gx, int gy, int gz, cons
     const int F = (int)l.size(); P->F = F;
     delete tmS_; tmS_ = nullptr;
     // ---- renumber once to the library's cell order (no permutation pass ever after)
-    // group hint for the tiled sweeps: 2-D tiles of x-columns, FFM_TILE x FFM_TILE cells in (y,z) (ignored by the level mode)
-    int tileEdge = 16;
-    if (const char *e = getenv("FFM_TILE")) tileEdge = std::max(1, atoi(e));
+    // group hint for the tiled sweeps: 2-D tiles of x-columns, TILE_EDGE x TILE_EDGE cells in (y,z) (ignored by the level mode)
     std::vector<int> hint(nOwn);
-    for (int k = 0; k < nz; k++) for (int j = 0; j < ny; j++) for (int i = 0; i < nx; i++) hint[cellOf(i, j, k)] = ffm_tile_label(j / tileEdge, k / tileEdge);
+    for (int k = 0; k < nz; k++) for (int j = 0; j < ny; j++) for (int i = 0; i < nx; i++) hint[cellOf(i, j, k)] = ffm_tile_label(j / TILE_EDGE, k / TILE_EDGE);
     std::vector<int> c2(N), f2(F);
     { FfmStageTimer tm_("plume_create: renumber_hint"); FFM_TRY(ffm_renumber_hint((int)nOwn, (int)nGhost, F, l.data(), u.data(), hint.data(), c2.data(), f2.data())); }
     P->newToOld = c2; P->faceNewToOld = f2;
@@ -1108,7 +1103,7 @@ extern "C" int ffm_plume_set_radiation(ffm_plume *P, int solverFreq, int nPhi, i
     }
     // ---- direction-ordered solves: one block without ghost layers (a decomposed block keeps the iterative solve: the
     // exact sweep would have to cross rank boundaries)
-    if (!P->hL2.empty() && !P->radOrdered && !getenv("FFM_RAD_ITERATIVE")) {
+    if (!P->hL2.empty() && !P->radOrdered) {
         const int N = P->N, F = P->F, nx = P->nx, ny = P->ny, nz = P->nz; const long nNat = P->nNat;
         std::vector<int> ownerStart(N + 1, 0);
         for (int f = 0; f < F; f++) ownerStart[P->hL2[f] + 1]++;

@@ -597,9 +597,8 @@ static int pcg(ffm_ldu *A, int precond, const Controls &k, double *psi, const do
             // is deferred into the next search-direction update.  Per-cell arithmetic unchanged.
             // one more fusion where the tiled Amul runs without ghost faces: the direction update and the deferred solution update
             // ride on the Amul (k_tile_amul<true, true>: pNew = wA + beta*pOld, psi += alpha*pOld, qA = A pNew, pNew.qA), with
-            // two direction buffers and the Amul result in a vector of its own (FFM_PCG_AMUL_UNFUSED=1: separate k_p_psi)
-            const char *ea = getenv("FFM_PCG_AMUL_UNFUSED");
-            const bool fuseP = ffm_tile_amul_pcg_usable(A) && !(ea && atoi(ea) != 0);
+            // two direction buffers and the Amul result in a vector of its own (elsewhere: separate k_p_psi)
+            const bool fuseP = ffm_tile_amul_pcg_usable(A);
             double *pB = nullptr, *qA = wA;
             if (fuseP) { FFM_TRY(ffm_ldu_work(A, 4, &pB)); FFM_TRY(ffm_ldu_work(A, 5, &qA)); }
             do {

@@ -32,10 +32,7 @@ constexpr int T_RING = 4096;        // doubles (power of two)
 constexpr int T_ENT = 256;          // max cells per entry = workgroup size
 constexpr int T_THREADS = 256;
 constexpr int T_W = 3;              // neighbour slots per cell and direction (hexahedra: 3)
-#ifndef FFM_T_PF
-#define FFM_T_PF 8
-#endif
-constexpr int T_PF = FFM_T_PF;      // entries fetched ahead of the one being computed
+constexpr int T_PF = 8;             // entries fetched ahead of the one being computed
 constexpr int T_PM = 3;             // mailbox values are loaded this many entries ahead (2 <= T_PM < T_PF)
 constexpr int T_XMAX = 64;          // max external references per entry (one lane of the mail wave each; power of two)
 constexpr int T_RINGD = T_RING - 2 * T_ENT;     // largest cell distance served by the ring
@@ -66,7 +63,6 @@ struct ffm_tile_plan {
     double *mailAll = nullptr;
     long nMail = 0;
     double *mailMulti = nullptr;    // [FFM_TILE_MAXSYS][nMail]: the mailboxes of the multi-system sweeps (k_tile_m), allocated on first use
-    unsigned long long *trace = nullptr;    // diagnostics (ffm_debug_tile_trace): per group {start, first entry done, end, re-loads} of the last launch
     // ---- tiled Amul (symmetric matrices): same groups and entries as the forward sweep
     bool amulUsable = false;
     bool gsTables = false;          // the upper-neighbour and tail tables below exist (Gauss-Seidel sweeps, Amul tail)
@@ -111,7 +107,7 @@ void ffm_tile_free(ffm_ldu *A)
 {
     if (!A->tile) return;
     free_dir(A->tile->f); free_dir(A->tile->b);
-    hipFree(A->tile->mailAll); hipFree(A->tile->mailMulti); hipFree(A->tile->trace);
+    hipFree(A->tile->mailAll); hipFree(A->tile->mailMulti);
     hipFree(A->tile->arec); hipFree(A->tile->acode); hipFree(A->tile->aext); hipFree(A->tile->aseg); hipFree(A->tile->amulPartials);
     hipFree(A->tile->fvSeg); hipFree(A->tile->upNbrCell);
     hipFree(A->tile->tailCell); hipFree(A->tile->tailStart); hipFree(A->tile->tailFace); hipFree(A->tile->tailNbr);
@@ -332,8 +328,7 @@ static int build_amul(ffm_ldu *A, const std::vector<int> &grpOfCell, const std::
         const std::vector<int> &grpEntH = T->grpEntHost;
         // measured at 400^3 (r02, scripts/tile_probe.py): 16 entries 0.82 ms, 24 0.83, 32 0.84, 64 0.87, a whole tile (430) 0.93, 8 0.94 --
         // short segments balance the 256 CUs better than their two extra ring entries cost
-        int L = std::min(20, std::max(16, nEnt / 2048));
-        if (const char *e = getenv("FFM_AMUL_SEG")) L = std::max(1, atoi(e));
+        const int L = std::min(20, std::max(16, nEnt / 2048));
         std::vector<int4> seg;
         for (int g = 0; g < T->G; g++) for (int a = grpEntH[g]; a < grpEntH[g + 1]; a += L) seg.push_back(make_int4(g, a, std::min(a + L, grpEntH[g + 1]), grpEntH[g + 1]));
         T->nSeg = (int)seg.size();
@@ -379,7 +374,6 @@ struct TileView {
     const uint2 *code;
     double *mail;
     unsigned int *ticket;       // [0] ticket counter, [1] abort word
-    unsigned long long *trace;  // diagnostics or nullptr
 };
 
 __device__ __forceinline__ double t_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -393,8 +387,7 @@ struct __attribute__((aligned(8))) T3 { double a, b, c; };       // the three co
 static_assert(T_W == 3, "T3");
 
 // slow path of a mailbox read: re-load until the producer's value has replaced the sentinel; bounded, watches the abort word
-template <bool TRACE>
-__device__ __noinline__ double t_wait_value(const double *addr, unsigned int *ticket, int *shAbort, unsigned long long *traceWord)
+__device__ __noinline__ double t_wait_value(const double *addr, unsigned int *ticket, int *shAbort)
 {
     double v = t_ld(addr);
     if (*(volatile int *)shAbort) return v;
@@ -407,7 +400,6 @@ __device__ __noinline__ double t_wait_value(const double *addr, unsigned int *ti
             if (spins > T_SPIN_LIMIT) { __hip_atomic_store(&ticket[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); *shAbort = 1; break; }
         }
     }
-    if (TRACE) atomicAdd(traceWord, (unsigned long long)spins);
     return v;
 }
 
@@ -429,7 +421,7 @@ __device__ __noinline__ double t_wait_value(const double *addr, unsigned int *ti
 //           partials[group] = sum |rA| (the residual norm of the iteration that just ended);
 //   TM_BWD: partials[group] = sum wA*rA of the finished preconditioned residual (PCG.C wArA = gSumProd(wA, rA)).
 // The per-cell arithmetic is that of k_pcg_xr / the unfused sweep; only the order of the two sums differs (as in any reduction).
-template <int MODE, bool TRACE, bool FUSE = false>
+template <int MODE, bool FUSE = false>
 __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const double *__restrict__ ca, const double *__restrict__ cb,
                                                          const double *__restrict__ dg, const double *__restrict__ r, double *w, double *aux,
                                                          const double *__restrict__ scal = nullptr, double *__restrict__ partials = nullptr)
@@ -456,7 +448,6 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const doubl
     const unsigned gs = (unsigned)__builtin_amdgcn_readfirstlane(t.grpCell[g]);
     const int e0 = __builtin_amdgcn_readfirstlane(t.grpEnt[g]), e1 = __builtin_amdgcn_readfirstlane(t.grpEnt[g + 1]);
     if (e0 >= e1) { if (FUSE && tid == 0) partials[g] = 0.0; return; }
-    if (TRACE && tid == 0) { t.trace[4 * g] = wall_clock64(); t.trace[4 * g + 3] = 0; }
 
     if (tid >= (unsigned)T_THREADS) {
         // ------------------------------------------------------------------ mail wave
@@ -470,7 +461,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const doubl
 #define Q_PUT(k, e) {                                                                                    \
         if (lane < qne[k]) {                                                                              \
             double v_ = qxv[k];                                                                           \
-            if (__builtin_expect(t_pending(v_), 0)) v_ = t_wait_value<TRACE>(&t.mail[qxi[k]], t.ticket, &shAbort, TRACE ? &t.trace[4 * g + 3] : nullptr); \
+            if (__builtin_expect(t_pending(v_), 0)) v_ = t_wait_value(&t.mail[qxi[k]], t.ticket, &shAbort); \
             halo[(((e) & 1) * T_XMAX) + lane] = v_;                                                       \
         }                                                                                                 \
     }
@@ -527,7 +518,6 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const doubl
 #pragma unroll
     for (int k = 0; k < T_PF; k++) { const int4 R0 = t.rec[min(e0 + k, e1)]; T_FETCH(k, e0 + k, R0); }
     t_barrier();
-    if (TRACE && tid == 0) t.trace[4 * g + 1] = wall_clock64();
     for (int e = e0; e < e1; e += T_PF) {
 #pragma unroll
         for (int k = 0; k < T_PF; k++) {
@@ -582,7 +572,6 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const doubl
             t_barrier();                                    // one barrier per level: ring and halo are visible to the next entry
         }
     }
-    if (TRACE && tid == 0) t.trace[4 * g + 2] = wall_clock64();
 #undef T_FETCH
     if (FUSE) {             // the four compute waves (the mail wave has left): wave sums through LDS, lane 0 adds them in wave order
         double v = fsum;
@@ -613,7 +602,7 @@ __global__ void k_tile_fill(long n, unsigned long long *p, unsigned long long v,
 static TileView tview(const ffm_ldu *A, const TileDir &d)
 {
     TileView t; t.G = A->tile->G; t.grpCell = A->grpCell; t.grpEnt = d.grpEnt; t.extSrc = d.extSrc; t.rec = d.rec;
-    t.code = (const uint2 *)d.code; t.mail = d.mail; t.ticket = A->sweepTicket; t.trace = A->tile->trace;
+    t.code = (const uint2 *)d.code; t.mail = d.mail; t.ticket = A->sweepTicket;
     return t;
 }
 
@@ -650,13 +639,8 @@ int ffm_tile_precond(ffm_ldu *A, int precond, bool transpose, const double *r, d
     FFM_TRY(tile_coef(A, T->f, fwdUpper, &cf));
     FFM_TRY(tile_coef(A, T->b, bwdUpper, &cb));
     tile_fill(A, T->mailAll, T->nMail);
-    if (T->trace) {
-        hipLaunchKernelGGL((k_tile<TM_FWD, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
-        hipLaunchKernelGGL((k_tile<TM_BWD, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
-    } else {
-        hipLaunchKernelGGL((k_tile<TM_FWD, false>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
-        hipLaunchKernelGGL((k_tile<TM_BWD, false>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
-    }
+    hipLaunchKernelGGL(k_tile<TM_FWD>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
+    hipLaunchKernelGGL(k_tile<TM_BWD>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
@@ -669,7 +653,7 @@ bool ffm_tile_pcg_fusable(const ffm_ldu *A)
 {
     const char *e = getenv("FFM_PCG_UNFUSED");
     const bool off = e && atoi(e) != 0;
-    return !off && ffm_tile_usable(A) && !A->tile->trace && A->tile->G <= 4 * RED_BLOCKS;
+    return !off && ffm_tile_usable(A) && A->tile->G <= 4 * RED_BLOCKS;
 }
 int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double *qA)
 {
@@ -679,7 +663,7 @@ int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double 
     FFM_TRY(tile_coef(A, T->f, true, &cf));
     FFM_TRY(tile_coef(A, T->b, true, &cb));
     tile_fill(A, T->mailAll, T->nMail);
-    hipLaunchKernelGGL((k_tile<TM_FWD, false, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr,
+    hipLaunchKernelGGL((k_tile<TM_FWD, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr,
                        (const double *)A->rD, qA, wA, rA, (const double *)A->ctx->scal_d, A->ctx->partials_d);
     hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
     FFM_HIP(hipGetLastError());
@@ -691,7 +675,7 @@ int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot)
     hipStream_t s = A->ctx->stream;
     const double *cb;
     FFM_TRY(tile_coef(A, T->b, true, &cb));
-    hipLaunchKernelGGL((k_tile<TM_BWD, false, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr,
+    hipLaunchKernelGGL((k_tile<TM_BWD, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr,
                        (const double *)A->rD, rA, wA, (double *)nullptr, (const double *)A->ctx->scal_d, A->ctx->partials_d);
     hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
     FFM_HIP(hipGetLastError());
@@ -721,9 +705,9 @@ int ffm_tile_gs(ffm_ldu *A, bool sym, double *psi, const double *bP, double *bSa
     hipLaunchKernelGGL(k_tile_gs_products, dim3(std::max(1, std::min(ffm_grid(n3, 256), 8 * RED_BLOCKS))), dim3(256), 0, s, n3,
                        (const int *)T->upNbrCell, cu, (const double *)psi, prod);
     tile_fill(A, T->mailAll, T->nMail);
-    hipLaunchKernelGGL((k_tile<TM_GSF, false>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cl, (const double *)prod, (const double *)A->diag, bP, psi, bSave);
+    hipLaunchKernelGGL(k_tile<TM_GSF>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cl, (const double *)prod, (const double *)A->diag, bP, psi, bSave);
     if (sym)
-        hipLaunchKernelGGL((k_tile<TM_GSB, false>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cu, (const double *)nullptr, (const double *)A->diag,
+        hipLaunchKernelGGL(k_tile<TM_GSB>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cu, (const double *)nullptr, (const double *)A->diag,
                            (const double *)bSave, psi, (double *)nullptr);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
@@ -737,7 +721,7 @@ int ffm_tile_calc_rD(ffm_ldu *A)
     FFM_TRY(tile_coef(A, T->f, true, &cu));
     if (A->lower == A->upper) cl = cu; else FFM_TRY(tile_coef(A, T->f, false, &cl));
     tile_fill(A, T->f.mail, (long)T->f.nPub + 1);
-    hipLaunchKernelGGL((k_tile<TM_RD, false>), dim3(T->G), dim3(T_THREADS + 64), 0, A->ctx->stream, tview(A, T->f), cu, cl, (const double *)A->diag,
+    hipLaunchKernelGGL(k_tile<TM_RD>, dim3(T->G), dim3(T_THREADS + 64), 0, A->ctx->stream, tview(A, T->f), cu, cl, (const double *)A->diag,
                        (const double *)nullptr, A->rD, (double *)nullptr);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
@@ -789,7 +773,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
         if (lane < qne[k]) {                                                                              \
             _Pragma("unroll") for (int i_ = 0; i_ < NF; i_++) {                                           \
                 double v_ = qxv[k][i_];                                                                   \
-                if (__builtin_expect(t_pending(v_), 0)) v_ = t_wait_value<false>(&m.mail[i_][qxi[k]], t.ticket, &shAbort, nullptr); \
+                if (__builtin_expect(t_pending(v_), 0)) v_ = t_wait_value(&m.mail[i_][qxi[k]], t.ticket, &shAbort); \
                 ring[i_][T_RING + (((e) & 1) * T_XMAX) + lane] = v_;                                      \
             }                                                                                             \
         }                                                                                                 \
@@ -892,7 +876,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
 }
 
 
-bool ffm_tile_multi_usable(const ffm_ldu *A) { return ffm_tile_usable(A) && !A->tile->trace; }
+bool ffm_tile_multi_usable(const ffm_ldu *A) { return ffm_tile_usable(A); }
 static int tile_multi_mail(ffm_ldu *A)
 {
     ffm_tile_plan *T = A->tile;
@@ -1144,7 +1128,7 @@ bool ffm_tile_amul_usable(const ffm_ldu *A) { return ffm_tile_usable(A) && A->ti
 // array, lower coefficients from the forward sweep's; ghost faces by the tail kernel as in the symmetric case
 bool ffm_tile_amul_asym_usable(const ffm_ldu *A)
 {
-    return ffm_tile_usable(A) && A->tile->amulUsable && !A->symmetric && A->ifaces.empty() && !getenv("FFM_NO_TILE_AMUL_ASYM");
+    return ffm_tile_usable(A) && A->tile->amulUsable && !A->symmetric && A->ifaces.empty();
 }
 int ffm_tile_amul_asym(ffm_ldu *A, const double *x, double *y)
 {
@@ -1207,22 +1191,6 @@ int ffm_tile_amul(ffm_ldu *A, const double *x, double *y, int dotSlot)
     return fusedDot || dotSlot < 0 ? FFM_OK : 1;       // 1: the caller still has to take the dot product
 }
 
-// Diagnostics: the first call switches tracing on; later calls copy out, for the LAST tiled launch, 4 words per group:
-// wall_clock64 (100 MHz) at start, after the first entry's externals, at the end, and the number of mailbox re-loads.
-extern "C" int ffm_debug_tile_trace(ffm_ldu *A, unsigned long long *out, int nWords)
-{
-    if (!A || !ffm_tile_usable(A)) return FFM_ERR_ARG;
-    ffm_tile_plan *T = A->tile;
-    FFM_HIP(hipStreamSynchronize(A->ctx->stream));
-    if (!T->trace) {
-        FFM_HIP(hipMalloc((void **)&T->trace, sizeof(unsigned long long) * 4 * T->G));
-        FFM_TRY(ffm_dzero(A->ctx, T->trace, sizeof(unsigned long long) * 4 * T->G)); FFM_HIP(hipStreamSynchronize(A->ctx->stream));
-        return T->G;
-    }
-    if (out && nWords > 0) FFM_TRY(ffm_d2h(A->ctx, out, T->trace, sizeof(unsigned long long) * std::min(nWords, 4 * T->G)));
-    return T->G;
-}
-
 extern "C" int ffm_debug_set_sweep_ticket(ffm_ldu *A, unsigned int value)
 {
     if (!A || !A->sweepTicket) return FFM_ERR_ARG;
@@ -1235,8 +1203,8 @@ extern "C" int ffm_debug_set_sweep_ticket(ffm_ldu *A, unsigned int value)
 extern "C" int ffm_debug_tile_occupancy(int *out3)
 {
     if (!out3) return FFM_ERR_ARG;
-    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[0], k_tile<TM_FWD, false>, T_THREADS + 64, 0));
-    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[1], k_tile<TM_BWD, false>, T_THREADS + 64, 0));
+    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[0], k_tile<TM_FWD>, T_THREADS + 64, 0));
+    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[1], k_tile<TM_BWD>, T_THREADS + 64, 0));
     FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[2], k_tile_amul<true>, T_THREADS + 64, 0));
     return FFM_OK;
 }

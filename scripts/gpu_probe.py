@@ -9,7 +9,7 @@ for n in [int(a) for a in sys.argv[1:]] or [100, 200]:
     t0 = time.time()
     blk = H.HexBlock((n, n, n))
     s = H.synth_p_rgh(blk)
-    T = int(os.environ.get("FFM_TILE", "16"))
+    T = 16                                              # the library's tile edge
     hint = (blk.j // T) + 10000 * (blk.k // T)          # 2-D tiles of cell columns (used by the tile/pipe sweeps)
     cOrd, fOrd = ffm.renumber_levels(blk.nCells, blk.l, blk.u, groupHint=hint)
     l2, u2, _ = H.apply_renumbering(blk.nCells, blk.l, blk.u, cOrd, fOrd)

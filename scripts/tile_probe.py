@@ -1,5 +1,5 @@
 """Time the tiled kernels on an n^3 box: one DIC application (forward + backward sweep) and one symmetric Amul.
-   usage: tile_probe.py n [reps]      env: FFM_TILE, FFM_TILE_EDGE_ORDER, FFM_TILE_ROW_ORDER, FFM_AMUL_SEG"""
+   usage: tile_probe.py n [reps]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
@@ -26,4 +26,4 @@ for _ in range(reps): apply()
 ctx.sync(); ms = (time.perf_counter() - t0) / reps * 1e3
 sp = C.c_double()
 assert L.ffm_bench_spmv(A.h, C.c_void_p(r.data_ptr()), C.c_void_p(w.data_ptr()), reps, C.byref(sp)) == 0, L.ffm_last_error()
-print("n %d edge_order %s: DIC apply %.3f ms, Amul %.3f ms" % (n, os.environ.get("FFM_TILE_EDGE_ORDER", "1"), ms, sp.value))
+print("n %d: DIC apply %.3f ms, Amul %.3f ms" % (n, ms, sp.value))
