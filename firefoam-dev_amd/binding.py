@@ -153,6 +153,10 @@ def lib():
         "ffm_pyro_set_surface_radiation": ([vp] + [C.c_double] * 4, C.c_int),
         "ffm_pyro_evolve_d": ([vp, C.c_double, dp, dp, dp, dp, C.c_double, C.c_double], C.c_int),
         "ffm_pyro_gas_side_d": ([vp, dp, dp, dp, dp, dp, dp, C.c_double, C.c_double, dp, dp, dp, dp, dp], C.c_int),
+        "ffm_pyro_set_incident_radiation": ([vp, C.c_double, dp], C.c_int),
+        "ffm_pyro_set_qr_source": ([vp, C.c_int, dp], C.c_int),
+        "ffm_pyro_step_incident": ([vp, C.c_double], C.c_int),
+        "ffm_pyro_run_incident": ([vp, C.c_double, C.c_int, C.c_int, dp, C.c_long], C.c_int),
         "ffm_pyro_destroy": ([vp], C.c_int),
         "ffm_thermo_create": ([vp, C.c_int] + [hp] * 8 + [C.c_double, C.POINTER(vp)], C.c_int),
         "ffm_thermo_correct_d": ([vp, C.c_long, C.POINTER(vp), dp, dp, dp, dp, dp, dp], C.c_int),
@@ -935,6 +939,60 @@ class PyrolysisPanel:
         """one step with the heat flux of the last couple()"""
         self.ctx._ready()
         _check(lib().ffm_pyro_step(self.h, float(dt), C.c_void_p(lib().ffm_pyro_qSurf_d(self.h)), 0 if Tback is None else 1, 0.0 if Tback is None else float(Tback)), "ffm_pyro_step")
+
+    def set_reaction(self, A, Ta, Tcrit, n):
+        """the Arrhenius solid reaction of constant/panelRegion/reactions (ffm_pyro_set_reaction)"""
+        _check(lib().ffm_pyro_set_reaction(self.h, float(A), float(Ta), float(Tcrit), float(n)), "ffm_pyro_set_reaction")
+
+    def set_incident_radiation(self, Qr):
+        """`QrIncident` of the fixedIncidentRadiation patch [W/m2]: a scalar, or one value per column (numpy array or torch CUDA tensor)"""
+        if np.ndim(Qr) == 0:
+            _check(lib().ffm_pyro_set_incident_radiation(self.h, float(Qr), None), "ffm_pyro_set_incident_radiation")
+        else:
+            t = self._column_array(Qr)
+            _check(lib().ffm_pyro_set_incident_radiation(self.h, 0.0, C.c_void_p(t.data_ptr())), "ffm_pyro_set_incident_radiation")
+            self.ctx.sync()         # the copy has read t before it is released
+
+    def set_qr_source(self, qr0):
+        """qrHSource: qr0 = the radiative flux entering through the exposed face [W/m2] (scalar or one value per column); None: off"""
+        if qr0 is None:
+            _check(lib().ffm_pyro_set_qr_source(self.h, 0, None), "ffm_pyro_set_qr_source")
+            return
+        t = self._column_array(np.full(self.nCol, float(qr0)) if np.ndim(qr0) == 0 else qr0)
+        _check(lib().ffm_pyro_set_qr_source(self.h, 1, C.c_void_p(t.data_ptr())), "ffm_pyro_set_qr_source")
+        self.ctx.sync()
+
+    def _column_array(self, a):
+        t = a if hasattr(a, "data_ptr") else self.ctx.to_device(np.asarray(a, np.float64))
+        if tuple(t.shape) != (self.nCol,):
+            raise ValueError("expected one value per column (%d), got shape %r" % (self.nCol, tuple(t.shape)))
+        self.ctx._ready()           # t comes from torch's stream
+        return t
+
+    def step_incident(self, dt):
+        """one step with the exposed face closed by fixedIncidentRadiation (ffm_pyro_step_incident)"""
+        self.ctx._ready()
+        _check(lib().ffm_pyro_step_incident(self.h, float(dt)), "ffm_pyro_step_incident")
+
+    def run_incident(self, dt, nSteps, sampleEvery=None):
+        """nSteps steps of step_incident in one kernel launch (ffm_pyro_run_incident).  sampleEvery: record a history sample after every
+        sampleEvery-th step and return it as a dict of numpy arrays -- Twall, phiGas [nSamples][nCol]; T, rho, Yw, chemistryQdot
+        [nSamples][nCol][nLay]; None: no history, returns None"""
+        self.ctx._ready()
+        nSteps = int(nSteps)
+        if sampleEvery is None:
+            _check(lib().ffm_pyro_run_incident(self.h, float(dt), nSteps, 1, None, 0), "ffm_pyro_run_incident")
+            return None
+        sampleEvery = int(sampleEvery)
+        nS, rows = (nSteps // sampleEvery if sampleEvery > 0 else 0), 2 + 4 * self.nLay
+        hist = self.ctx.zeros(max(nS * rows * self.nCol, 1))
+        _check(lib().ffm_pyro_run_incident(self.h, float(dt), nSteps, sampleEvery, C.c_void_p(hist.data_ptr()), nS * rows * self.nCol), "ffm_pyro_run_incident")
+        self.ctx.sync()
+        H = hist.cpu().numpy()[:nS * rows * self.nCol].reshape(nS, rows, self.nCol)
+        L = self.nLay
+        layers = lambda r: np.ascontiguousarray(H[:, r:r + L, :].transpose(0, 2, 1))
+        return {"Twall": H[:, 0, :].copy(), "phiGas": H[:, 1, :].copy(), "T": layers(2), "rho": layers(2 + L), "Yw": layers(2 + 2 * L),
+                "chemistryQdot": layers(2 + 3 * L)}
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,5 +1,7 @@
 """Host-side communicator over torch.distributed (gloo): the callbacks of ffm_comm_init_host (several ranks sharing one GPU,
 the fall-back transport of bench.py when no RCCL communicator can be made) and of the oracle's ffo_comm, on CPU tensors."""
+import atexit
+
 import numpy as np
 
 
@@ -22,6 +24,16 @@ def _dist():
 def init(rank, world, port):
     dist = _dist()
     dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
+    # a rank that exits with its process group alive leaves gloo's threads to the static destructors, which now and then end the
+    # process with std::terminate ("terminate called without an active exception", exit status -6) after its work is done: shut
+    # the group down while the interpreter is still whole
+    atexit.register(_shutdown)
+
+
+def _shutdown():
+    dist = _dist()
+    if dist.is_initialized():
+        dist.destroy_process_group()
 
 
 def allreduce(vals, op=0):

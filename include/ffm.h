@@ -567,6 +567,30 @@ int ffm_pyro_gas_side_d(ffm_pyro *p, const int *map_d, const double *rho_b_d, co
 /* reactingOneDim21::solidRegionDiffNo (reactingOneDim21.C:697-714; solver/solidRegionDiffusionNo.H): max over the region's internal faces of
  * deltaCoeffs^2 interpolate(kappa())/interpolate(Cp() rho) * deltaT -- the diffusion number solver/setMultiRegionDeltaT.H limits with maxDi */
 int ffm_pyro_diff_no(ffm_pyro *p, double deltaT, double *out);
+/* The closed column: BASELINE config 1 (cases/pyrolysis1D) on its own dictionaries.
+ * ffm_pyro_set_incident_radiation: `QrIncident` of the fixedIncidentRadiation patch (cases/pyrolysis1D/0/panelRegion/T:51-55), one value
+ *   per column: Qr_d[nCol] (device, copied) or, with Qr_d NULL, uniformQr everywhere.
+ * ffm_pyro_step_incident: evolveRegion with the exposed face closed by fixedIncidentRadiationFvPatchScalarField::updateCoeffs
+ *   (lib/fvPatchFieldsPyrolysis/fixedIncidentRadiation/fixedIncidentRadiationFvPatchScalarField.C:155-213): gradient = e (QrIncident -
+ *   sigma pow4(T_cell))/kappa(*this), evaluated where OpenFOAM evaluates the patch (construction of hEqn: old cell temperature, emissivity
+ *   and kappa() of the composition after solveSpeciesMass); qSurf and the wall value of the step are stored.  The emissivity is the
+ *   surface radiation model's (`kappaMethod solidThermo`, radiationProperties:19-38): FFM_ERR_ARG with a message if
+ *   ffm_pyro_set_surface_radiation or ffm_pyro_set_incident_radiation was not called -- there is no constant to fall back to.
+ * ffm_pyro_set_qr_source: `qrHSource` of reactingOneDimCoeffs (constant/pyrolysisZones; off by default, as both shipped cases have it):
+ *   on != 0 adds the in-depth absorption of reactingOneDim::updateqr / solveEnergy (reactingOneDim.C:95-144, 335-339; reactingOneDim21.C:
+ *   96-145, 350-354) to every kind of step: qr0_d[nCol] (device, copied; clipped at 0, :110) is the radiative flux entering through the
+ *   exposed face, attenuated with the absorptivities of the surface radiation model (kappaRad(), :656-659) of the composition before
+ *   the step; cell i gains A (qr_face,i-1/2 - qr_face,i+1/2).  Call it again when qr0 changes.
+ * ffm_pyro_run_incident: solver/fireFoam.C:92-97 with `solvePrimaryRegion false` (cases/pyrolysis1D/constant/additionalControls:18) --
+ *   the time loop only calls pyrolysis.evolve() -- as ONE kernel launch: nSteps steps of ffm_pyro_step_incident with every column's
+ *   state kept in registers, bitwise equal to nSteps single steps.  hist_d (device, histCap doubles; NULL: no history): after every
+ *   sampleEvery-th step, what the case's function objects write (system/controlDict:64-176), hist_d[sample][row][column] with the
+ *   2 + 4 nLay rows Twall, phiGas, T[nLay], rho[nLay], Yw[nLay], chemistryQdot[nLay]; nSteps/sampleEvery samples.  FFM_ERR_ARG, before
+ *   anything is launched, if nSteps < 1, sampleEvery < 1 or histCap is too small.                                                    */
+int ffm_pyro_set_incident_radiation(ffm_pyro *p, double uniformQr, const double *Qr_d);
+int ffm_pyro_set_qr_source(ffm_pyro *p, int on, const double *qr0_d);
+int ffm_pyro_step_incident(ffm_pyro *p, double deltaT);
+int ffm_pyro_run_incident(ffm_pyro *p, double deltaT, int nSteps, int sampleEvery, double *hist_d, long histCap);
 int ffm_pyro_destroy(ffm_pyro *p);
 
 /* ------------------------------------------------------- thermo, combustion, LES (N2) */
