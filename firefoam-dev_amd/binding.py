@@ -113,6 +113,7 @@ def lib():
         "ffm_residual": ([vp, dp, dp, dp], C.c_int),
         "ffm_precond_setup": ([vp, C.c_int, dp], C.c_int),
         "ffm_precond_apply": ([vp, C.c_int, C.c_int, dp, dp], C.c_int),
+        "ffm_precond_setup_multi": ([vp, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
         "ffm_gs_smooth": ([vp, C.c_int, C.c_int, dp, dp], C.c_int),
         "ffm_solve_d": ([vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, dp, dp,
                          C.POINTER(Perf)], C.c_int),
@@ -594,6 +595,17 @@ class lduMatrix:
         _check(lib().ffm_precond_setup(self.h, PRECONDS[preconditioner], C.c_void_p(rD.data_ptr())), "ffm_precond_setup")
         self.ctx.sync()
         return rD
+
+    def reciprocalD_multi(self, preconditioner, diags):
+        """calcReciprocalD of systems with the bound off-diagonals and the given diagonals (native order), in the one sweep of
+        the lock-step solves (ffm_precond_setup_multi): a list of rD tensors"""
+        self.ctx._ready()
+        n = len(diags)
+        out = [self.ctx.empty(self.nCells) for _ in range(n)]
+        arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+        _check(lib().ffm_precond_setup_multi(self.h, PRECONDS[preconditioner], n, arr(diags), arr(out)), "ffm_precond_setup_multi")
+        self.ctx.sync()
+        return out
 
     def precondition(self, preconditioner, rA, transpose=False):
         self.ctx._ready()

@@ -39,7 +39,8 @@ enum {
 
 #define VSMALL_ 1e-300
 
-__global__ void k_scalar_op(double *__restrict__ s, int op, double arg, int iter)
+// in: the slot the operation takes its sum from (the prologue kernel leaves three sums in S_TMP0..S_TMP2)
+__global__ void k_scalar_op(double *__restrict__ s, int op, double arg, int iter, int in)
 {
     if (threadIdx.x || blockIdx.x) return;
     switch (op) {
@@ -49,7 +50,7 @@ __global__ void k_scalar_op(double *__restrict__ s, int op, double arg, int iter
         break;
     case OP_XREF: s[S_XREF] = s[S_TMP0] / arg; break;                    // gAverage(psi)
     case OP_NORMF: s[S_NORMF] = s[S_TMP0] + 1e-20; break;                // + solverPerformance::small_
-    case OP_RES_INIT: s[S_RES] = s[S_TMP0] / s[S_NORMF]; s[S_RES0] = s[S_RES]; break;
+    case OP_RES_INIT: s[S_RES] = s[in] / s[S_NORMF]; s[S_RES0] = s[S_RES]; break;
     case OP_RES: if (s[S_SING] == 0.0) s[S_RES] = s[S_TMP0] / s[S_NORMF]; break;
     case OP_PCG_BETA: {                                                  // wArAold = wArA; wArA = (wA,rA)
         const double old = s[S_WARA], nw = s[S_TMP0];
@@ -62,7 +63,7 @@ __global__ void k_scalar_op(double *__restrict__ s, int op, double arg, int iter
         else { s[S_SING] = 1.0; s[S_ALPHA] = 0.0; }
         break; }
     case OP_BS_RHO: {                                                    // rA0rAold = rA0rA; rA0rA = (rA0,rA)
-        const double old = s[S_RA0RA], nw = s[S_TMP0];
+        const double old = s[S_RA0RA], nw = s[in];
         s[S_RA0RA_OLD] = old; s[S_RA0RA] = nw;
         if (!(fabs(nw) > VSMALL_)) { s[S_SING] = 1.0; break; }
         if (iter > 0) {
@@ -79,9 +80,9 @@ __global__ void k_scalar_op(double *__restrict__ s, int op, double arg, int iter
     }
 }
 
-static int scalar_op(ffm_ctx *c, int op, double arg = 0.0, int iter = 0)
+static int scalar_op(ffm_ctx *c, int op, double arg = 0.0, int iter = 0, int in = S_TMP0)
 {
-    hipLaunchKernelGGL(k_scalar_op, dim3(1), dim3(64), 0, c->stream, c->scal_d, op, arg, iter);
+    hipLaunchKernelGGL(k_scalar_op, dim3(1), dim3(64), 0, c->stream, c->scal_d, op, arg, iter, in);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
@@ -98,24 +99,38 @@ static int finish_dot(ffm_ctx *c, int op, int nSlots = 1, double arg = 0.0, int 
 __global__ void k_sub(long n, double *__restrict__ r, const double *__restrict__ b, const double *__restrict__ w)
 { GRID_STRIDE(i, n) r[i] = b[i] - w[i]; }
 
-__global__ void k_sub2(long n, double *__restrict__ r, double *__restrict__ rT, const double *__restrict__ b,
-                       const double *__restrict__ w, const double *__restrict__ wT)
-{ GRID_STRIDE(i, n) { r[i] = b[i] - w[i]; rT[i] = b[i] - wT[i]; } }
 
 __global__ void k_copy(long n, double *__restrict__ d, const double *__restrict__ s)
 { GRID_STRIDE(i, n) d[i] = s[i]; }
 
-// normFactor partial: |Apsi - xRef*sumA| + |source - xRef*sumA|
-__global__ __launch_bounds__(256) void k_normf(long n, const double *__restrict__ Ax, const double *__restrict__ b,
-                                               const double *__restrict__ sumA, const double *__restrict__ scal,
-                                               double *__restrict__ partials)
+// The prologue of a solve once xRef is known, one pass over Apsi, source and sumA:
+//   rA = source - Apsi;  partials[0..] = the normFactor sum |Apsi - xRef*sumA| + |source - xRef*sumA|;  partials[RED_BLOCKS..] = sum |rA|;
+//   BS (PBiCGStab): rA0 = rA, pA = rA (the search direction of iteration 0) and partials[2*RED_BLOCKS..] = rA0.rA = sum rA*rA.
+// Grid, block, stride and block_sum are those of the reductions of ffm_ctx.hip (k_reduce1), so every sum keeps its partition and
+// its tree.  sumA may be the vector pA is written to: every load of a cell precedes its stores, hence no __restrict__ on the two.
+template <bool BS>
+__global__ __launch_bounds__(256) void k_prologue(long n, const double *__restrict__ Ax, const double *__restrict__ b, const double *sumA,
+                                                  const double *__restrict__ scal, double *__restrict__ r, double *__restrict__ r0,
+                                                  double *p, double *__restrict__ partials)
 {
     __shared__ double sm[4];
     const double xRef = scal[S_XREF];
-    double acc = 0.0;
-    GRID_STRIDE(i, n) { const double t = sumA[i] * xRef; acc += fabs(Ax[i] - t) + fabs(b[i] - t); }
-    const double r = block_sum(acc, sm);
-    if (threadIdx.x == 0) partials[blockIdx.x] = r;
+    double accN = 0.0, accR = 0.0, accD = 0.0;
+    GRID_STRIDE(i, n) {
+        const double ax = Ax[i], bi = b[i], t = sumA[i] * xRef;
+        const double ri = bi - ax;
+        accN += fabs(ax - t) + fabs(bi - t);
+        accR += fabs(ri);
+        r[i] = ri;
+        if (BS) { accD += ri * ri; r0[i] = ri; p[i] = ri; }
+    }
+    const double sN = block_sum(accN, sm);
+    const double sR = block_sum(accR, sm);
+    const double sD = BS ? block_sum(accD, sm) : 0.0;
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = sN; partials[RED_BLOCKS + blockIdx.x] = sR;
+        if (BS) partials[2 * RED_BLOCKS + blockIdx.x] = sD;
+    }
 }
 
 // pA = first ? wA : wA + beta*pA
@@ -161,14 +176,13 @@ __global__ void k_axmy_alpha(long n, double *__restrict__ r, const double *__res
     GRID_STRIDE(i, n) r[i] -= alpha * w[i];
 }
 
-// PBiCGStab: pA = first ? rA : rA + beta*(pA - omega*AyA)
+// PBiCGStab: pA = rA + beta*(pA - omega*AyA)      (iteration 0, pA = rA: k_prologue)
 __global__ void k_bs_p(long n, double *__restrict__ p, const double *__restrict__ r, const double *__restrict__ AyA,
-                       const double *__restrict__ scal, int first)
+                       const double *__restrict__ scal)
 {
     if (scal[S_SING] != 0.0) return;
     const double beta = scal[S_BETA], omega = scal[S_OMEGA];
-    if (first) { GRID_STRIDE(i, n) p[i] = r[i]; }
-    else { GRID_STRIDE(i, n) p[i] = r[i] + beta * (p[i] - omega * AyA[i]); }
+    GRID_STRIDE(i, n) p[i] = r[i] + beta * (p[i] - omega * AyA[i]);
 }
 
 // sA = rA - alpha*AyA; partial |sA|
@@ -465,10 +479,7 @@ int ffm_sweep_check_abort(ffm_ldu *A)
 static int calc_rD(ffm_ldu *A)
 {
     if (A->sweepMode == 2) {
-        FFM_TRY(ffm_tile_calc_rD(A));
-        hipLaunchKernelGGL(k_recip, dim3(sgrid(A->nOwned)), dim3(256), 0, A->ctx->stream, (long)A->nOwned, A->rD, A->rD);
-        FFM_HIP(hipGetLastError());
-        return FFM_OK;
+        return ffm_tile_calc_rD(A);          // (stores 1/D)
     }
     FlowArgs a; FFM_TRY(flow_args(A, SM_RD, a));
     FLOW_LAUNCH(SM_RD, a);
@@ -557,20 +568,21 @@ static inline bool check_convergence(ffm_perf *p, const Controls &k)
     return p->converged;
 }
 
-// normFactor + initial residual: wA = A psi already computed, rA = source - wA already formed
-// tmp holds sumA on entry (ffm_k_spmv_sumA at the top of every solver)
-static int norm_and_initial(ffm_ldu *A, const double *psi, const double *source, const double *Apsi, double *tmp,
-                            const double *rA, ffm_perf *perf)
+// rA = source - Apsi, normFactor and the initial residual: Apsi = A psi already computed, tmp holds sumA on entry
+// (ffm_k_spmv_sumA at the top of every solver).  PBiCGStab passes rA0 and pA (pA may be tmp) and gets rA0 = pA = rA and
+// rA0.rA in S_TMP2 as well (k_prologue).  The sums' ranks are added in one all-reduce.
+static int norm_and_initial(ffm_ldu *A, const double *psi, const double *source, const double *Apsi, const double *tmp,
+                            double *rA, ffm_perf *perf, double *rA0 = nullptr, double *pA = nullptr)
 {
     ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned;
     FFM_TRY(ffm_k_sum(c, psi, N, S_TMP0));
     FFM_TRY(finish_dot(c, OP_XREF, 1, (double)A->globalCells));
-    const int g = sgrid(N);
-    hipLaunchKernelGGL(k_normf, dim3(g), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, c->partials_d);
-    FFM_TRY(partial_sum_to(c, g, S_TMP0));
-    FFM_TRY(finish_dot(c, OP_NORMF));
-    FFM_TRY(ffm_k_summag(c, rA, N, S_TMP0));
-    FFM_TRY(finish_dot(c, OP_RES_INIT));
+    const int g = sgrid(N), nSums = rA0 ? 3 : 2;
+    if (rA0) hipLaunchKernelGGL(k_prologue<true>, dim3(g), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, rA0, pA, c->partials_d);
+    else hipLaunchKernelGGL(k_prologue<false>, dim3(g), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, (double *)nullptr, (double *)nullptr, c->partials_d);
+    FFM_TRY(partial_sum_to(c, g, S_TMP0, nSums));
+    FFM_TRY(finish_dot(c, OP_NORMF, nSums));
+    FFM_TRY(scalar_op(c, OP_RES_INIT, 0.0, 0, S_TMP1));
     FFM_TRY(ffm_read_scalars(c));
     perf->initialResidual = c->scal_h[S_RES0];
     perf->finalResidual = perf->initialResidual;
@@ -586,7 +598,6 @@ static int pcg(ffm_ldu *A, int precond, const Controls &k, double *psi, const do
     FFM_TRY(ffm_ldu_work(A, 1, &pA)); FFM_TRY(ffm_ldu_work(A, 2, &wA)); FFM_TRY(ffm_ldu_work(A, 3, &rA));
     FFM_TRY(scalar_op(c, OP_RESET));
     FFM_TRY(ffm_k_spmv_sumA(A, psi, wA, pA));
-    hipLaunchKernelGGL(k_sub, dim3(g), dim3(256), 0, s, N, rA, source, wA);
     FFM_TRY(norm_and_initial(A, psi, source, wA, pA, rA, perf));
     if (k.minIter > 0 || !check_convergence(perf, k)) {
         FFM_TRY(ffm_precond_setup_i(A, precond));
@@ -651,20 +662,21 @@ static int pbicgstab(ffm_ldu *A, int precond, const Controls &k, double *psi, co
 {
     ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned; const int g = sgrid(N);
     double *yA, *rA, *pA, *AyA, *sA, *zA, *tA, *rA0;
-    FFM_TRY(ffm_ldu_work(A, 1, &pA)); FFM_TRY(ffm_ldu_work(A, 2, &yA)); FFM_TRY(ffm_ldu_work(A, 3, &rA));
+    FFM_TRY(ffm_ldu_work(A, 1, &pA)); FFM_TRY(ffm_ldu_work(A, 2, &yA)); FFM_TRY(ffm_ldu_work(A, 3, &rA)); FFM_TRY(ffm_ldu_work(A, 8, &rA0));
     FFM_TRY(scalar_op(c, OP_RESET));
     FFM_TRY(ffm_k_spmv_sumA(A, psi, yA, pA));
-    hipLaunchKernelGGL(k_sub, dim3(g), dim3(256), 0, s, N, rA, source, yA);
-    FFM_TRY(norm_and_initial(A, psi, source, yA, pA, rA, perf));
+    FFM_TRY(norm_and_initial(A, psi, source, yA, pA, rA, perf, rA0, pA));
     if (k.minIter > 0 || !check_convergence(perf, k)) {
         FFM_TRY(ffm_ldu_work(A, 4, &AyA)); FFM_TRY(ffm_ldu_work(A, 5, &sA)); FFM_TRY(ffm_ldu_work(A, 6, &zA));
-        FFM_TRY(ffm_ldu_work(A, 7, &tA)); FFM_TRY(ffm_ldu_work(A, 8, &rA0));
-        hipLaunchKernelGGL(k_copy, dim3(g), dim3(256), 0, s, N, rA0, rA);
+        FFM_TRY(ffm_ldu_work(A, 7, &tA));
         FFM_TRY(ffm_precond_setup_i(A, precond));
         do {
-            FFM_TRY(ffm_k_dot(c, rA0, rA, N, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_BS_RHO, 1, 0.0, perf->nIterations));
-            hipLaunchKernelGGL(k_bs_p, dim3(g), dim3(256), 0, s, N, pA, rA, AyA, c->scal_d, perf->nIterations == 0 ? 1 : 0);
+            if (perf->nIterations == 0) FFM_TRY(scalar_op(c, OP_BS_RHO, 0.0, 0, S_TMP2));        // rA0.rA and pA = rA came with the prologue
+            else {
+                FFM_TRY(ffm_k_dot(c, rA0, rA, N, S_TMP0));
+                FFM_TRY(finish_dot(c, OP_BS_RHO, 1, 0.0, perf->nIterations));
+                hipLaunchKernelGGL(k_bs_p, dim3(g), dim3(256), 0, s, N, pA, rA, AyA, c->scal_d);
+            }
             FFM_TRY(ffm_precond_apply_i(A, precond, false, pA, yA));
             FFM_TRY(ffm_k_spmv(A, yA, AyA, false));
             FFM_TRY(ffm_k_dot(c, rA0, AyA, N, S_TMP0));
@@ -705,7 +717,7 @@ static int pbicg(ffm_ldu *A, int precond, const Controls &k, double *psi, const 
     FFM_TRY(scalar_op(c, OP_RESET));
     FFM_TRY(ffm_k_spmv_sumA(A, psi, wA, pA));
     FFM_TRY(ffm_k_spmv(A, psi, wT, true));
-    hipLaunchKernelGGL(k_sub2, dim3(g), dim3(256), 0, s, N, rA, rT, source, wA, wT);
+    hipLaunchKernelGGL(k_sub, dim3(g), dim3(256), 0, s, N, rT, source, wT);
     FFM_TRY(norm_and_initial(A, psi, source, wA, pA, rA, perf));
     if (k.minIter > 0 || !check_convergence(perf, k)) {
         FFM_TRY(ffm_precond_setup_i(A, precond));
@@ -737,13 +749,12 @@ static int pbicg(ffm_ldu *A, int precond, const Controls &k, double *psi, const 
 static int smooth(ffm_ldu *A, int smoother, const Controls &k, double *psi, const double *source, ffm_perf *perf)
 {
     if (smoother != FFM_GS && smoother != FFM_SYMGS) { ffm_set_error("smoothSolver: smoother must be GaussSeidel or symGaussSeidel"); return FFM_ERR_UNSUPPORTED; }
-    ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned; const int g = sgrid(N);
+    ffm_ctx *c = A->ctx; const long N = A->nOwned;
     const int nSweeps = k.nSweeps > 0 ? k.nSweeps : 1;
     double *Apsi, *tmp, *res;
     FFM_TRY(ffm_ldu_work(A, 1, &Apsi)); FFM_TRY(ffm_ldu_work(A, 2, &tmp)); FFM_TRY(ffm_ldu_work(A, 3, &res));
     FFM_TRY(scalar_op(c, OP_RESET));
     FFM_TRY(ffm_k_spmv_sumA(A, psi, Apsi, tmp));
-    hipLaunchKernelGGL(k_sub, dim3(g), dim3(256), 0, s, N, res, source, Apsi);
     FFM_TRY(norm_and_initial(A, psi, source, Apsi, tmp, res, perf));
     if (k.minIter > 0 || !check_convergence(perf, k)) {
         do {
@@ -872,27 +883,24 @@ static int pbicgstab_multi(ffm_ldu *A, int precond, const Controls &k, int n, La
     for (int i = 0; i < n; i++) {
         Lane &l = L[i]; G.use(l);
         FFM_TRY(scalar_op(c, OP_RESET));
-        hipLaunchKernelGGL(k_sub, dim3(g), dim3(256), 0, s, N, l.rA, l.source, l.yA);
-        FFM_TRY(norm_and_initial(A, l.psi, l.source, l.yA, l.pA, l.rA, l.perf));          // (reads this lane's scalars back)
+        FFM_TRY(norm_and_initial(A, l.psi, l.source, l.yA, l.pA, l.rA, l.perf, l.rA0, l.pA));          // (reads this lane's scalars back)
         l.active = k.minIter > 0 || !check_convergence(l.perf, k);
-        if (l.active) hipLaunchKernelGGL(k_copy, dim3(g), dim3(256), 0, s, N, l.rA0, l.rA);
     }
     {   // calcReciprocalD of the systems that iterate
         const double *dg[FFM_TILE_MAXSYS]; double *D[FFM_TILE_MAXSYS]; int m = 0, only = -1;
         for (int i = 0; i < n; i++) if (L[i].active) { dg[m] = L[i].diag; D[m] = L[i].rD; m++; only = i; }
-        if (m >= 2) {
-            FFM_TRY(ffm_tile_calc_rD_multi(A, m, dg, D));
-            for (int j = 0; j < m; j++) hipLaunchKernelGGL(k_recip, dim3(g), dim3(256), 0, s, N, D[j], (const double *)D[j]);
-        } else if (m == 1) { G.use(L[only]); A->rDKind = -1; FFM_TRY(ffm_precond_setup_i(A, precond)); }
+        if (m >= 2) FFM_TRY(ffm_tile_calc_rD_multi(A, m, dg, D));          // (stores 1/D)
+        else if (m == 1) { G.use(L[only]); A->rDKind = -1; FFM_TRY(ffm_precond_setup_i(A, precond)); }
         A->rDKind = precond; A->rDEpoch = A->coeffEpoch;         // every lane's rD is current: the single-lane calls below must not redo it
     }
     for (;;) {
         bool any = false;
         for (int i = 0; i < n; i++) if (L[i].active) {
             Lane &l = L[i]; G.use(l); any = true;
+            if (l.perf->nIterations == 0) { FFM_TRY(scalar_op(c, OP_BS_RHO, 0.0, 0, S_TMP2)); continue; }
             FFM_TRY(ffm_k_dot(c, l.rA0, l.rA, N, S_TMP0));
             FFM_TRY(finish_dot(c, OP_BS_RHO, 1, 0.0, l.perf->nIterations));
-            hipLaunchKernelGGL(k_bs_p, dim3(g), dim3(256), 0, s, N, l.pA, l.rA, l.AyA, c->scal_d, l.perf->nIterations == 0 ? 1 : 0);
+            hipLaunchKernelGGL(k_bs_p, dim3(g), dim3(256), 0, s, N, l.pA, l.rA, l.AyA, c->scal_d);
         }
         if (!any) break;
         FFM_TRY(precond_lanes(A, precond, L, n, &Lane::pA, &Lane::yA, G));
@@ -1000,6 +1008,21 @@ extern "C" int ffm_precond_setup(ffm_ldu *A, int precond, double *rD_out_d)
     if (!A) return FFM_ERR_ARG;
     FFM_TRY(ffm_precond_setup_i(A, precond));
     if (rD_out_d) FFM_TRY(ffm_from_internal(A, A->rD, rD_out_d));
+    FFM_HIP(hipStreamSynchronize(A->ctx->stream));
+    FFM_TRY(ffm_sweep_check_abort(A));
+    return FFM_OK;
+}
+
+// the reciprocal diagonals of several systems from the one sweep of the lock-step solves (tests)
+extern "C" int ffm_precond_setup_multi(ffm_ldu *A, int precond, int nSys, const double *const *diag_d, double *const *rD_out_d)
+{
+    if (!A || !diag_d || !rD_out_d || nSys < 2 || nSys > FFM_TILE_MAXSYS) { ffm_set_error("ffm_precond_setup_multi: bad argument"); return FFM_ERR_ARG; }
+    if (precond != FFM_DIC && precond != FFM_DILU) { ffm_set_error("ffm_precond_setup_multi: DIC or DILU"); return FFM_ERR_UNSUPPORTED; }
+    if (!(A->identity && A->sweepMode == 2 && ffm_tile_multi_usable(A))) { ffm_set_error("ffm_precond_setup_multi needs a tiled matrix in the library's cell order"); return FFM_ERR_UNSUPPORTED; }
+    if (precond == FFM_DIC && !A->symmetric) { ffm_set_error("DIC needs a symmetric matrix"); return FFM_ERR_UNSUPPORTED; }
+    for (int i = 0; i < nSys; i++) if (!diag_d[i] || !rD_out_d[i]) { ffm_set_error("ffm_precond_setup_multi: null array"); return FFM_ERR_ARG; }
+    FFM_HIP(hipSetDevice(A->ctx->device));
+    FFM_TRY(ffm_tile_calc_rD_multi(A, nSys, diag_d, rD_out_d));
     FFM_HIP(hipStreamSynchronize(A->ctx->stream));
     FFM_TRY(ffm_sweep_check_abort(A));
     return FFM_OK;

@@ -405,7 +405,7 @@ __device__ __noinline__ double t_wait_value(const double *addr, unsigned int *ti
 
 // TM_FWD: w[c] = rD[c]*r[c] - sum_k rD[c]*a[c][k]*w[l_k]           (k ascending: the reference's face order)
 // TM_BWD: w[c] -= sum_k rD[c]*a[c][k]*w[u_k]                       (k descending)
-// TM_RD : D[c] = diag[c] - sum_k a[c][k]*b[c][k]/D[l_k]            (k ascending; the caller inverts D afterwards)
+// TM_RD : D[c] = diag[c] - sum_k a[c][k]*b[c][k]/D[l_k]            (k ascending); D stays in the ring and the mailboxes, w[c] = 1/D[c]
 // TM_GSF: Gauss-Seidel forward row sweep: v = bPrime[c] - sum_k lower[c][k]*psi[l_k] (new values); aux[c] = v (kept for the
 //         reverse sweep of symGaussSeidel); v -= b[c][k] for k = 0..2 (b = upper*psi_old of the upper neighbours, computed
 //         by k_tile_gs_products; +0.0 where there is none); psi[c] = v/diag[c]
@@ -563,7 +563,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const doubl
                     for (int s = 0; s < W; s++) { const double nv = val - pa[k][s] * x[s]; val = (cd[s] != T_NONE) ? nv : val; }
                     val = val / d;
                 }
-                if (pok[k]) { *(double *)((char *)w + c * 8u) = val; ring[(c - gs) & (unsigned)(T_RING - 1)] = val; }
+                if (pok[k]) { *(double *)((char *)w + c * 8u) = (MODE == TM_RD) ? 1.0 / val : val; ring[(c - gs) & (unsigned)(T_RING - 1)] = val; }
                 if (FUSE && MODE == TM_BWD) fsum += pok[k] ? val * pv2[FUSE ? k : 0] : 0.0;
                 if (pok[k] && cd[3] != T_NONE) t_st(&t.mail[ppb[k] + cd[3]], val);
             }
@@ -713,7 +713,7 @@ int ffm_tile_gs(ffm_ldu *A, bool sym, double *psi, const double *bP, double *bSa
     return FFM_OK;
 }
 
-// D = diag - sum upper*lower/D[l] in face order (un-inverted; the caller inverts)
+// rD = 1/D, D = diag - sum upper*lower/D[l] in face order
 int ffm_tile_calc_rD(ffm_ldu *A)
 {
     ffm_tile_plan *T = A->tile;
@@ -862,7 +862,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
                 if (pok[k]) {
 #pragma unroll
                     for (int i = 0; i < NF; i++) {
-                        *(double *)((char *)m.w[i] + c * 8u) = val[i];
+                        *(double *)((char *)m.w[i] + c * 8u) = (MODE == TM_RD) ? 1.0 / val[i] : val[i];
                         ring[i][(c - gs) & (unsigned)(T_RING - 1)] = val[i];
                         if (cd[3] != T_NONE) t_st(&m.mail[i][ppb[k] + cd[3]], val[i]);
                     }
@@ -909,7 +909,7 @@ int ffm_tile_precond_multi(ffm_ldu *A, int precond, int n, const double *const *
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
-// D[i] = diag[i] - sum upper*lower/D[i][l] in face order (un-inverted) for n systems
+// D[i] = 1/(diag[i] - sum upper*lower/D[i][l]) in face order for n systems
 int ffm_tile_calc_rD_multi(ffm_ldu *A, int n, const double *const *diag, double *const *D)
 {
     ffm_tile_plan *T = A->tile;

@@ -220,6 +220,9 @@ int ffm_residual(ffm_ldu *ldu, const double *x_d, const double *b_d, double *r_d
 int ffm_precond_setup(ffm_ldu *ldu, int precond, double *rD_out_d /*nullable*/);
 int ffm_precond_apply(ffm_ldu *ldu, int precond, int transpose,
                       const double *r_d, double *w_d);
+/* calcReciprocalD (DIC / DILU) of nSys = 2..4 systems that share the bound off-diagonal coefficients and differ in the diagonal,
+ * in the ONE sweep ffm_solve_multi_d uses for them (tiled matrix in the library's cell order; anything else is refused).           */
+int ffm_precond_setup_multi(ffm_ldu *ldu, int precond, int nSys, const double *const *diag_d, double *const *rD_out_d);
 int ffm_gs_smooth(ffm_ldu *ldu, int symmetric_sweep, int nSweeps, double *psi_d,
                   const double *b_d);
 
