@@ -192,6 +192,131 @@ extern "C" int b1_demo(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, double deltaT,
     return n;
 }
 
+// ---- A mesh whose matrix handle has a history (tests/test_foam_layer_reuse_gpu.py): solves in the order that leaves the library's
+// gathered off-diagonal layouts belonging to ANOTHER equation when a matrix is solved again -- fvMatrix::solve() may tell the library
+// `the off-diagonals are those of the previous call` only while that is true.  Inputs as in b1_demo; the p_rgh-like equation as in
+// b1_gamg_solve.  otherDiag [N] / otherUpperF [F, LDU face order] / otherSource [N]: a symmetric system "another user" of mesh.ldu
+// sets and solves directly through the C ABI.  The statements:
+//   R1  YiEqn (ddt + div - laplacian == R, relaxed; PBiCGStab + DILU) from Yi0          UEqn (PBiCGStab: the lock-step vector solve)
+//   R2  the same YiEqn again from Yi0
+//   R3  YjEqn: the same rho, phi, common weights and diffusivity (its coefficient arrays are YiEqn's: fvMesh::transportCache)      UEqn
+//   R4  YjEqn again from Yj0
+//   R5  p_rghEqn (PCG + DIC) from p0      the other user sets its coefficients on mesh.ldu and solves
+//   R6  p_rghEqn again from p0            p_rghEqn by GAMG from p0 (-> gamgOut)
+//   R7  p_rghEqn by PCG again from p0
+// fieldsOut [7][N]; nIterOut [14] / residualsOut [14][2] in the order of mesh.log (R1, U x 3, R2, R3, U x 3, R4, R5, R6, GAMG, R7);
+// epochsOut [9]: ffm_ldu_offdiag_epoch after R1, UEqn, R2, R3, UEqn, R4, R5, the other user, R6.  Returns the number of solves logged.
+extern "C" int b1_solve_sequence(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, ffm_gamg* gamg, double deltaT, double alphaY,
+                                 const double* rhoOld, const double* rhoNow, const double* phiF, const double* phiB,
+                                 const double* Yi0, const double* Yj0, const double* const* bcY, const double* dEffC, const double* RYi, const double* RYj,
+                                 const double* U0, const double* const* bcU, double muValue,
+                                 const double* psiC, const double* gammaC, const double* p0, const double* const* bcP, const double* SC,
+                                 const double* otherDiag, const double* otherUpperF, const double* otherSource,
+                                 double* fieldsOut, double* gamgOut, int* nIterOut, double* residualsOut, unsigned long* epochsOut)
+{
+    fvMesh mesh(ctx, ldu, msh, deltaT);
+    mesh.gamg = gamg;
+    const solverControls krylovY = {FFM_PBICGSTAB, FFM_DILU, 1e-10, 0, 0, 1000, 1}, pcg = {FFM_PCG, FFM_DIC, 1e-10, 0, 0, 1000, 1};
+    solverControls mg; mg.solver = FFM_GAMG; mg.preconditioner = FFM_GS; mg.tolerance = 1e-8; mg.relTol = 0;
+    mesh.solvers["U"] = krylovY;
+    mesh.divSchemes["div(phi,U)"] = {4, 1, 0, 1};               // Gauss LUST grad(U)
+    mesh.multivariateSelection["div(phi,Yi_h)"] = {{"Yi", {3, 1, 0, 1}}, {"Yj", {3, 1, 0, 1}}};      // limitedLinear01 1 for both
+    mesh.equationRelaxation["Yi"] = alphaY; mesh.equationRelaxation["Yj"] = alphaY;
+    const label N = mesh.nCells;
+    const std::vector<double> zeroB(mesh.nBoundary, 0.0);
+    int nEpoch = 0;
+    auto epoch = [&]() { epochsOut[nEpoch++] = ffm_ldu_offdiag_epoch(ldu); };
+    auto keep = [&](int k, const volScalarField& f) { f.v.toHost(fieldsOut + (size_t)k*N); };
+
+    volScalarField rho("rho", mesh); rho.v.assignHost(rhoOld); rho.b.assignHost(zeroB.data());
+    rho.storeOldTime();
+    rho.v.assignHost(rhoNow);
+    const surfaceScalarField phi(surfaceFromHost(mesh, phiF, phiB));
+    volScalarField Yi("Yi", mesh), Yj("Yj", mesh);
+    Yi.v.assignHost(Yi0); Yi.bc = makeBC(mesh, bcY[0], bcY[1], bcY[2]); Yi.correctBoundaryConditions(); Yi.storeOldTime();
+    Yj.v.assignHost(Yj0); Yj.bc = makeBC(mesh, bcY[0], bcY[1], bcY[2]); Yj.correctBoundaryConditions(); Yj.storeOldTime();
+    volScalarField dEff("dEff", mesh); dEff.v.assignHost(dEffC); dEff.b.assignHost(zeroB.data());
+    dEff.bc = makeBC(mesh, zeroB.data(), zeroB.data(), zeroB.data()); dEff.correctBoundaryConditions();          // zeroGradient
+    volScalarField Ri("Ri", mesh), Rj("Rj", mesh); Ri.v.assignHost(RYi); Rj.v.assignHost(RYj);
+    multivariateSurfaceInterpolationScheme<scalar>::fieldTable fields;
+    fields.add(Yi); fields.add(Yj);
+    tmp<fv::convectionScheme<scalar>> mvConvection(fv::convectionScheme<scalar>::New(mesh, fields, phi, mesh.divScheme("div(phi,Yi_h)")));
+
+    volVectorField U("U", mesh);
+    for (int d = 0; d < 3; d++) { U.v[d].assignHost(U0 + (size_t)d*N); U.bc[d] = makeBC(mesh, bcU[3*d], bcU[3*d + 1], bcU[3*d + 2]); }
+    U.correctBoundaryConditions(); U.storeOldTime();
+    volScalarField mu("mu", mesh, muValue);
+    fvVectorMatrix UEqn
+    (
+        fvm::ddt(rho, U) + fvm::div(phi, U)
+      - fvm::laplacian(mu, U)
+    );
+
+    // ---- the specie equations around the vector solve
+    fvScalarMatrix YiEqn
+    (
+        fvm::ddt(rho, Yi)
+      + mvConvection->fvmDiv(phi, Yi)
+      - fvm::laplacian(dEff, Yi)
+     ==
+        Ri
+    );
+    YiEqn.relax();
+    YiEqn.solve(krylovY); keep(0, Yi); epoch();
+    UEqn.solve(mesh.solver("U")); epoch();
+    Yi.v.assignHost(Yi0);
+    YiEqn.solve(krylovY); keep(1, Yi); epoch();
+    fvScalarMatrix YjEqn
+    (
+        fvm::ddt(rho, Yj)
+      + mvConvection->fvmDiv(phi, Yj)
+      - fvm::laplacian(dEff, Yj)
+     ==
+        Rj
+    );
+    YjEqn.relax();
+    YjEqn.solve(krylovY); keep(2, Yj); epoch();
+    UEqn.solve(mesh.solver("U")); epoch();
+    Yj.v.assignHost(Yj0);
+    YjEqn.solve(krylovY); keep(3, Yj); epoch();
+
+    // ---- the pressure-like equation around other users of the matrix handle
+    volScalarField psi("psi", mesh); psi.v.assignHost(psiC); psi.bc = makeBC(mesh, zeroB.data(), zeroB.data(), zeroB.data()); psi.correctBoundaryConditions();
+    psi.storeOldTime();
+    volScalarField gamma("gamma", mesh); gamma.v.assignHost(gammaC); gamma.bc = makeBC(mesh, zeroB.data(), zeroB.data(), zeroB.data()); gamma.correctBoundaryConditions();
+    volScalarField p_rgh("p_rgh", mesh); p_rgh.v.assignHost(p0); p_rgh.bc = makeBC(mesh, bcP[0], bcP[1], bcP[2]);
+    p_rgh.correctBoundaryConditions(); p_rgh.storeOldTime();
+    volScalarField S("S", mesh); S.v.assignHost(SC);
+    fvScalarMatrix p_rghEqn
+    (
+        fvm::ddt(psi, p_rgh) - fvm::laplacian(gamma, p_rgh)
+     ==
+        S
+    );
+    p_rghEqn.solve(pcg); keep(4, p_rgh); epoch();
+    {
+        dField oD(ctx, N), oU(ctx, mesh.nInternalNative), oB(ctx, N), oX(ctx, N);
+        oD.assignHost(otherDiag); oB.assignHost(otherSource);
+        FFM_FOAM_CHK(ffm_faces_to_native(msh, otherUpperF, oU.data()));
+        FFM_FOAM_CHK(ffm_ldu_set_coeffs_native_d(ldu, rd(oD), rd(oU), nullptr));
+        ffm_perf pf;
+        FFM_FOAM_CHK(ffm_solve_d(ldu, FFM_PCG, FFM_DIC, 1e-8, 0, 0, 1000, 1, oX.data(), rd(oB), &pf));
+        if (pf.nIterations < 1) FatalError("b1_solve_sequence: the other user's solve did not iterate");
+    }
+    epoch();
+    p_rgh.v.assignHost(p0);
+    p_rghEqn.solve(pcg); keep(5, p_rgh); epoch();
+    p_rgh.v.assignHost(p0);
+    p_rghEqn.solve(mg); p_rgh.v.toHost(gamgOut);
+    p_rgh.v.assignHost(p0);
+    p_rghEqn.solve(pcg); keep(6, p_rgh);
+
+    FFM_FOAM_CHK(ffm_ctx_sync(ctx));
+    int n = 0;
+    for (const solverPerformance& sp : mesh.log) { nIterOut[n] = sp.nIterations; residualsOut[2*n] = sp.initialResidual; residualsOut[2*n + 1] = sp.finalResidual; n++; }
+    return n;
+}
+
 // The order in which pimpleControl walks one time step (no device work): for every pass of the innermost loop one int
 //   outer*10000 + corrector*100 + nonOrthogonal*10 + finalInnerIter, then -1 at the end of each outer pass.
 extern "C" int b1_pimple_sequence(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, int nOuter, int nCorr, int nNonOrth, int* out, int cap)

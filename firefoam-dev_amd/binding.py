@@ -86,6 +86,7 @@ def lib():
         "ffm_ctx_create": ([C.c_int, vp, C.POINTER(vp)], C.c_int),
         "ffm_ctx_destroy": ([vp], C.c_int),
         "ffm_ctx_sync": ([vp], C.c_int),
+        "ffm_ctx_trim": ([vp], C.c_int),
         "ffm_ctx_stream": ([vp], vp),
         "ffm_last_error": ([], C.c_char_p),
         "ffm_version": ([], C.c_char_p),
@@ -122,6 +123,8 @@ def lib():
         "ffm_solve_multi_d": ([vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_void_p), dp, dp,
                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(Perf)], C.c_int),
         "ffm_ldu_unbind_coeffs": ([vp], C.c_int),
+        "ffm_ldu_offdiag_epoch": ([vp], C.c_ulong),
+        "ffm_debug_pool_poison": ([vp, C.c_int], C.c_int),
         "ffm_bench_spmv": ([vp, dp, dp, C.c_int, hp], C.c_int),
         "ffm_bench_precond": ([vp, C.c_int, dp, dp, C.c_int, hp], C.c_int),
         "ffm_debug_set_sweep_ticket": ([vp, C.c_uint], C.c_int),
@@ -380,6 +383,18 @@ class Context:
         self._ready()               # the fill runs on torch's stream: complete before libffm's stream writes into the tensor
         return z
 
+    def debug_pool_poison(self, on):
+        """tests: while on, every block ffm_malloc_uninit hands out is NaN-filled (ffm_debug_pool_poison); returns the number of blocks
+        filled since the switch was last turned on"""
+        n = lib().ffm_debug_pool_poison(self.h, 1 if on else 0)
+        if n < 0:
+            raise FfmError("ffm_debug_pool_poison failed (%d)" % n)
+        return n
+
+    def trim(self):
+        """give the allocator's cached blocks back to the runtime (ffm_ctx_trim)"""
+        _check(lib().ffm_ctx_trim(self.h), "ffm_ctx_trim")
+
     def _ready(self):
         # tensors produced on torch's stream must be complete before libffm's stream reads them
         self.torch.cuda.current_stream().synchronize()
@@ -511,13 +526,26 @@ class lduMatrix:
         _check(lib().ffm_ldu_get_face_map(self.h, _ip(m)), "ffm_ldu_get_face_map")
         return m
 
-    def bind_coeffs_native(self, diag, upper, lower=None):
+    def bind_coeffs_native(self, diag, upper, lower=None, offDiagUnchanged=False):
         """zero-copy: the matrix reads device tensors in the library's native layout (diag [nCells], upper / lower [nNative])
-        until the next set / bind call; the caller keeps them alive (ffm_ldu_bind_coeffs_native_d)"""
+        until the next set / bind call; the caller keeps them alive (ffm_ldu_bind_coeffs_native_d).  offDiagUnchanged: upper / lower
+        hold the values of the previous bind, the layouts the library derived from them are kept"""
         self._bound = (diag, upper, lower)
         _check(lib().ffm_ldu_bind_coeffs_native_d(self.h, C.c_void_p(diag.data_ptr()), C.c_void_p(upper.data_ptr()),
-                                                  None if lower is None else C.c_void_p(lower.data_ptr()), 0), "ffm_ldu_bind_coeffs_native_d")
+                                                  None if lower is None else C.c_void_p(lower.data_ptr()), 1 if offDiagUnchanged else 0),
+               "ffm_ldu_bind_coeffs_native_d")
         return self
+
+    def unbind_coeffs(self):
+        """ends a bind: the matrix refers to its own buffers again and the bound tensors may go (ffm_ldu_unbind_coeffs)"""
+        _check(lib().ffm_ldu_unbind_coeffs(self.h), "ffm_ldu_unbind_coeffs")
+        self._bound = None
+        return self
+
+    @property
+    def offdiag_epoch(self):
+        """the generation of the off-diagonal coefficients (ffm_ldu_offdiag_epoch)"""
+        return int(lib().ffm_ldu_offdiag_epoch(self.h))
 
     def debug_set_sweep_ticket(self, value):
         """tests: preset the group ticket counter of the tiled sweeps (each sweep launch zeroes it again)"""

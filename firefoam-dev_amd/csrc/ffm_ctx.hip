@@ -69,15 +69,25 @@ extern "C" int ffm_ctx_trim(ffm_ctx *c)
     c->poolFree.clear(); c->poolCachedBytes = 0;
     return FFM_OK;
 }
-__global__ void k_zero_bytes8(size_t n8, unsigned long long *__restrict__ d)
-{ for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) d[i] = 0ull; }
-// zero-fill on the context's stream by a kernel of this library (size classes are multiples of 8 bytes)
-static int pool_zero(ffm_ctx *c, void *p, size_t bytes)
+__global__ void k_fill_bytes8(size_t n8, unsigned long long *__restrict__ d, unsigned long long v)
+{ for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) d[i] = v; }
+// fill with one 64-bit value on the context's stream by a kernel of this library (size classes are multiples of 8 bytes)
+static int pool_fill(ffm_ctx *c, void *p, size_t bytes, unsigned long long v)
 {
     const size_t n8 = bytes / 8;
-    if (n8) hipLaunchKernelGGL(k_zero_bytes8, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((n8 + 255) / 256, 4096))), dim3(256), 0, c->stream, n8, (unsigned long long *)p);
+    if (n8) hipLaunchKernelGGL(k_fill_bytes8, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((n8 + 255) / 256, 4096))), dim3(256), 0, c->stream, n8, (unsigned long long *)p, v);
     if (bytes % 8) FFM_HIP(hipMemsetAsync((char *)p + 8 * n8, 0, bytes % 8, c->stream));
     FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+static int pool_zero(ffm_ctx *c, void *p, size_t bytes) { return pool_fill(c, p, bytes, 0ull); }
+// ffm_debug_pool_poison: a quiet NaN that is neither mailbox sentinel of the sweeps (ffm_tile.hip: T_SENT, ffm_solve.hip: FLOW_SENT --
+// a sentinel in user data would make a sweep wait for a value that never comes)
+constexpr unsigned long long POOL_POISON = 0x7FF8B01550B01550ull;
+static inline int pool_hand_out(ffm_ctx *c, void *p, size_t cls, bool zero)
+{
+    if (zero) return pool_zero(c, p, cls);             // as fresh memory: the padding slots of face arrays must read 0
+    if (c->poolPoison) { c->poolPoisoned++; return pool_fill(c, p, cls, POOL_POISON); }
     return FFM_OK;
 }
 static int pool_alloc(ffm_ctx *c, size_t bytes, void **p, bool zero)
@@ -87,8 +97,7 @@ static int pool_alloc(ffm_ctx *c, size_t bytes, void **p, bool zero)
     auto it = c->poolFree.find(cls);
     if (it != c->poolFree.end() && !it->second.empty()) {
         *p = it->second.back(); it->second.pop_back(); c->poolCachedBytes -= cls;
-        if (zero) FFM_TRY(pool_zero(c, *p, cls));          // as fresh memory: the padding slots of face arrays must read 0
-        return FFM_OK;
+        return pool_hand_out(c, *p, cls, zero);
     }
     FFM_HIP(hipSetDevice(c->device));
     if (hipMalloc(p, cls) != hipSuccess) {                       // out of memory: give the cached blocks back and try once more
@@ -97,8 +106,15 @@ static int pool_alloc(ffm_ctx *c, size_t bytes, void **p, bool zero)
         FFM_HIP(hipMalloc(p, cls));
     }
     c->poolSize[*p] = cls;
-    if (zero) FFM_TRY(pool_zero(c, *p, cls));
-    return FFM_OK;
+    return pool_hand_out(c, *p, cls, zero);
+}
+extern "C" int ffm_debug_pool_poison(ffm_ctx *c, int on)
+{
+    if (!c) return FFM_ERR_ARG;
+    const int n = c->poolPoisoned;
+    if (on && !c->poolPoison) c->poolPoisoned = 0;
+    c->poolPoison = on != 0;
+    return n;
 }
 extern "C" int ffm_malloc(ffm_ctx *c, size_t bytes, void **p) { return pool_alloc(c, bytes, p, true); }
 extern "C" int ffm_malloc_uninit(ffm_ctx *c, size_t bytes, void **p) { return pool_alloc(c, bytes, p, false); }

@@ -88,6 +88,8 @@ struct ffm_ctx {
     std::unordered_map<size_t, std::vector<void *>> poolFree;
     std::unordered_map<void *, size_t> poolSize;
     size_t poolCachedBytes = 0, poolCapBytes = (size_t)96 << 30;
+    bool poolPoison = false;              // ffm_debug_pool_poison (tests): unzeroed blocks are handed out NaN-filled
+    int poolPoisoned = 0;                 // ... and counted
 };
 
 // Host <-> device copies, correct by construction: the context's stream is created non-blocking, so a null-stream hipMemcpy neither

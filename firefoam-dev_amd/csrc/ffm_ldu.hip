@@ -862,6 +862,8 @@ extern "C" int ffm_ldu_unbind_coeffs(ffm_ldu *A)
     return FFM_OK;
 }
 
+extern "C" unsigned long ffm_ldu_offdiag_epoch(const ffm_ldu *A) { return A ? A->offDiagEpoch : 0ul; }
+
 LduView ffm_view(const ffm_ldu *A)
 {
     LduView v; v.N = A->nOwned; v.upOff = A->upOff; v.loOff = A->loOff; v.upNbr = A->upNbr; v.loEnt = A->loEnt;

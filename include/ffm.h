@@ -189,6 +189,10 @@ int ffm_ldu_bind_coeffs_native_d(ffm_ldu *ldu, const double *diag_d, const doubl
                                  const double *lower_d, int offDiagUnchanged);
 /* ends a bind: the matrix refers to its own buffers again (contents unspecified until the next set / bind), the caller may free its arrays */
 int ffm_ldu_unbind_coeffs(ffm_ldu *ldu);
+/* the generation of the off-diagonal coefficients: every set call and every bind with offDiagUnchanged == 0 advances it, unbind and
+ * a bind with offDiagUnchanged != 0 do not.  A caller that remembers which arrays it bound last may pass offDiagUnchanged != 0 only
+ * while this value is the one it saw after that bind: nobody else has given the matrix other off-diagonals meanwhile          */
+unsigned long ffm_ldu_offdiag_epoch(const ffm_ldu *ldu);
 
 /* processor patches (lduInterface / interfaceBouCoeffs / interfaceIntCoeffs):
  * face i of patch p couples cell faceCells[p][i] (caller numbering) with face i
@@ -716,6 +720,10 @@ int ffm_comm_size(const ffm_ctx *ctx);
 /* tests: preset the group ticket counter of the tiled sweeps (every sweep launch zeroes it again on the stream, so a preset
  * close to 2^32 must not change any result)                                                                             */
 int ffm_debug_set_sweep_ticket(ffm_ldu *A, unsigned int value);
+/* tests: while on != 0, every block ffm_malloc_uninit hands out (fresh or recycled) is filled over its whole size class with one
+ * quiet-NaN pattern on the context's stream, so that a consumer which lets a padding slot or a ghost row of such an array reach a
+ * real value shows.  Returns the number of blocks filled since the switch was last turned on (< 0: error).  Off by default       */
+int ffm_debug_pool_poison(ffm_ctx *ctx, int on);
 
 /* ------------------------------------------------------- decomposition (host) */
 /* decomposePar's job for this path (reference: scotch, cases/steckler/system/decomposeParDict:18-20; `simple`,

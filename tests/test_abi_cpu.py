@@ -11,6 +11,8 @@ def test_library_loads_and_exports_every_declared_symbol(ffm):
     assert len(declared) > 30
     missing = [s for s in declared if s not in exported]
     assert not missing, "declared in include/ffm.h but not exported by libffm.so: %s" % missing
+    for name in ("ffm_debug_pool_poison", "ffm_ldu_offdiag_epoch"):          # test support of the reuse / poison tests
+        assert name in declared and name in exported, name
     L = ffm.lib()
     assert b"gfx950" in L.ffm_version()
 

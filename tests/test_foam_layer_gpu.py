@@ -16,41 +16,13 @@ pytestmark = pytest.mark.gpu
 
 def test_b1_demo_matches_oracle(O, ffm, ctx):
     from oracle import fv, plume
-    m = plume.make_mesh((9, 8, 7), h=0.1)
-    N, F = m.nCells, m.nFaces
-    B = sum(p.size for p in m.patches)
-    cOrd, fOrd = ffm.renumber_levels(N, m.l, m.u)
-    l2, u2, oldToNew = ffm.hexmesh.apply_renumbering(N, m.l, m.u, cOrd, fOrd)
-    A = ffm.lduMatrix(ctx, N, l2, u2)
-    patches = [(oldToNew[p.faceCells].astype(np.int32), p.Sf.T.copy(), p.deltaCoeffs) for p in m.patches]
-    mesh = ffm.fvMesh(A, m.V[cOrd], m.C[cOrd].T.copy(), m.Sf[fOrd].T.copy(), m.magSf[fOrd], m.weights[fOrd], m.deltaCoeffs[fOrd], patches)
-    mesh.set_face_centres(m.Cf[fOrd].T.copy())
-    hu = lambda seed, n: O.hash_u(seed, np.arange(n))
-    pl = lambda seed, scale=1.0, shift=0.0: [shift + scale * hu(seed + q, p.size) for q, p in enumerate(m.patches)]
-    dt, alphaY, mu = 2e-3, 0.8, 1.8e-5
-    rho_old = 1.0 + 0.2 * hu(1, N); rho_now = rho_old * (1 + 0.01 * (hu(2, N) - 0.5))
-    phi = 0.02 * (hu(3, F) - 0.5); phib = pl(10, 0.02, -0.01)
-    Yi0 = 0.1 + 0.8 * hu(4, N); dEff = 2e-5 * (1 + hu(5, N)); R = 0.5 * (hu(6, N) - 0.5)
-    U0 = np.stack([hu(20 + d, N) - 0.5 for d in range(3)])
-    p_rgh = 10.0 * (hu(7, N) - 0.5); ghf = -9.81 * m.Cf[:, 1]; ghfb = [-9.81 * p.Cf[:, 1] for p in m.patches]
-    bcY = fv.MixedBC(m, f=pl(30), ref=pl(40, 0.5), refGrad=pl(50, 0.1, -0.05))
-    bcU = [fv.MixedBC(m, f=pl(60 + 10 * d), ref=pl(90 + 10 * d, 1.0, -0.5)) for d in range(3)]
-    p_b = pl(120, 10.0, -5.0)
-    # pEqn inputs: compressibility now / old, gh, pRef; p_rgh: fixedFluxPressure on inlet, floor and sides (gradient set by
-    # constrainPressure), fixedValue on the top; U fixes its value on inlet and floor
-    psi_now = 1.17e-5 * (0.9 + 0.2 * hu(130, N)); psi_old = psi_now * (1 + 1e-3 * (hu(131, N) - 0.5))
-    gh = -9.81 * m.C[:, 1]; pRef = 101325.0
-    names = [p.name for p in m.patches]
-    fluxMask = [np.full(p.size, 0.0 if p.name == "top" else 1.0) for p in m.patches]
-    UfixMask = [np.full(p.size, 1.0 if p.name in ("inlet", "floor") else 0.0) for p in m.patches]
-    for d in range(3):                                    # consistent with the mask: fixedValue there
-        for q, p in enumerate(m.patches):
-            if p.name in ("inlet", "floor"):
-                bcU[d].f[q] = np.ones(p.size)
-    bcP = fv.MixedBC(m, f=[np.full(p.size, 1.0 if p.name == "top" else 0.0) for p in m.patches], ref=pl(140, 2.0, -1.0))
-    rdt = 1.0 / dt
-    zb = [np.zeros(p.size) for p in m.patches]
-    ctl = dict(tolerance=1e-10, relTol=0.0)
+    from b1_case import b1_inputs, run_b1_demo
+    I = b1_inputs(O, ffm, ctx)
+    A, mesh, m, N, F, B, cOrd, fOrd = I.A, I.mesh, I.m, I.N, I.F, I.B, I.cOrd, I.fOrd
+    dt, alphaY, mu, pRef, rdt, zb, ctl = I.dt, I.alphaY, I.mu, I.pRef, I.rdt, I.zb, I.ctl
+    rho_old, rho_now, phi, phib, Yi0, dEff, R, U0 = I.rho_old, I.rho_now, I.phi, I.phib, I.Yi0, I.dEff, I.R, I.U0
+    p_rgh, ghf, p_b, psi_now, psi_old, gh = I.p_rgh, I.ghf, I.p_b, I.psi_now, I.psi_old, I.gh
+    bcY, bcU, bcP, fluxMask, UfixMask = I.bcY, I.bcU, I.bcP, I.fluxMask, I.UfixMask
 
     # ------------------------------------------------------------------ the oracle's evaluation of the same statements
     M = fv.fvm_ddt(m, rdt, np.ones(N), np.ones(N), rho_old); M.add_vol(fv.surface_integrate(m, phi, phib))
@@ -115,35 +87,7 @@ def test_b1_demo_matches_oracle(O, ffm, ctx):
     Ucorr_ref = HbyA_ref + rAU_ref * rec2.T
 
     # ------------------------------------------------------------------ the C++ layer on the device
-    lib = C.CDLL(os.path.join(os.path.dirname(ffm.libpath()), "libffm_b1demo.so"))
-    dp = C.POINTER(C.c_double)
-    h = lambda a: np.ascontiguousarray(a, np.float64)
-    cell = lambda a: h(np.asarray(a)[..., cOrd])
-    face = lambda a: h(np.asarray(a)[fOrd])
-    bnd = lambda lst: h(np.concatenate(lst))
-    keep = []
-    def P(a):
-        keep.append(a)
-        return a.ctypes.data_as(dp)
-    def PP(arrs):
-        arrs = [h(a) for a in arrs]; keep.append(arrs)
-        arr = (dp * len(arrs))(*[a.ctypes.data_as(dp) for a in arrs]); keep.append(arr)
-        return arr
-    out = dict(rho=np.empty(N), Yi=np.empty(N), U=np.empty((3, N)), K=np.empty(N), rAU=np.empty(N), HbyA=np.empty((3, N)),
-               p=np.empty(N), phi=np.empty(F), phib=np.empty(B), Uc=np.empty((3, N)))
-    nit = (C.c_int * 16)()
-    lib.b1_demo.restype = C.c_int
-    lib.b1_demo.argtypes = ([C.c_void_p] * 3 + [C.c_double] * 2 + [dp] * 5 + [C.POINTER(dp)] + [dp] * 3 + [C.POINTER(dp)] + [C.c_double] + [dp] * 4
-                            + [dp] * 3 + [C.c_double] + [C.POINTER(dp)] + [dp] * 2 + [dp] * 10 + [C.POINTER(C.c_int)])
-    bcPp = PP([bnd(bcP.f), bnd(bcP.ref), bnd(bcP.refGrad)])
-    bcYp = PP([bnd(bcY.f), bnd(bcY.ref), bnd(bcY.refGrad)])
-    bcUp = PP([x for d in range(3) for x in (bnd(bcU[d].f), bnd(bcU[d].ref), bnd(bcU[d].refGrad))])
-    ctx._ready()
-    ns = lib.b1_demo(ctx.h, A.h, mesh.h, dt, alphaY, P(cell(rho_old)), P(cell(rho_now)), P(face(phi)), P(bnd(phib)),
-                     P(cell(Yi0)), bcYp, P(cell(dEff)), P(cell(R)), P(cell(U0)), bcUp, mu, P(face(ghf)), P(bnd(ghfb)),
-                     P(cell(p_rgh)), P(bnd(p_b)), P(cell(psi_now)), P(cell(psi_old)), P(cell(gh)), pRef, bcPp, P(bnd(fluxMask)), P(bnd(UfixMask)),
-                     P(out["rho"]), P(out["Yi"]), P(out["U"]), P(out["K"]), P(out["rAU"]), P(out["HbyA"]),
-                     P(out["p"]), P(out["phi"]), P(out["phib"]), P(out["Uc"]), nit)
+    ns, out, nit = run_b1_demo(ffm, ctx, I)
     assert ns == 6                                   # rho, Yi, Ux, Uy, Uz, p_rgh
     back = lambda a: (lambda o: (o.__setitem__((Ellipsis, cOrd), a), o)[1])(np.empty_like(a))
     assert np.array_equal(back(out["rho"]), rho_new)
