@@ -90,6 +90,7 @@ struct ScalarEqns {
     const double *vf[FUSE_MAX], *gx[FUSE_MAX], *gy[FUSE_MAX], *gz[FUSE_MAX], *vf0[FUSE_MAX];
     const double *f[FUSE_MAX], *ref[FUSE_MAX], *refGrad[FUSE_MAX];      // mixed patch condition [B]
     const double *su[FUSE_MAX];                                          // explicit volume source (nullable)
+    double suFactor[FUSE_MAX];                                           // SUSCALED: the source of field i is suFactor[i]*su[i] (the species' nu_i*wFuel)
     const double *su2[FUSE_MAX], *sp[FUSE_MAX];                          // a second explicit source and an implicit one (fvm::Sp): nullable
     const double *expl[FUSE_MAX][3];                                     // explicit LHS volume terms (nullable)
     double *diag[FUSE_MAX], *upper[FUSE_MAX], *lower[FUSE_MAX], *src[FUSE_MAX];
@@ -108,7 +109,7 @@ struct ScalarEqns {
 // waves spill too much (25 / 27 ms), and the one-field kernel is better left alone (7.97 vs 8.35 ms).  Measured r02u.
 // GIVENW: the face weights come from a.wGiven (a multivariateSelection scheme's common weights) instead of one limiter per field: no
 // gradient / neighbour-value gathers at all
-template <int W, int NF, bool GIVENW = false>
+template <int W, int NF, bool GIVENW = false, bool SUSCALED = false>
 __global__ __launch_bounds__(256, ((NF > 1 && !GIVENW) ? 4 : 1)) void k_scalar_eqns(MeshView q, ScalarEqns a)
 {
     CELL_SCHED(ci, q) {
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(256, ((NF > 1 && !GIVENW) ? 4 : 1)) void k_scalar_e
             // source: ddt, explicit LHS terms (one `source -= V*term` each), explicit source
             double sc = a.rdt * rho0c * a.vf0[i][c] * V;
             if (a.expl[i][0]) sc = ((sc - V * a.expl[i][0][c]) - V * a.expl[i][1][c]) - V * a.expl[i][2][c];
-            if (a.su[i]) sc = sc + V * a.su[i][c];
+            if (a.su[i]) sc = sc + V * (SUSCALED ? a.suFactor[i] * a.su[i][c] : a.su[i][c]);
             if (a.sp[i]) d = d + V * a.sp[i][c];
             if (a.su2[i]) sc = sc + V * a.su2[i][c];
             // boundary coefficients of the mixed condition, added in (patch, face) order
@@ -481,6 +482,59 @@ __global__ __launch_bounds__(256) void k_lust_source(MeshView q, LustSource a)
     }
 }
 
+// The explicit left-hand-side terms of EEqn (solver/YEEqn.H:89-101) in one pass over the cells:
+//     divK = fvc::div(phi, K) with `Gauss limitedLinear 1`,  ddtK = fvc::ddt(rho, K),  ndpdt = -dpdt
+// Each cell walks its faces in the order of k_face_sum (lower entries, owned slots, boundary faces) and forms per face the
+// limitedLinear weight (k_limited_weights), the interpolated K (k_interpolate) and its product with phi -- the expressions of
+// the per-operator passes, so both cells of a face get the same bits and no face field is written.
+struct DivPhiK {
+    const double *K, *Kb, *gx, *gy, *gz, *phi, *phib, *rho, *rho0, *K0, *dpdt, *Cx, *Cy, *Cz;
+    double *divK, *ddtK, *ndpdt;
+    double rdt, twoByk, lo, hi;
+    int scheme;
+};
+template <int W>
+__global__ __launch_bounds__(256) void k_div_phiK(MeshView q, DivPhiK a)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci;
+        RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
+        const double cx = a.Cx[c], cy = a.Cy[c], cz = a.Cz[c];
+        const double P = a.K[c], gxc = a.gx[c], gyc = a.gy[c], gzc = a.gz[c];
+        double fl[W], fu[W], wl[W], wu[W], kl[W], ku[W], dlx[W], dly[W], dlz[W], dux[W], duy[W], duz[W], glx[W], gly[W], glz[W], gux[W], guy[W], guz[W];
+#pragma unroll
+        for (int s = 0; s < W; s++) {
+            const int el = L.f[s], eu = U.f[s], o = L.nb[s], n = U.nb[s];
+            fl[s] = a.phi[el]; fu[s] = a.phi[eu]; wl[s] = q.w[el]; wu[s] = q.w[eu];
+            kl[s] = a.K[o]; ku[s] = a.K[n];
+            // d = C[neighbour] - C[owner]; the gradient of the upwind cell (the owner when the flux is positive)
+            dlx[s] = cx - a.Cx[o]; dly[s] = cy - a.Cy[o]; dlz[s] = cz - a.Cz[o];
+            dux[s] = a.Cx[n] - cx; duy[s] = a.Cy[n] - cy; duz[s] = a.Cz[n] - cz;
+            const bool upl = fl[s] > 0, upu = fu[s] > 0;
+            glx[s] = upl ? a.gx[o] : gxc; gly[s] = upl ? a.gy[o] : gyc; glz[s] = upl ? a.gz[o] : gzc;
+            gux[s] = upu ? gxc : a.gx[n]; guy[s] = upu ? gyc : a.gy[n]; guz[s] = upu ? gzc : a.gz[n];
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int s = 0; s < W; s++) if (L.on[s]) {          // owner = L.nb[s], neighbour = c
+            const double w = limited_weight(a.scheme, a.twoByk, a.lo, a.hi, fl[s], wl[s], kl[s], P, dlx[s], dly[s], dlz[s], glx[s], gly[s], glz[s]);
+            const double Kf = w * kl[s] + (1.0 - w) * P;
+            acc = acc - fl[s] * Kf;
+        }
+#pragma unroll
+        for (int s = 0; s < W; s++) if (U.on[s]) {
+            const double w = limited_weight(a.scheme, a.twoByk, a.lo, a.hi, fu[s], wu[s], P, ku[s], dux[s], duy[s], duz[s], gux[s], guy[s], guz[s]);
+            const double Kf = w * P + (1.0 - w) * ku[s];
+            acc += fu[s] * Kf;
+        }
+        const int j = q.cellB[c];
+        if (j >= 0) for (int t = q.bcStart[j]; t < q.bcStart[j + 1]; t++) { const int k = q.bcItem[t]; acc += a.phib[k] * a.Kb[k]; }
+        a.divK[c] = acc / q.V[c];
+        a.ddtK[c] = a.rdt * (a.rho[c] * P - a.rho0[c] * a.K0[c]);
+        a.ndpdt[c] = -a.dpdt[c];
+    }
+}
+
 // ------------------------------------------------------------------ entry points (internal + C ABI) ---
 
 extern "C" int ffm_fvc_grad_multi(ffm_mesh *m, int nf, const double *const *vf, const double *const *vb, double *const *gx,
@@ -519,7 +573,7 @@ extern "C" int ffm_fvm_scalar_transport_multi(ffm_mesh *m, int nf, int scheme, d
                        (m->B && (!f[q] || !ref[q] || !refGrad[q])))) return FFM_ERR_ARG;
         a.vf[i] = vf[q]; a.gx[i] = gx[q]; a.gy[i] = gy[q]; a.gz[i] = gz[q]; a.vf0[i] = vf0[q];
         a.f[i] = f[q]; a.ref[i] = ref[q]; a.refGrad[i] = refGrad[q];
-        a.su[i] = su ? su[q] : nullptr;
+        a.su[i] = su ? su[q] : nullptr; a.suFactor[i] = 1.0;
         a.su2[i] = su2 ? su2[q] : nullptr; a.sp[i] = sp ? sp[q] : nullptr;
         for (int e = 0; e < 3; e++) a.expl[i][e] = expl3 ? expl3[3 * q + e] : nullptr;
         if (a.expl[i][0] && (!a.expl[i][1] || !a.expl[i][2])) return FFM_ERR_ARG;
@@ -557,14 +611,17 @@ extern "C" int ffm_fv_multivariate_weights(ffm_mesh *m, int nf, const int *schem
 
 // ffm_fvm_scalar_transport_multi with the face weights given (a multivariate scheme's common weights) instead of one limiter per field:
 // ddt(rho, vf_i) + div(phi, vf_i) [weights w_f] - laplacian(gamma, vf_i) == su_i ... for nf fields in one pass
-extern "C" int ffm_fvm_scalar_transport_multi_w(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
-                                                const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
-                                                const double *const *vf0, const double *const *f, const double *const *ref,
-                                                const double *const *refGrad, const double *const *su, const double *const *su2,
-                                                const double *const *sp, const double *const *expl3, double *const *diag,
-                                                double *const *upper, double *const *lower, double *const *source)
+// suFactor (nullable): the explicit source of field i is suFactor[i]*su[i], the product formed where it is used -- the species of
+// solver/YEEqn.H share one reaction rate and differ in the stoichiometric factor only
+extern "C" int ffm_fvm_scalar_transport_multi_ws(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
+                                                 const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
+                                                 const double *const *vf0, const double *const *f, const double *const *ref,
+                                                 const double *const *refGrad, const double *const *su, const double *suFactor,
+                                                 const double *const *su2, const double *const *sp, const double *const *expl3,
+                                                 double *const *diag, double *const *upper, double *const *lower, double *const *source)
 {
     CHECK_M(m);
+    if (suFactor && !su) return FFM_ERR_ARG;
     if (nf < 1 || nf > FUSE_MAX || !w_f || !rho || !rho0 || !phi_f || !gamma_f || (m->B && (!phi_b || !gamma_b))) return FFM_ERR_ARG;
     if (!vf0 || !f || !ref || !refGrad || !diag || !upper || !lower || !source) return FFM_ERR_ARG;
     ScalarEqns a;
@@ -573,7 +630,7 @@ extern "C" int ffm_fvm_scalar_transport_multi_w(ffm_mesh *m, int nf, const doubl
         if (i < nf && (!vf0[q] || !diag[q] || !source[q] || (m->B && (!f[q] || !ref[q] || !refGrad[q])))) return FFM_ERR_ARG;
         a.vf[i] = a.gx[i] = a.gy[i] = a.gz[i] = nullptr; a.vf0[i] = vf0[q];
         a.f[i] = f[q]; a.ref[i] = ref[q]; a.refGrad[i] = refGrad[q];
-        a.su[i] = su ? su[q] : nullptr;
+        a.su[i] = su ? su[q] : nullptr; a.suFactor[i] = suFactor ? suFactor[q] : 1.0;
         a.su2[i] = su2 ? su2[q] : nullptr; a.sp[i] = sp ? sp[q] : nullptr;
         for (int e = 0; e < 3; e++) a.expl[i][e] = expl3 ? expl3[3 * q + e] : nullptr;
         if (a.expl[i][0] && (!a.expl[i][1] || !a.expl[i][2])) return FFM_ERR_ARG;
@@ -585,11 +642,22 @@ extern "C" int ffm_fvm_scalar_transport_multi_w(ffm_mesh *m, int nf, const doubl
     // off-diagonals: every field with non-null upper AND lower writes its own; the fields after the first null pair share what was written
     a.nOffDiag = 0;
     for (int i = 0; i < nf; i++) { if (upper[i] && lower[i]) { if (a.nOffDiag != i) return FFM_ERR_ARG; a.nOffDiag = i + 1; } else if ((upper[i] == nullptr) != (lower[i] == nullptr)) return FFM_ERR_ARG; }
-#define SEW(NF) FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_scalar_eqns<W, NF, true>), mview(m), a))
+#define SEW(NF) do { if (suFactor) FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_scalar_eqns<W, NF, true, true>), mview(m), a)); \
+                     else FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_scalar_eqns<W, NF, true, false>), mview(m), a)); } while (0)
     switch (nf) { case 1: SEW(1); break; case 2: SEW(2); break; case 3: SEW(3); break; default: SEW(4); break; }
 #undef SEW
     FFM_HIP(hipGetLastError());
     return FFM_OK;
+}
+extern "C" int ffm_fvm_scalar_transport_multi_w(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
+                                                const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
+                                                const double *const *vf0, const double *const *f, const double *const *ref,
+                                                const double *const *refGrad, const double *const *su, const double *const *su2,
+                                                const double *const *sp, const double *const *expl3, double *const *diag,
+                                                double *const *upper, double *const *lower, double *const *source)
+{
+    return ffm_fvm_scalar_transport_multi_ws(m, nf, w_f, rDeltaT, rho, rho0, phi_f, phi_b, gamma_f, gamma_b, vf0, f, ref, refGrad, su, nullptr, su2, sp,
+                                             expl3, diag, upper, lower, source);
 }
 
 extern "C" int ffm_fvm_lust_source3(ffm_mesh *m, double rDeltaT, const double *phi_f, const double *rho0, const double *const *U0,
@@ -606,6 +674,30 @@ extern "C" int ffm_fvm_lust_source3(ffm_mesh *m, double rDeltaT, const double *p
     a.phi = phi_f; a.rho0 = rho0; a.Cx = m->C[0]; a.Cy = m->C[1]; a.Cz = m->C[2]; a.Cfx = m->Cf[0]; a.Cfy = m->Cf[1]; a.Cfz = m->Cf[2];
     a.rdt = rDeltaT;
     FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_lust_source<W>, mview(m), a));
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// fvc::div(phi, K) (limitedLinear k or limitedLinear01 k: scheme 2 / 3), fvc::ddt(rho, K) and -dpdt of the owned cells: k_div_phiK.
+// K_b, phi_b: boundary values [B]; gx, gy, gz: fvc::grad(K), ghost cells refreshed by the caller.  FFM_ERR_UNSUPPORTED (nothing launched) on
+// meshes with more than 8 lower or upper neighbours per cell.
+extern "C" int ffm_fvc_div_phiK_terms(ffm_mesh *m, int scheme, double k, double lo, double hi, double rDeltaT, const double *phi_f,
+                                      const double *phi_b, const double *K, const double *K_b, const double *gx, const double *gy,
+                                      const double *gz, const double *rho, const double *rho0, const double *K0, const double *dpdt,
+                                      double *divK, double *ddtK, double *negDpdt)
+{
+    CHECK_M(m);
+    if ((scheme != 2 && scheme != 3) || !phi_f || !K || !gx || !gy || !gz || !rho || !rho0 || !K0 || !dpdt || !divK || !ddtK || !negDpdt) return FFM_ERR_ARG;
+    if (m->B && (!phi_b || !K_b)) return FFM_ERR_ARG;
+    DivPhiK a;
+    a.K = K; a.Kb = K_b; a.gx = gx; a.gy = gy; a.gz = gz; a.phi = phi_f; a.phib = phi_b; a.rho = rho; a.rho0 = rho0; a.K0 = K0; a.dpdt = dpdt;
+    a.Cx = m->C[0]; a.Cy = m->C[1]; a.Cz = m->C[2]; a.divK = divK; a.ddtK = ddtK; a.ndpdt = negDpdt;
+    a.rdt = rDeltaT; a.twoByk = 2.0 / std::max(k, 1e-15); a.lo = lo; a.hi = hi; a.scheme = scheme;
+    // rows wider than 8 entries would spill the per-face registers to scratch: the caller runs the per-operator passes there
+    if (m->A->maxW > 8) return FFM_ERR_UNSUPPORTED;
+    if (m->A->maxW <= 3) LAUNCH_CELLS(k_div_phiK<3>, mview(m), a);
+    else if (m->A->maxW <= 4) LAUNCH_CELLS(k_div_phiK<4>, mview(m), a);
+    else LAUNCH_CELLS(k_div_phiK<8>, mview(m), a);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
@@ -681,6 +773,32 @@ __global__ __launch_bounds__(256) void k_flux_rho(MeshView q, const double *__re
             out[e] = (w * Px + (1.0 - w) * (rN * vx[nb])) * q.Sfx[e] + (w * Py + (1.0 - w) * (rN * vy[nb])) * q.Sfy[e] + (w * Pz + (1.0 - w) * (rN * vz[nb])) * q.Sfz[e];
         }
     }
+}
+// fvc::ddtCorr(rho, U, phi) on the internal faces (solver/pEqn.H:13): coeff*rDeltaT*(phi0 - fvc::flux(rho0*U0)), the flux of k_flux_rho
+// consumed where it is formed (ddtCouplingCoeff: 1 - min(|phiCorr|/(|phi0| + SMALL), 1))
+__global__ __launch_bounds__(256) void k_ddt_corr(MeshView q, double rdt, const double *__restrict__ rho, const double *__restrict__ vx,
+                                                  const double *__restrict__ vy, const double *__restrict__ vz, const double *__restrict__ phi0,
+                                                  double *__restrict__ out)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci; const double rP = rho[c]; const double Px = rP * vx[c], Py = rP * vy[c], Pz = rP * vz[c];
+        FOR_OWN_FACES(q, c, e, nb) {
+            const double w = q.w[e], rN = rho[nb];
+            const double fl0 = (w * Px + (1.0 - w) * (rN * vx[nb])) * q.Sfx[e] + (w * Py + (1.0 - w) * (rN * vy[nb])) * q.Sfy[e] + (w * Pz + (1.0 - w) * (rN * vz[nb])) * q.Sfz[e];
+            const double p0 = phi0[e], phiCorr = p0 - fl0;
+            const double coeff = 1.0 - fmin(fabs(phiCorr) / (fabs(p0) + 1e-15), 1.0);
+            out[e] = coeff * rdt * phiCorr;
+        }
+    }
+}
+extern "C" int ffm_fvc_ddt_corr(ffm_mesh *m, double rDeltaT, const double *rho0, const double *vx0, const double *vy0, const double *vz0,
+                                const double *phi0_f, double *out_f)
+{
+    CHECK_M(m);
+    if (!rho0 || !vx0 || !vy0 || !vz0 || !phi0_f || !out_f) return FFM_ERR_ARG;
+    LAUNCH_CELLS(k_ddt_corr, mview(m), rDeltaT, rho0, vx0, vy0, vz0, phi0_f, out_f);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
 }
 extern "C" int ffm_fvc_flux_rho(ffm_mesh *m, const double *rho, const double *vx, const double *vy, const double *vz, double *out_f)
 {

@@ -386,6 +386,30 @@ __global__ void k_face_sum(MeshView q, const double *__restrict__ ssf, const dou
     }
 }
 
+// rhoEqn (solver/rhoEqn.H:33-43): fvm::ddt(rho) + fvc::div(phi) == 0 is diagonal -- k_face_sum<0> with the solve as its epilogue,
+// rho = (rDeltaT*rho0*V - V*div)/(rDeltaT*V); div does not go through memory
+template <int W>
+__global__ void k_rho_eqn(MeshView q, double rdt, const double *__restrict__ ssf, const double *__restrict__ ssb, const double *__restrict__ rho0,
+                          double *__restrict__ rho)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci;
+        RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
+        double a[W], b[W];
+#pragma unroll
+        for (int s = 0; s < W; s++) { a[s] = ssf[L.f[s]]; b[s] = ssf[U.f[s]]; }
+        double acc = 0.0;
+#pragma unroll
+        for (int s = 0; s < W; s++) if (L.on[s]) acc = acc - a[s];
+#pragma unroll
+        for (int s = 0; s < W; s++) if (U.on[s]) acc += b[s];
+        const int j = q.cellB[c];
+        if (j >= 0 && ssb) for (int t = q.bcStart[j]; t < q.bcStart[j + 1]; t++) acc += ssb[q.bcItem[t]];
+        const double V = q.V[c], div = acc / V;
+        rho[c] = (rdt * rho0[c] * V - V * div) / (rdt * V);
+    }
+}
+
 // fvc::grad, Gauss linear: (1/V) sum_f Sf * (w P + (1-w) N); face values formed on the fly exactly
 // as the owner row would form them, so no face field is materialised
 template <int W>
@@ -558,6 +582,26 @@ __global__ void k_matrix_A(MeshView q, int nc, const double *__restrict__ diag, 
     }
 }
 
+// k_matrix_A with the cell algebra that follows it in solver/pEqn.H:1-3 on a single block: rho = psi*p (thermo.rho()), rAU = 1/A,
+// rhorAU = rho*rAU
+__global__ void k_matrix_rAU(MeshView q, int nc, const double *__restrict__ diag, const double *__restrict__ ic0, const double *__restrict__ ic1,
+                             const double *__restrict__ ic2, const double *__restrict__ psi, const double *__restrict__ p,
+                             double *__restrict__ rho, double *__restrict__ rAU, double *__restrict__ rhorAU)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci;
+        double d = diag[c];
+        const int j = q.cellB[c];
+        if (j >= 0) for (int t = q.bcStart[j]; t < q.bcStart[j + 1]; t++) {
+            const int k = q.bcItem[t];
+            d += (nc == 3) ? (ic0[k] + ic1[k] + ic2[k]) / 3.0 : ic0[k];
+        }
+        const double A = d / q.V[c];
+        const double r = psi[c] * p[c], ra = 1.0 / A;
+        rho[c] = r; rAU[c] = ra; rhorAU[c] = r * ra;
+    }
+}
+
 // fvMatrix::H() for one component: ((avgBD - BD_cmpt)*psi - sum_offdiag a*psi_nb + source + boundarySource)/V
 template <int W>
 __global__ void k_matrix_H(MeshView q, int nc, const double *__restrict__ upper, const double *__restrict__ lower,
@@ -616,6 +660,17 @@ extern "C" int ffm_fvc_flux(ffm_mesh *m, const double *vx, const double *vy, con
 { CHECK_M(m); LAUNCH_CELLS(k_flux, mview(m), vx, vy, vz, out_f); DONE(); }
 extern "C" int ffm_fvc_surface_integrate(ffm_mesh *m, const double *ssf, const double *ssb, double *out)
 { CHECK_M(m); FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_face_sum<0, W>), mview(m), ssf, ssb, out)); DONE(); }
+extern "C" int ffm_fvc_rho_eqn(ffm_mesh *m, double rDeltaT, const double *phi_f, const double *phi_b, const double *rho0, double *rho)
+{
+    CHECK_M(m);
+    if (!phi_f || !rho0 || !rho || rho == rho0) return FFM_ERR_ARG;
+    if (m->A->maxW > 16) return FFM_ERR_UNSUPPORTED;       // 32 slots per row would spill: ffm_fvc_surface_integrate + the cell algebra there
+    if (m->A->maxW <= 3) LAUNCH_CELLS(k_rho_eqn<3>, mview(m), rDeltaT, phi_f, phi_b, rho0, rho);
+    else if (m->A->maxW <= 4) LAUNCH_CELLS(k_rho_eqn<4>, mview(m), rDeltaT, phi_f, phi_b, rho0, rho);
+    else if (m->A->maxW <= 8) LAUNCH_CELLS(k_rho_eqn<8>, mview(m), rDeltaT, phi_f, phi_b, rho0, rho);
+    else LAUNCH_CELLS(k_rho_eqn<16>, mview(m), rDeltaT, phi_f, phi_b, rho0, rho);
+    DONE();
+}
 extern "C" int ffm_fvc_surface_sum(ffm_mesh *m, const double *ssf, const double *ssb, double *out)
 { CHECK_M(m); FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_face_sum<1, W>), mview(m), ssf, ssb, out)); DONE(); }
 extern "C" int ffm_fvc_grad(ffm_mesh *m, const double *vf, const double *vb, double *gx, double *gy, double *gz)
@@ -757,6 +812,13 @@ extern "C" int ffm_fvm_add_boundary(ffm_mesh *m, const double *ic, const double 
 { CHECK_M(m); LAUNCH_CELLS(k_add_boundary, mview(m), ic, bc, diag, src, su, diagOut, srcOut); DONE(); }
 extern "C" int ffm_fvm_A(ffm_mesh *m, int nc, const double *diag, const double *ic0, const double *ic1, const double *ic2, double *out)
 { CHECK_M(m); if (nc != 1 && nc != 3) return FFM_ERR_ARG; LAUNCH_CELLS(k_matrix_A, mview(m), nc, diag, ic0, ic1, ic2, out); DONE(); }
+extern "C" int ffm_fvm_rAU(ffm_mesh *m, int nc, const double *diag, const double *ic0, const double *ic1, const double *ic2, const double *psi,
+                           const double *p, double *rho, double *rAU, double *rhorAU)
+{
+    CHECK_M(m);
+    if ((nc != 1 && nc != 3) || !diag || !psi || !p || !rho || !rAU || !rhorAU) return FFM_ERR_ARG;
+    LAUNCH_CELLS(k_matrix_rAU, mview(m), nc, diag, ic0, ic1, ic2, psi, p, rho, rAU, rhorAU); DONE();
+}
 extern "C" int ffm_fvm_H(ffm_mesh *m, int nc, int cmpt, const double *upper, const double *lower, const double *src,
                          const double *ic0, const double *ic1, const double *ic2, const double *bcC, const double *psi, double *out)
 {

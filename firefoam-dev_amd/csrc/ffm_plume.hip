@@ -99,7 +99,7 @@ struct ffm_plume {
     std::vector<double *> pool;            // every device buffer, for destroy
     // fields
     double *Y[NSP], *Y0[NSP], *T, *hs, *hs0, *U[3], *U0[3], *p, *p0, *p_rgh, *p_rgh0, *psi, *psi0, *rho, *rho0, *K, *K0, *dpdt;
-    double *phi, *phi0, *phib, *phib0, *gh, *ghf, *ph_rgh, *ph_rgh_b;
+    double *phi, *phib, *gh, *ghf, *ph_rgh, *ph_rgh_b;      // (phi's old-time value is read from phi itself: p_corrector)
     // boundary-condition data [B]
     double *kind_d;                        // patch kind per boundary face (as double for simple kernels)
     double *fU[3], *refU[3], *fS, *refS, *fP, *refP, *gradP, *zeroB, *oneB;
@@ -257,6 +257,11 @@ static int bc_p_rgh(ffm_plume *P, const double *grad /*[B] or null*/, double *Ub
 
 static int rho_eqn(ffm_plume *P)
 {   // fvm::ddt(rho) + fvc::div(phi) == 0  -> diagonal: rho = (rdt*rho0*V - V*div(phi))/(rdt*V)
+    if (P->fused) {
+        const int rc = ffm_fvc_rho_eqn(P->mesh, P->rdt, P->phi, P->phib, P->rho0, P->rho);
+        if (rc == FFM_OK) return HX(P, P->rho);
+        if (rc != FFM_ERR_UNSUPPORTED) return rc;           // (rows too wide for the one-pass form: the two passes below)
+    }
     double *div = P->wN[0];
     FFM_TRY(ffm_fvc_surface_integrate(P->mesh, P->phi, P->phib, div));
     const double *V = ffm_mesh_geom(P->mesh, 0), *rho0 = P->rho0; double *rho = P->rho; const double rdt = P->rdt;
@@ -427,11 +432,11 @@ static int p_corrector(ffm_plume *P, bool final)
     const double *Sx = ffm_mesh_geom(m, 9), *Sy = ffm_mesh_geom(m, 10), *Sz = ffm_mesh_geom(m, 11), *wlin = ffm_mesh_geom(m, 3);
     double *rho = P->rho; const double *psi = P->psi; double *p = P->p;
     double *rAU = P->wN[0], *rhorAU = P->wN[1], *HbyA[3] = {P->wN[2], P->wN[3], P->wN[4]};
-    FFM_TRY(ffm_fvm_A(m, 3, P->Udiag, P->Uic[0], P->Uic[1], P->Uic[2], rAU));
     if (P->fused && P->N == P->nOwn) {
-        // rho = thermo.rho(); rAU = 1/A; rhorAU = rho*rAU in one pass (single block: no ghost refresh in between)
-        forN(P, N, [=] __device__(long i) { const double r = psi[i] * p[i], a = 1.0 / rAU[i]; rho[i] = r; rAU[i] = a; rhorAU[i] = r * a; });
+        // rho = thermo.rho(); rAU = 1/A; rhorAU = rho*rAU inside the pass of UEqn.A() (single block: no ghost refresh in between)
+        FFM_TRY(ffm_fvm_rAU(m, 3, P->Udiag, P->Uic[0], P->Uic[1], P->Uic[2], psi, p, rho, rAU, rhorAU));
     } else {
+    FFM_TRY(ffm_fvm_A(m, 3, P->Udiag, P->Uic[0], P->Uic[1], P->Uic[2], rAU));
     mul(P, rho, psi, p, N);                                                        // rho = thermo.rho()
     forN(P, P->nOwn, [=] __device__(long i) { rAU[i] = 1.0 / rAU[i]; });
     FFM_TRY(HX(P, rAU));
@@ -486,19 +491,20 @@ static int p_corrector(ffm_plume *P, bool final)
     {
         double *dc = P->ddtCorrF;
         if (!P->ddtCorrValid) {         // old-time fields only: evaluated in the first corrector of a step, reused by the second
-            double *fl0 = P->wF[4];
-            if (P->fused) FFM_TRY(ffm_fvc_flux_rho(m, P->rho0, P->U0[0], P->U0[1], P->U0[2], fl0));
+            // phi still holds the old-time flux here: this corrector overwrites it further down (ffm_pc_flux), the second one reuses dc
+            const double *phi0 = P->phi;
+            if (P->fused) FFM_TRY(ffm_fvc_ddt_corr(m, rdt, P->rho0, P->U0[0], P->U0[1], P->U0[2], phi0, dc));
             else {
+                double *fl0 = P->wF[4];
                 double *rU0[3] = {P->wN[8], P->wN[9], P->wN[10]};
                 for (int c = 0; c < 3; c++) mul(P, rU0[c], P->rho0, P->U0[c], N);
                 FFM_TRY(ffm_fvc_flux(m, rU0[0], rU0[1], rU0[2], fl0));
+                forN(P, nNat, [=] __device__(long e) {
+                    const double phiCorr = phi0[e] - fl0[e];
+                    const double coeff = 1.0 - fmin(fabs(phiCorr) / (fabs(phi0[e]) + 1e-15), 1.0);
+                    dc[e] = coeff * rdt * phiCorr;
+                });
             }
-            const double *phi0 = P->phi0;
-            forN(P, nNat, [=] __device__(long e) {
-                const double phiCorr = phi0[e] - fl0[e];
-                const double coeff = 1.0 - fmin(fabs(phiCorr) / (fabs(phi0[e]) + 1e-15), 1.0);
-                dc[e] = coeff * rdt * phiCorr;
-            });
             P->ddtCorrValid = true;
         }
         if (P->fused) FFM_TRY(ffm_pc_phiHbyA(m, rho, HbyA[0], HbyA[1], HbyA[2], rhorAUf, dc, phig, phiHbyA));
@@ -587,10 +593,13 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     P->log.clear();
     P->ddtCorrValid = false;
     // oldTime fields
-    dcopy(P, P->rho0, P->rho, N); dcopy(P, P->hs0, P->hs, N); dcopy(P, P->K0, P->K, N); dcopy(P, P->p0, P->p, N);
-    dcopy(P, P->psi0, P->psi, N); dcopy(P, P->p_rgh0, P->p_rgh, N); dcopy(P, P->phi0, P->phi, nNat); dcopy(P, P->phib0, P->phib, B);
+    // rho, K and psi are rewritten in full before their first read (rho by rhoEqn just below, K after the momentum solve, psi by the
+    // thermo update after EEqn): the old-time field takes the buffer, no copy.  Every kernel gets its pointers from P at launch.
+    // phi's old-time value is read where phi still holds it (ddtCorr, first corrector), and nothing reads the inert specie's.
+    std::swap(P->rho0, P->rho); std::swap(P->K0, P->K); std::swap(P->psi0, P->psi);
+    dcopy(P, P->hs0, P->hs, N); dcopy(P, P->p0, P->p, N); dcopy(P, P->p_rgh0, P->p_rgh, N);
     for (int c = 0; c < 3; c++) dcopy(P, P->U0[c], P->U[c], N);
-    for (int i = 0; i < NSP; i++) dcopy(P, P->Y0[i], P->Y[i], N);
+    for (int i = 0; i < NSP; i++) if (i != INERT) dcopy(P, P->Y0[i], P->Y[i], N);
     FFM_TRY(rho_eqn(P));
     // ---------------- UEqn.H
     FFM_TRY(update_bcs(P));
@@ -665,7 +674,8 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     double *wFuel = P->wN[8], *Qdot = P->wN[9], *Yt = P->wN[10], *su = P->wN[11];
     {
         const double *rho = P->rho, *fuel = P->Y[2], *o2 = P->Y[0];
-        forN(P, N, [=] __device__(long i) { const double w = rho[i] * fmin(fuel[i], o2[i] / S_O2) / TAU; wFuel[i] = w; Qdot[i] = w * HC; Yt[i] = 0.0; });
+        if (P->fused) forN(P, N, [=] __device__(long i) { const double w = rho[i] * fmin(fuel[i], o2[i] / S_O2) / TAU; wFuel[i] = w; Qdot[i] = w * HC; });
+        else forN(P, N, [=] __device__(long i) { const double w = rho[i] * fmin(fuel[i], o2[i] / S_O2) / TAU; wFuel[i] = w; Qdot[i] = w * HC; Yt[i] = 0.0; });
     }
     if (P->mvSelection && P->mvOverride) P->mvOverride = false;      // weights of this step were handed in: wMv stays as uploaded
     else if (P->mvSelection) {
@@ -723,10 +733,12 @@ extern "C" int ffm_plume_step(ffm_plume *P)
         int sp[NSP - 1], ns = 0;
         for (int i = 0; i < NSP; i++) if (i != INERT) sp[ns++] = i;
         const double *vf[4], *vb[4], *vf0[4], *fq[4], *rq[4], *gq[4], *suq[4], *cgx[4], *cgy[4], *cgz[4];
-        double *ggx[4], *ggy[4], *ggz[4];
+        double *ggx[4], *ggy[4], *ggz[4], nuq[4];
         for (int j = 0; j < ns; j++) {
-            const int i = sp[j]; const double nu = NU[i]; double *sj = P->suM[j];
-            forN(P, N, [=] __device__(long c) { sj[c] = nu * wFuel[c]; });
+            const int i = sp[j]; const double nu = NU[i]; const double *sj = wFuel;
+            // common weights: the assembly pass forms nu_i*wFuel itself; one limiter per field: the product field, as before
+            if (!P->mvSelection) { double *sm = P->suM[j]; forN(P, N, [=] __device__(long c) { sm[c] = nu * wFuel[c]; }); sj = sm; }
+            nuq[j] = nu;
             if (!P->mvSelection) FFM_TRY(ffm_bc_values(m, P->fS, P->refY[i], P->zeroB, P->Y[i], P->spB[j]));
             vf[j] = P->Y[i]; vb[j] = P->spB[j]; vf0[j] = P->Y0[i]; fq[j] = P->fS; rq[j] = P->refY[i]; gq[j] = P->zeroB; suq[j] = sj;
             ggx[j] = P->gM[j][0]; ggy[j] = P->gM[j][1]; ggz[j] = P->gM[j][2]; cgx[j] = ggx[j]; cgy[j] = ggy[j]; cgz[j] = ggz[j];
@@ -735,8 +747,8 @@ extern "C" int ffm_plume_step(ffm_plume *P)
         // differ, through the patch conditions and the sources): written once, gathered into the sweeps' layout once
         double *uShared[4] = {P->spU[0], nullptr, nullptr, nullptr}, *lShared[4] = {P->spL[0], nullptr, nullptr, nullptr};
         if (P->mvSelection)
-            FFM_TRY(ffm_fvm_scalar_transport_multi_w(m, ns, P->wMv, rdt, P->rho, P->rho0, P->phi, P->phib, af, afb, vf0, fq, rq, gq, suq, nullptr, nullptr,
-                                                     nullptr, P->spD, uShared, lShared, P->spS));
+            FFM_TRY(ffm_fvm_scalar_transport_multi_ws(m, ns, P->wMv, rdt, P->rho, P->rho0, P->phi, P->phib, af, afb, vf0, fq, rq, gq, suq, nuq, nullptr,
+                                                      nullptr, nullptr, P->spD, uShared, lShared, P->spS));
         else {
         FFM_TRY(ffm_fvc_grad_multi(m, ns, vf, vb, ggx, ggy, ggz));
         for (int j = 0; j < ns; j++) { FFM_TRY(HX(P, ggx[j])); FFM_TRY(HX(P, ggy[j])); FFM_TRY(HX(P, ggz[j])); }
@@ -752,8 +764,15 @@ extern "C" int ffm_plume_step(ffm_plume *P)
             const int i = sp[j];
             if (!P->mvSelection) FFM_TRY(solve_named(P, SPN[i], FFM_PBICGSTAB, FFM_DILU, 1e-8, 0.0, P->spD[j], P->spU[j], P->spL[j], P->Y[i], P->spS[j]));
             FFM_TRY(HX(P, P->Y[i]));
-            double *Yi = P->Y[i];
-            forN(P, N, [=] __device__(long c) { const double v = fmax(Yi[c], 0.0); Yi[c] = v; Yt[c] += v; });
+        }
+        {   // Yi.max(0), Yt = sum Yi in the species' order starting from zero, Y[inertIndex] = max(1 - Yt, 0): one pass (solver/YEEqn.H:60-66)
+            double *y0 = P->Y[sp[0]], *y1 = P->Y[sp[1]], *y2 = P->Y[sp[2]], *y3 = P->Y[sp[3]], *Yn = P->Y[INERT];
+            forN(P, N, [=] __device__(long c) {
+                const double a = fmax(y0[c], 0.0), b = fmax(y1[c], 0.0), d = fmax(y2[c], 0.0), e = fmax(y3[c], 0.0);
+                y0[c] = a; y1[c] = b; y2[c] = d; y3[c] = e;
+                const double t = (((0.0 + a) + b) + d) + e;
+                Yn[c] = fmax(1.0 - t, 0.0);
+            });
         }
     } else
     for (int i = 0; i < NSP; i++) {
@@ -764,7 +783,7 @@ extern "C" int ffm_plume_step(ffm_plume *P)
         double *Yi = P->Y[i];
         forN(P, N, [=] __device__(long c) { const double v = fmax(Yi[c], 0.0); Yi[c] = v; Yt[c] += v; });
     }
-    {
+    if (!P->fused) {
         double *Yn = P->Y[INERT];
         forN(P, N, [=] __device__(long c) { Yn[c] = fmax(1.0 - Yt[c], 0.0); });
     }
@@ -778,15 +797,23 @@ extern "C" int ffm_plume_step(ffm_plume *P)
         forN(P, B, [=] __device__(long k) { Kb[k] = 0.5 * ((b0[k] * b0[k] + b1[k] * b1[k]) + b2[k] * b2[k]); });
         FFM_TRY(ffm_fvc_grad(m, P->K, Kb, kgx, kgy, kgz));
         FFM_TRY(HX(P, kgx)); FFM_TRY(HX(P, kgy)); FFM_TRY(HX(P, kgz));
+        double *divK = P->wN[4], *ddtK = P->wN[0], *ndpdt = P->wN[5];
+        int rcK = FFM_ERR_UNSUPPORTED;
+        if (P->fused) {
+            // limitedLinear weights, interpolate(K), *phi, surfaceIntegrate and the two cell terms in one cell-centred pass: no wK, no Kf
+            rcK = ffm_fvc_div_phiK_terms(m, 2, 1.0, 0.0, 1.0, rdt, P->phi, P->phib, P->K, Kb, kgx, kgy, kgz, P->rho, P->rho0, P->K0, P->dpdt, divK, ddtK, ndpdt);
+            if (rcK != FFM_OK && rcK != FFM_ERR_UNSUPPORTED) return rcK;
+        }
+        if (rcK != FFM_OK) {
         FFM_TRY(ffm_fv_limited_weights(m, 2, 1.0, 0.0, 1.0, P->phi, P->K, kgx, kgy, kgz, wK));
         FFM_TRY(ffm_fvc_interpolate(m, wK, P->K, Kf));
         const double *phi = P->phi, *phib = P->phib;
         forN(P, nNat, [=] __device__(long e) { Kf[e] = phi[e] * Kf[e]; });
         forN(P, B, [=] __device__(long k) { KfB[k] = phib[k] * Kb[k]; });
-        double *divK = P->wN[4];
         FFM_TRY(ffm_fvc_surface_integrate(m, Kf, KfB, divK));
-        double *ddtK = P->wN[0], *ndpdt = P->wN[5]; const double *rho = P->rho, *rho0 = P->rho0, *K = P->K, *K0 = P->K0, *dpdt = P->dpdt;
+        const double *rho = P->rho, *rho0 = P->rho0, *K = P->K, *K0 = P->K0, *dpdt = P->dpdt;
         forN(P, N, [=] __device__(long c) { ddtK[c] = rdt * (rho[c] * K[c] - rho0[c] * K0[c]); ndpdt[c] = -dpdt[c]; });
+        }
         const double *expl[3] = {ddtK, divK, ndpdt};       // fvc::ddt(rho,K) + fvc::div(phi,K) + (-dpdt), solver/YEEqn.H:89-101
         // + radiation->Sh(thermo, he) = Ru - fvm::Sp(4 Rp T^3/Cpv, he) - Rp T^3 (T - 4 he/Cpv), Rp = 4 a sigma, Ru = a G - E
         // (radiationModel.C:229-244, fvDOM.C Rp / Ru), E of the current Qdot
@@ -994,12 +1021,12 @@ extern "C" int ffm_plume_create_block(ffm_ctx *ctx, int gx, int gy, int gz, cons
     const int B = Btot; const long nNat = P->nNat;
     // ---- fields
     auto NN = [&]() { return dalloc(P, N); };
-    for (int i = 0; i < NSP; i++) { P->Y[i] = dfill(P, N, Y_AMB[i]); P->Y0[i] = NN(); }
+    for (int i = 0; i < NSP; i++) { P->Y[i] = dfill(P, N, Y_AMB[i]); P->Y0[i] = i == INERT ? nullptr : NN(); }      // nothing reads the inert specie's old time
     P->T = dfill(P, N, TREF); P->hs = NN(); P->hs0 = NN();
     for (int c = 0; c < 3; c++) { P->U[c] = NN(); P->U0[c] = NN(); }
     P->p = dfill(P, N, PREF); P->p0 = NN(); P->p_rgh = NN(); P->p_rgh0 = NN(); P->psi = NN(); P->psi0 = NN();
     P->rho = NN(); P->rho0 = NN(); P->K = NN(); P->K0 = NN(); P->dpdt = NN(); P->ph_rgh = NN();
-    P->phi = dalloc(P, nNat); P->phi0 = dalloc(P, nNat); P->phib = dalloc(P, B); P->phib0 = dalloc(P, B); P->ph_rgh_b = dalloc(P, B);
+    P->phi = dalloc(P, nNat); P->phib = dalloc(P, B); P->ph_rgh_b = dalloc(P, B);
     {
         const double ghRef = -9.81 * (ny_glob * h);
         std::vector<double> gh(N), ghf(std::max<long>(nNat, 1), 0.0);
@@ -1149,14 +1176,21 @@ extern "C" int ffm_plume_set_radiation_model(ffm_plume *P, double absorption, do
 }
 // Start state and boundary values other than the quiescent ambient / pure-fuel inflow (tests: a state in which no transported
 // field is uniform, tests/test_plume_gpu.py).  Y[5], h: cell fields in natural blockMesh order of the (single) block; Yamb / Yin:
-// the inletOutlet and inlet values of the species, hAmb the inletOutlet value of h.  Only before the first step: the hydrostatic
-// initialisation (solver/phrghEqn.H) is redone from the new state.
+// the inletOutlet and inlet values of the species, hAmb the inletOutlet value of h.  The hydrostatic initialisation
+// (solver/phrghEqn.H) is redone from the new state; after steps have been taken the case starts again from it (time 0).
 extern "C" int ffm_plume_set_initial_state(ffm_plume *P, const double *const *Y, const double *h, const double *Yamb, const double *Yin, double hAmb)
 {
     if (!P || !Y || !h || !Yamb || !Yin) return FFM_ERR_ARG;
-    if (P->stepNo != 0 || P->N != P->nOwn) { ffm_set_error("plume: the start state can be set on a single block before the first step only"); return FFM_ERR_ARG; }
+    if (P->N != P->nOwn) { ffm_set_error("plume: the start state can be set on a single block only"); return FFM_ERR_ARG; }
     PL_HIP(hipSetDevice(P->ctx->device));
     const int N = P->N, B = P->B;
+    if (P->stepNo != 0) {       // restart: what the steps have changed and the start state does not set goes back to its value at creation
+        PL_HIP(hipStreamSynchronize(P->ctx->stream));
+        for (int c = 0; c < 3; c++) FFM_TRY(ffm_dzero(P->ctx, P->U[c], sizeof(double) * N));
+        FFM_TRY(ffm_dzero(P->ctx, P->K, sizeof(double) * N)); FFM_TRY(ffm_dzero(P->ctx, P->dpdt, sizeof(double) * N));
+        FFM_TRY(ffm_dzero(P->ctx, P->phi, sizeof(double) * std::max<long>(P->nNat, 1))); FFM_TRY(ffm_dzero(P->ctx, P->phib, sizeof(double) * std::max(B, 1)));
+        P->stepNo = 0; P->time = 0.0; P->radHaveG = false; P->mvOverride = false; P->ddtCorrValid = false;
+    }
     std::vector<double> v(N);
     auto up = [&](double *dst, const double *nat) -> int {
         for (int c = 0; c < N; c++) v[c] = nat[P->newToOld[c]];
@@ -1242,6 +1276,11 @@ extern "C" long ffm_plume_get_raw(ffm_plume *P, const char *name, double *out, l
     if (n == "K") return cellF(P->K); if (n == "dpdt") return cellF(P->dpdt); if (n == "gh") return cellF(P->gh); if (n == "T") return cellF(P->T);
     if (n == "Ux") return cellF(P->U[0]); if (n == "Uy") return cellF(P->U[1]); if (n == "Uz") return cellF(P->U[2]);
     for (int i = 0; i < NSP; i++) if (n == SPN[i]) return cellF(P->Y[i]);
+    // old-time fields as the last step left them (rho0, K0 and psi0 trade buffers with rho, K and psi at every step)
+    if (n == "rho0") return cellF(P->rho0); if (n == "K0") return cellF(P->K0); if (n == "psi0") return cellF(P->psi0); if (n == "psi") return cellF(P->psi);
+    if (n == "h0") return cellF(P->hs0); if (n == "p0") return cellF(P->p0); if (n == "p_rgh0") return cellF(P->p_rgh0);
+    for (int c = 0; c < 3; c++) if (n == std::string("U0") + char('x' + c)) return cellF(P->U0[c]);
+    for (int i = 0; i < NSP; i++) if (i != INERT && n == std::string(SPN[i]) + "_0") return cellF(P->Y0[i]);
     if (n == "phi") return faceF(P->phi); if (n == "ghf") return faceF(P->ghf);
     if (n == "phib") return bndF(P->phib); if (n == "ph_rgh_b") return bndF(P->ph_rgh_b); if (n == "kind") return bndF(P->kind_d);
     if (n == "fStaticS") return bndF(P->fStaticS); if (n == "fStaticH") return bndF(P->fStaticH); if (n == "refH") return bndF(P->refH);

@@ -407,6 +407,24 @@ int ffm_ue_buoyancy_flux(ffm_mesh *m, const double *ghf, const double *rho, cons
 /* fvc::flux(rho*v) on the internal faces (solver/pEqn.H:15 fvc::flux(rho*HbyA); the old-time flux of fvc::ddtCorr) without
  * storing the product fields; bitwise equal to ffm_fvc_flux of the products */
 int ffm_fvc_flux_rho(ffm_mesh *m, const double *rho, const double *vx, const double *vy, const double *vz, double *out_f);
+/* fvc::ddtCorr(rho, U, phi) of solver/pEqn.H:13 on the internal faces in one pass: coeff*rDeltaT*(phi0 - fvc::flux(rho0*U0)) with
+ * ddtCouplingCoeff's coeff = 1 - min(|phi0 - flux|/(|phi0| + SMALL), 1); bitwise equal to ffm_fvc_flux_rho + that face algebra */
+int ffm_fvc_ddt_corr(ffm_mesh *m, double rDeltaT, const double *rho0, const double *vx0, const double *vy0, const double *vz0,
+                     const double *phi0_f, double *out_f);
+/* solver/pEqn.H:1-3 on a single block: rho = psi*p, rAU = 1/UEqn.A(), rhorAU = rho*rAU in the pass of ffm_fvm_A */
+int ffm_fvm_rAU(ffm_mesh *m, int nCmpt, const double *diag, const double *ic0, const double *ic1, const double *ic2,
+                const double *psi, const double *p, double *rho, double *rAU, double *rhorAU);
+/* solver/rhoEqn.H: fvm::ddt(rho) + fvc::div(phi) == 0 solved on the owned cells, rho = (rDeltaT*rho0*V - V*div(phi))/(rDeltaT*V);
+ * bitwise equal to ffm_fvc_surface_integrate + that cell algebra.  rho and rho0 are different arrays. */
+int ffm_fvc_rho_eqn(ffm_mesh *m, double rDeltaT, const double *phi_f, const double *phi_b, const double *rho0, double *rho);
+/* the explicit terms of EEqn (solver/YEEqn.H:89-101) on the owned cells in one pass: divK = fvc::div(phi, K) [scheme 2 limitedLinear k |
+ * 3 limitedLinear01 k in [lo,hi]; gx, gy, gz = fvc::grad(K)], ddtK = rDeltaT*(rho*K - rho0*K0), negDpdt = -dpdt.  Bitwise equal to
+ * ffm_fv_limited_weights + ffm_fvc_interpolate + the product with phi + ffm_fvc_surface_integrate + the cell algebra.
+ * FFM_ERR_UNSUPPORTED, nothing launched, on meshes with more than 8 lower or upper neighbours per cell (ffm_fvc_rho_eqn: 16). */
+int ffm_fvc_div_phiK_terms(ffm_mesh *m, int scheme, double k, double lo, double hi, double rDeltaT, const double *phi_f,
+                           const double *phi_b, const double *K, const double *K_b, const double *gx, const double *gy,
+                           const double *gz, const double *rho, const double *rho0, const double *K0, const double *dpdt,
+                           double *divK, double *ddtK, double *negDpdt);
 int ffm_fvm_flux(ffm_mesh *m, const double *upper, const double *lower, const double *internalCoeffs,
                  const double *boundaryCoeffs, const double *psi, double *out_f, double *out_b);
 
@@ -442,6 +460,14 @@ int ffm_fvm_scalar_transport_multi_w(ffm_mesh *m, int nf, const double *w_f, dou
                                      const double *const *refGrad, const double *const *su, const double *const *su2,
                                      const double *const *sp, const double *const *expl3, double *const *diag,
                                      double *const *upper, double *const *lower, double *const *source);
+/* ffm_fvm_scalar_transport_multi_w with the explicit source of field i given as suFactor[i]*su[i] (suFactor: HOST array of nf factors,
+ * NULL: 1): the species of solver/YEEqn.H:37-67 share one reaction rate; bitwise equal to handing in the products */
+int ffm_fvm_scalar_transport_multi_ws(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
+                                      const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
+                                      const double *const *vf0, const double *const *f, const double *const *ref,
+                                      const double *const *refGrad, const double *const *su, const double *suFactor,
+                                      const double *const *su2, const double *const *sp, const double *const *expl3,
+                                      double *const *diag, double *const *upper, double *const *lower, double *const *source);
 /* momentum source of solver/UEqn.H:5 with `div(phi,U) Gauss LUST grad(U)`: source_c = rDeltaT*rho0*U0_c*V
  * - V*fvc::surfaceIntegrate(phi*LUST::correction(U_c)) for the three components from their gradients                  */
 int ffm_fvm_lust_source3(ffm_mesh *m, double rDeltaT, const double *phi_f, const double *rho0, const double *const *U0,
@@ -495,7 +521,7 @@ int ffm_plume_set_radiation(ffm_plume *plume, int solverFreq, int nPhi, int nThe
 int ffm_plume_set_radiation_model(ffm_plume *plume, double absorption, double Ehrr1, double Ehrr2);
 /* tests: a start state and boundary values other than the quiescent ambient / pure-fuel inflow -- Y[5] and h as cell fields in
  * natural blockMesh order, Yamb / Yin the inletOutlet and inlet values of the species, hAmb the inletOutlet value of h; redoes
- * the hydrostatic initialisation (solver/phrghEqn.H).  Single block, before the first step.                                   */
+ * the hydrostatic initialisation (solver/phrghEqn.H).  Single block; after steps, a restart from time 0.                                  */
 int ffm_plume_set_initial_state(ffm_plume *plume, const double *const *Y, const double *h, const double *Yamb, const double *Yin, double hAmb);
 /* tests: the next step convects the species and h with the face weights w[F] (natural face order) instead of evaluating the
  * multivariateSelection limiter of solver/YEEqn.H:1-10 -- separates the limiter's conditioning from everything else in a step */
