@@ -250,6 +250,10 @@ def lib():
         "ffm_plume_set_solvers": ([vp, C.c_int], C.c_int),
         "ffm_plume_set_radiation": ([vp, C.c_int, C.c_int, C.c_int, vp, vp], C.c_int),
         "ffm_plume_set_radiation_model": ([vp, C.c_double, C.c_double, C.c_double], C.c_int),
+        "ffm_plume_set_radiation_ordering": ([vp, C.c_int], C.c_int),
+        "ffm_plume_ray_system": ([vp, C.c_int, C.c_int, hp, hp, hp, hp], C.c_int),
+        "ffm_ray_schedule": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, hp, ip, C.c_int], C.c_int),
+        "ffm_ray_octant": ([hp], C.c_int),
         "ffm_plume_set_initial_state": ([vp, C.POINTER(C.c_void_p), hp, hp, hp, C.c_double], C.c_int),
         "ffm_plume_override_mv_weights": ([vp, hp], C.c_int),
         "ffm_plume_ncells": ([vp], C.c_int),
@@ -294,6 +298,22 @@ def _ip(a):
 
 def _hp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def ray_octant(d):
+    """octant index of a ray direction (ffm_ray_octant): bit a set where component a is negative"""
+    return lib().ffm_ray_octant(_hp(np.ascontiguousarray(d, dtype=np.float64)))
+
+
+def ray_schedule(grid, block, dAve):
+    """(tickRay, nTicks) of the staged ray sweep for one block of a box of blocks (ffm_ray_schedule; host code, no GPU)"""
+    d = np.ascontiguousarray(dAve, dtype=np.float64).reshape(-1, 3)
+    args = [int(v) for v in (*grid, *block)]
+    n = lib().ffm_ray_schedule(*args, len(d), _hp(d), None, 0)
+    _check(min(n, 0), "ffm_ray_schedule")
+    ticks = np.full(max(n, 1), -1, dtype=np.int32)
+    _check(min(lib().ffm_ray_schedule(*args, len(d), _hp(d), _ip(ticks), n), 0), "ffm_ray_schedule")
+    return ticks[:n], n
 
 
 def tile_hint_from_centres(C_, tileCells=0):
@@ -738,6 +758,18 @@ class Plume:
     def set_radiation_model(self, absorption, Ehrr1, Ehrr2):
         """the reference's absorption / emission model and radiation->Sh in the enthalpy equation (ffm_plume_set_radiation_model)"""
         _check(lib().ffm_plume_set_radiation_model(self.h, float(absorption), float(Ehrr1), float(Ehrr2)), "ffm_plume_set_radiation_model")
+
+    def set_radiation_ordering(self, mode):
+        """0: every ray a PBiCGStab solve over all ranks; 1: the staged direction-ordered sweep over the blocks of a decomposed box
+        (ffm_plume_set_radiation_ordering)"""
+        _check(lib().ffm_plume_set_radiation_ordering(self.h, int(mode)), "ffm_plume_set_radiation_ordering")
+
+    def ray_system(self, ray, fused):
+        """(diag, upper, lower, source) of one ray's system by the operator chain or by the one-pass kernel (ffm_plume_ray_system; tests)"""
+        d, s_ = np.empty(self.nCells), np.empty(self.nCells)
+        u, l = np.empty(self.nFaces), np.empty(self.nFaces)
+        _check(lib().ffm_plume_ray_system(self.h, int(ray), 1 if fused else 0, _hp(d), _hp(u), _hp(l), _hp(s_)), "ffm_plume_ray_system")
+        return d, u, l, s_
 
     def set_initial_state(self, Y, h, Yamb, Yin, hAmb):
         """start state (Y[5][N], h[N] in natural cell order) and the species' / enthalpy's ambient and inflow values; redoes the

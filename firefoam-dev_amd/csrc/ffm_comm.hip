@@ -367,16 +367,19 @@ int ffm_ghost_exchange_end(ffm_ldu *A)
     return FFM_OK;
 }
 
-int ffm_ghost_exchange(ffm_ldu *A, double *x)
+// One ghost refresh with the two ends apart: every neighbour gets this rank's send cells of `sendFrom`, and what the neighbours
+// send lands in ghostInto[0 .. nGhost), ghost layer after ghost layer.  ffm_ghost_exchange(x) is the case sendFrom = x,
+// ghostInto = x + nOwned; the ticks of the staged ray sweep send one ray and receive others.
+int ffm_ghost_exchange_split(ffm_ldu *A, const double *sendFrom, double *ghostInto)
 {
     ffm_ctx *c = A->ctx;
     const int nNbr = (int)A->ghNbrRank.size();
     if (!nNbr) return FFM_OK;
     const int nSend = A->ghSendOff[nNbr], nRecv = A->ghRecvOff[nNbr];
     if (nSend) hipLaunchKernelGGL(k_halo_pack, dim3(std::max(1, std::min(ffm_grid(nSend, 256), 1024))), dim3(256), 0, c->stream,
-                                  nSend, A->ghSendCells, x, A->ghSendBuf);
+                                  nSend, A->ghSendCells, sendFrom, A->ghSendBuf);
     FFM_HIP(hipGetLastError());
-    double *ghost = x + A->nOwned;
+    double *ghost = ghostInto;
     if (c->comm) return ghost_group(A, ghost, c->stream);
     if (!c->hostExchange2) { ffm_set_error("ghost cells set but no communicator attached"); return FFM_ERR_COMM; }
     FFM_HIP(hipMemcpyAsync(A->ghSendBuf_h, A->ghSendBuf, sizeof(double) * nSend, hipMemcpyDeviceToHost, c->stream));
@@ -385,6 +388,8 @@ int ffm_ghost_exchange(ffm_ldu *A, double *x)
     FFM_HIP(hipMemcpyAsync(ghost, A->ghRecvBuf_h, sizeof(double) * nRecv, hipMemcpyHostToDevice, c->stream));
     return FFM_OK;
 }
+
+int ffm_ghost_exchange(ffm_ldu *A, double *x) { return ffm_ghost_exchange_split(A, x, x + A->nOwned); }
 
 extern "C" int ffm_halo_refresh_d(ffm_ldu *A, double *field_d)
 {

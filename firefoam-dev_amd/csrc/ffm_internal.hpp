@@ -279,6 +279,8 @@ int ffm_k_spmv(ffm_ldu *A, const double *x, double *y, bool transpose);
 int ffm_k_spmv_dot(ffm_ldu *A, const double *x, double *y, int slot);  // y=Ax, scal[slot]=x.y (local)
 int ffm_k_residual(ffm_ldu *A, const double *x, const double *b, double *r);
 int ffm_k_sumA(ffm_ldu *A, double *s);
+int ffm_k_spmv_sumA_rows(ffm_ldu *A, const double *x, double *y, double *s);   // this rank's rows, no ghost refresh
+int ffm_k_residual_rows(ffm_ldu *A, const double *x, const double *b, double *r);
 int ffm_k_spmv_sumA(ffm_ldu *A, const double *x, double *y, double *s);
 int ffm_halo_update(ffm_ldu *A, const double *x, double *y, const double *coeffs, double sign);  // exchange + apply
 int ffm_halo_apply(ffm_ldu *A, double *y, const double *coeffs, const double *vals /*null => 1*/, double sign);
@@ -294,6 +296,7 @@ int ffm_sweep_check_abort(ffm_ldu *A);                   // abort word of the ti
 int ffm_tile_gs_ghost_terms(ffm_ldu *A, const double *psi, double *bP);
 int ffm_ghost_exchange(ffm_ldu *A, double *x);
 int ffm_ghost_exchange_begin(ffm_ldu *A, double *x);     // starts the refresh of x[nOwned..nCells); may return with it in flight
+int ffm_ghost_exchange_split(ffm_ldu *A, const double *sendFrom, double *ghostInto);   // the same exchange: owned cells of one field out, the ghost layers [nGhost] of another in
 int ffm_ghost_exchange_end(ffm_ldu *A);                  // the main stream waits for it
 int ffm_tile_gs(ffm_ldu *A, bool sym, double *psi, const double *bP, double *bSave, double *prod3);
 bool ffm_tile_amul_usable(const ffm_ldu *A);

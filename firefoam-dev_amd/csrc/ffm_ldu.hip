@@ -1082,6 +1082,23 @@ int ffm_k_spmv_sumA(ffm_ldu *A, const double *x, double *y, double *s)
     return FFM_OK;
 }
 
+// The row kernels over this rank's rows as they stand: no ghost refresh, so no rank waits for another.  For a matrix whose faces
+// towards ghost cells carry zero coefficients (the staged fvDOM ray solves: their terms have been moved into the source).
+int ffm_k_spmv_sumA_rows(ffm_ldu *A, const double *x, double *y, double *s)
+{
+    FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_rows<3, false, W>), dim3(rows_grid(A)), dim3(256), 0, A->ctx->stream, ffm_view(A),
+                                               A->diag, A->upper, A->lower, x, (const double *)nullptr, y, s));
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+int ffm_k_residual_rows(ffm_ldu *A, const double *x, const double *b, double *r)
+{
+    FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_rows<1, false, W>), dim3(rows_grid(A)), dim3(256), 0, A->ctx->stream, ffm_view(A),
+                                               A->diag, A->upper, A->lower, x, b, r, (double *)nullptr));
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
 int ffm_k_sumA(ffm_ldu *A, double *s)
 {
     FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_rows<2, false, W>), dim3(rows_grid(A)), dim3(256), 0, A->ctx->stream, ffm_view(A),

@@ -61,3 +61,96 @@ extern "C" int ffm_fvdom_sum_rays_d(ffm_mesh *m, int nRay, const double *all, do
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
+
+// ------------------------------------------------------------------ one ray's system in one pass ---
+// The equation of one fvDOM ray (radiativeIntensityRay.C:267-322 with `div(Ji,Ii_h) Gauss upwind`),
+//   fvm::div(Ji, Ii) + fvm::Sp(k omega, Ii) == omega/pi (k sigma T^4 [+ E/4]),  Ji = dAve & Sf,
+// inflow boundary faces at ref_b, outflow zero-gradient, as the solver takes it: what the per-operator chain
+//   Ji, w (faces) | Jb, f (boundary) | ffm_fvm_transport | ffm_fvm_boundary_coeffs | diag += V k omega, source | ffm_fvm_add_boundary
+// leaves in upper / lower / diag / source, every term rounded as there (so the coefficients are those of the chain bit for
+// bit), from one walk over the rows: a row forms Ji of its own faces in registers, the owner writes the face coefficients.
+template <int W>
+__global__ void k_ray_assemble(MeshView q, double d0, double d1, double d2, double kO, double cS, double kS,
+                               const double *__restrict__ T, const double *__restrict__ E, const double *__restrict__ refB,
+                               const double *__restrict__ bDelta, double *__restrict__ Jf, double *__restrict__ wf,
+                               double *__restrict__ upper, double *__restrict__ lower, double *__restrict__ diag,
+                               double *__restrict__ source)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci;
+        RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
+        double dDiv = 0.0;
+        // faces where c is the neighbour: diag -= upper[f]
+#pragma unroll
+        for (int s = 0; s < W; s++) if (L.on[s]) {
+            const int e = L.f[s];
+            const double j = (d0 * q.Sfx[e] + d1 * q.Sfy[e]) + d2 * q.Sfz[e];
+            const double w = j >= 0 ? 1.0 : 0.0, lo = -w * j;
+            dDiv -= (lo + j);
+        }
+        // faces owned by c: write coefficients, diag -= lower[f]
+#pragma unroll
+        for (int s = 0; s < W; s++) if (U.on[s]) {
+            const int e = U.f[s];
+            const double j = (d0 * q.Sfx[e] + d1 * q.Sfy[e]) + d2 * q.Sfz[e];
+            const double w = j >= 0 ? 1.0 : 0.0, lo = -w * j, up = lo + j;
+            dDiv -= lo;
+            upper[e] = up; lower[e] = lo;
+            if (Jf) Jf[e] = j;
+            if (wf) wf[e] = w;
+        }
+        const double Vc = q.V[c], t = T[c];
+        double d = dDiv + Vc * kO;
+        double s = E ? Vc * (cS * (kS * ((t * t) * (t * t)) + E[c] / 4.0)) : Vc * (cS * (kS * ((t * t) * (t * t))));
+        const int jb = q.cellB[c];
+        if (jb >= 0) for (int it = q.bcStart[jb]; it < q.bcStart[jb + 1]; it++) {
+            const int k = q.bcItem[it];
+            const double j = (d0 * q.bSfx[k] + d1 * q.bSfy[k]) + d2 * q.bSfz[k];
+            const double fk = 1.0 - (j >= 0 ? 1.0 : 0.0), rk = refB[k], gk = 0.0, dk = bDelta[k];
+            d += j * (1.0 - fk);                                             // internalCoeffs
+            s += -j * (fk * rk + (1.0 - fk) * gk / dk);                      // boundaryCoeffs
+        }
+        diag[c] = d; source[c] = s;
+    }
+}
+
+extern "C" int ffm_fvdom_ray_assemble_d(ffm_mesh *m, const double *dAve3, double omega, double absorption, double sigma, const double *T,
+                                        const double *E, const double *ref_b, double *J_f, double *w_f, double *upper, double *lower,
+                                        double *diag, double *source)
+{
+    if (!m || !dAve3 || !T || !upper || !lower || !diag || !source || (m->B && !ref_b)) return FFM_ERR_ARG;
+    const double kO = absorption * omega, cS = 1.0 / M_PI * omega, kS = absorption * sigma;
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_ray_assemble<W>, mview(m), dAve3[0], dAve3[1], dAve3[2], kO, cS, kS, T, E, ref_b, m->bDelta, J_f, w_f,
+                                            upper, lower, diag, source));
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// The upstream ghost inflow of a ray on one block of a decomposed mesh: a cut face is an upper face of its owned cell c towards
+// a ghost cell g, and upper[e] I_g is the term of row c that lies on the neighbour rank.  With I_g final (the neighbour is
+// upstream of this block and has solved the ray) the term moves to the right-hand side, source_c -= upper[e] I_g in the
+// row's face order, and the face leaves the matrix (both coefficients 0): what remains couples owned cells only.  On the
+// downstream cut faces upper[e] is already 0.  One thread per owned cell that has a cut face (cells[n]).
+__global__ void k_ray_fold_ghosts(MeshView q, int n, const int *__restrict__ cells, const double *__restrict__ I,
+                                  double *__restrict__ upper, double *__restrict__ lower, double *__restrict__ source)
+{
+    GRID_STRIDE(i, n) {
+        const int c = cells[i];
+        double s = source[c];
+        FOR_OWN_FACES(q, c, e, nb) if (nb >= q.v.N) {
+            s = s - upper[e] * I[nb];
+            upper[e] = 0.0; lower[e] = 0.0;
+        }
+        source[c] = s;
+    }
+}
+
+extern "C" int ffm_fvdom_fold_ghost_inflow_d(ffm_mesh *m, int nCells, const int *cells, const double *I, double *upper, double *lower,
+                                             double *source)
+{
+    if (!m || nCells < 0 || (nCells && (!cells || !I || !upper || !lower || !source))) return FFM_ERR_ARG;
+    if (nCells == 0) return FFM_OK;
+    LAUNCH(k_ray_fold_ghosts, nCells, mview(m), nCells, cells, I, upper, lower, source);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}

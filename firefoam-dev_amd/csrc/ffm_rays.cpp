@@ -1,0 +1,39 @@
+// ffm_rays.cpp -- the tick schedule of the direction-ordered fvDOM ray solves on a box of blocks (pure host code, no HIP).
+// For one ray direction the blocks of a box decomposition form a DAG: block b receives intensity from its face neighbour on
+// the upstream side of every axis.  All rays of an octant share that DAG, so they are pipelined through it: the block at
+// Manhattan distance s from the octant's upstream corner (its stage) solves the octant's r-th ray at tick r + s.  An octant
+// with r > 0 rays on a grid with S = (px - 1) + (py - 1) + (pz - 1) + 1 stages takes r + S - 1 ticks (an octant without rays:
+// none), and the octants follow one another in the order of their index.  Every rank computes the same tick count, so a
+// sweep that enters one exchange per tick cannot hang.
+#include "../../include/ffm.h"
+
+// Octant index of a direction: bit a is set where component a is negative.  A component that is not negative -- +0.0 and
+// -0.0 included -- counts as positive: the sign rule of the upwind weights (w = 1 where d & Sf >= 0) on a face whose normal
+// points along +a.
+static inline int octant_of(const double *d) { return (d[0] < 0 ? 1 : 0) | (d[1] < 0 ? 2 : 0) | (d[2] < 0 ? 4 : 0); }
+
+extern "C" int ffm_ray_octant(const double *d3) { return d3 ? octant_of(d3) : FFM_ERR_ARG; }
+
+extern "C" int ffm_ray_schedule(int px, int py, int pz, int bx, int by, int bz, int nRay, const double *dAve, int *tickRay, int cap)
+{
+    if (px < 1 || py < 1 || pz < 1 || bx < 0 || by < 0 || bz < 0 || bx >= px || by >= py || bz >= pz || nRay < 0 || (nRay && !dAve) || cap < 0 ||
+        (cap && !tickRay)) return FFM_ERR_ARG;
+    const int S = (px - 1) + (py - 1) + (pz - 1) + 1;
+    int t0 = 0;                                                  // first tick of the octant
+    for (int o = 0; o < 8; o++) {
+        int r = 0;
+        for (int i = 0; i < nRay; i++) r += octant_of(dAve + 3 * i) == o;
+        if (!r) continue;
+        // stage: blocks between this one and the upstream corner, axis by axis (upstream = block 0 where the rays run along +a)
+        const int s = ((o & 1) ? px - 1 - bx : bx) + ((o & 2) ? py - 1 - by : by) + ((o & 4) ? pz - 1 - bz : bz);
+        const int nTicks = r + S - 1;
+        for (int t = 0; t < nTicks && t0 + t < cap; t++) tickRay[t0 + t] = -1;
+        int k = 0;                                               // the octant's rays in ray-index order
+        for (int i = 0; i < nRay; i++) if (octant_of(dAve + 3 * i) == o) {
+            if (t0 + k + s < cap) tickRay[t0 + k + s] = i;
+            k++;
+        }
+        t0 += nTicks;
+    }
+    return t0;
+}

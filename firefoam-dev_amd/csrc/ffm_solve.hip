@@ -572,10 +572,18 @@ static inline bool check_convergence(ffm_perf *p, const Controls &k)
 // (ffm_k_spmv_sumA at the top of every solver).  PBiCGStab passes rA0 and pA (pA may be tmp) and gets rA0 = pA = rA and
 // rA0.rA in S_TMP2 as well (k_prologue).  The sums' ranks are added in one all-reduce.
 static int norm_and_initial(ffm_ldu *A, const double *psi, const double *source, const double *Apsi, const double *tmp,
-                            double *rA, ffm_perf *perf, double *rA0 = nullptr, double *pA = nullptr)
+                            double *rA, ffm_perf *perf, double *rA0 = nullptr, double *pA = nullptr, bool rowsOnly = false)
 {
     ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned;
     FFM_TRY(ffm_k_sum(c, psi, N, S_TMP0));
+    if (rowsOnly) {     // the norms of this rank's rows alone (ffm_solve_triangular_rows_d): no sum over ranks
+        FFM_TRY(scalar_op(c, OP_XREF, (double)N));
+        hipLaunchKernelGGL(k_prologue<false>, dim3(sgrid(N)), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, (double *)nullptr, (double *)nullptr, c->partials_d);
+        FFM_TRY(partial_sum_to(c, sgrid(N), S_TMP0, 2));
+        FFM_TRY(scalar_op(c, OP_NORMF));
+        FFM_TRY(scalar_op(c, OP_RES_INIT, 0.0, 0, S_TMP1));
+        return FFM_OK;
+    }
     FFM_TRY(finish_dot(c, OP_XREF, 1, (double)A->globalCells));
     const int g = sgrid(N), nSums = rA0 ? 3 : 2;
     if (rA0) hipLaunchKernelGGL(k_prologue<true>, dim3(g), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, rA0, pA, c->partials_d);
@@ -822,6 +830,42 @@ extern "C" int ffm_solve_d(ffm_ldu *A, int solver, int precond, double tol, doub
         FFM_TRY(ffm_from_internal(A, pi, psi_d));
     }
     FFM_HIP(hipStreamSynchronize(A->ctx->stream));
+    FFM_TRY(ffm_sweep_check_abort(A));
+    return FFM_OK;
+}
+
+// The exact solve of a matrix that is triangular in the matrix's cell order, on this rank's rows alone: calcReciprocalD of a
+// triangular matrix is 1/diag, and one DILU application is then the forward (lower-triangular) or the backward (upper-triangular)
+// substitution in face order -- psi = A^-1 source, one sweep pair, no Krylov iteration.  Nothing here reaches another rank (no
+// ghost refresh, no sum over ranks): faces towards ghost cells must carry zero coefficients, their terms belong in `source`.
+// out: nIterations 1; initialResidual and finalResidual are OpenFOAM's normalised residuals of the start value and of the
+// result, with the sums taken over this rank's rows.  converged says whether the substitution WAS the solve:
+// sum |source - A psi| <= 1e-10 sum |source| (an exact substitution leaves rounding, ~1e-15; a matrix that is not triangular
+// in this order -- a wrong renaming, a ghost face left in -- leaves O(1)).  The test is on the unnormalised sums because
+// OpenFOAM's normFactor is round-off wherever the solution is uniform over the rows.  The matrix is the bound one
+// (ffm_ldu_bind_coeffs_native_d), vectors in the library's cell order.
+extern "C" int ffm_solve_triangular_rows_d(ffm_ldu *A, double *psi_d, const double *source_d, ffm_perf *out)
+{
+    if (!A || !psi_d || !source_d || !out) { ffm_set_error("ffm_solve_triangular_rows_d: null argument"); return FFM_ERR_ARG; }
+    if (!A->identity || !A->ifaces.empty()) { ffm_set_error("ffm_solve_triangular_rows_d: needs the library's cell order and no coupled patches"); return FFM_ERR_UNSUPPORTED; }
+    memset(out, 0, sizeof(*out));
+    FFM_HIP(hipSetDevice(A->ctx->device));
+    ffm_ctx *c = A->ctx; const long N = A->nOwned;
+    double *sumA, *Apsi, *rA;
+    FFM_TRY(ffm_ldu_work(A, 1, &sumA)); FFM_TRY(ffm_ldu_work(A, 2, &Apsi)); FFM_TRY(ffm_ldu_work(A, 3, &rA));
+    FFM_TRY(scalar_op(c, OP_RESET));
+    FFM_TRY(ffm_k_spmv_sumA_rows(A, psi_d, Apsi, sumA));
+    FFM_TRY(norm_and_initial(A, psi_d, source_d, Apsi, sumA, rA, out, nullptr, nullptr, true));
+    FFM_TRY(ffm_precond_setup_i(A, FFM_DILU));
+    FFM_TRY(ffm_precond_apply_i(A, FFM_DILU, false, source_d, psi_d));
+    FFM_TRY(ffm_k_residual_rows(A, psi_d, source_d, rA));
+    FFM_TRY(ffm_k_summag(c, rA, N, S_TMP0));
+    FFM_TRY(scalar_op(c, OP_RES));
+    FFM_TRY(ffm_k_summag(c, source_d, N, S_TMP1));
+    FFM_TRY(ffm_read_scalars(c));
+    out->initialResidual = c->scal_h[S_RES0]; out->finalResidual = c->scal_h[S_RES];
+    out->nIterations = 1; out->singular = 0;
+    out->converged = (c->scal_h[S_TMP0] <= 1e-10 * c->scal_h[S_TMP1]) ? 1 : 0;      // (false for NaN too)
     FFM_TRY(ffm_sweep_check_abort(A));
     return FFM_OK;
 }

@@ -487,6 +487,37 @@ int ffm_fvdom_wall_coeffs_d(ffm_mesh *mesh, int nRay, int ray, const double *d3,
                             double *valueFraction_b, double *refValue_b);
 /* fvDOM::updateG, boundary fluxes (fvDOM.C:740-750): out_b[k] = sum over the rays, in ray order, of all[ray][k] */
 int ffm_fvdom_sum_rays_d(ffm_mesh *mesh, int nRay, const double *all, double *out_b);
+/* The system of ONE ray with `div(Ji,Ii_h) Gauss upwind` in one pass (radiativeIntensityRay.C:267-322):
+ *   fvm::div(Ji, Ii) + fvm::Sp(absorption omega, Ii) == omega/pi (absorption sigma T^4 [+ E/4]),  Ji = dAve & Sf,
+ * inflow boundary faces at ref_b, outflow faces zero-gradient, boundary coefficients added: upper / lower [native faces], diag /
+ * source [cells] are what the solver takes.  Bit for bit what the chain Ji and upwind weights -> ffm_fvm_transport ->
+ * ffm_fvm_boundary_coeffs -> absorption and source -> ffm_fvm_add_boundary gives.  E (the emission), J_f, w_f (Ji and the
+ * weights, should the caller want them) may be NULL.                                                                        */
+int ffm_fvdom_ray_assemble_d(ffm_mesh *mesh, const double *dAve3, double omega, double absorption, double sigma, const double *T,
+                             const double *E, const double *ref_b, double *J_f, double *w_f, double *upper, double *lower,
+                             double *diag, double *source);
+/* One block of a decomposed mesh, a ray whose upstream neighbour blocks are done: for the owned cells cells[nCells] that have a
+ * face towards a ghost cell g, source -= upper[face] I[g] in the row's face order, then both coefficients of the face are set to
+ * 0 -- the inflow from the neighbour ranks becomes a known term and the rows couple owned cells only.                         */
+int ffm_fvdom_fold_ghost_inflow_d(ffm_mesh *mesh, int nCells, const int *cells_d, const double *I, double *upper, double *lower,
+                                  double *source);
+/* The tick schedule of the direction-ordered ray solves on a px x py x pz box of blocks, for the block (bx,by,bz); pure host
+ * code, no GPU.  Rays are grouped by octant (ffm_ray_octant); a block's stage in an octant is its Manhattan distance from the
+ * octant's upstream corner block; at tick t of an octant the block at stage s solves the octant's ray number t - s (rays of an
+ * octant in ray-index order); an octant with r > 0 rays on a grid with S = px + py + pz - 2 stages takes r + S - 1 ticks, one
+ * without rays none; octants follow one another in index order.  tickRay[t], t < min(cap, ticks) = the ray this block solves in
+ * tick t or -1.  Returns the total tick count -- the same for every block -- or a negative ffm_status (tickRay may be NULL
+ * with cap 0 to ask for the count).  Every upstream face neighbour of a block solves a ray exactly one tick before the block. */
+int ffm_ray_schedule(int px, int py, int pz, int bx, int by, int bz, int nRay, const double *dAve, int *tickRay, int cap);
+/* octant index 0..7 of a direction: bit a set where component a is negative; +0.0 and -0.0 count as positive, the sign rule of
+ * the upwind weights (w = 1 where d & Sf >= 0)                                                                               */
+int ffm_ray_octant(const double *d3);
+/* psi = A^-1 source for a bound matrix that is triangular in the library's cell order, as one calcReciprocalD + one DILU
+ * application (the forward / backward substitution in face order) on THIS rank's rows: no ghost refresh, no sum over ranks.
+ * Faces towards ghost cells must carry zero coefficients.  out: nIterations 1, the normalised residuals of the start value and
+ * of the result over this rank's rows; converged = 1 only where sum |source - A psi| <= 1e-10 sum |source|, i.e. where the
+ * substitution was the solve (0: the matrix is not triangular in this order).  Vectors in the library's cell order.           */
+int ffm_solve_triangular_rows_d(ffm_ldu *ldu, double *psi_d, const double *source_d, ffm_perf *out);
 
 /* ------------------------------------------------------- synthetic plume case */
 /* Host-side driver (C++ over the entry points above) of one fireFoam time step on
@@ -519,6 +550,20 @@ int ffm_plume_set_radiation(ffm_plume *plume, int solverFreq, int nPhi, int nThe
  * EEqn gets radiation->Sh(thermo, he) = Ru - fvm::Sp(4 Rp T^3/Cpv, he) - Rp T^3 (T - 4 he/Cpv), Rp = 4 a sigma, Ru = a G - E
  * (radiationModel.C:229-244; solver/YEEqn.H:101).  Without this call the rays keep the round-1 stand-in (a = 0.1, no E, no Sh). */
 int ffm_plume_set_radiation_model(ffm_plume *plume, double absorption, double Ehrr1, double Ehrr2);
+/* How the rays are solved on a block of a decomposed box.  0 (default): every ray is a block-Jacobi PBiCGStab + DILU solve over
+ * all ranks.  1: the staged, direction-ordered sweep -- the ranks walk the ticks of ffm_ray_schedule; in a tick a rank assembles
+ * at most one ray (ffm_fvdom_ray_assemble_d), moves the inflow from its upstream neighbours' ghost values into the source
+ * (ffm_fvdom_fold_ghost_inflow_d) and solves its own, now triangular rows exactly (ffm_solve_triangular_rows_d; the solve is
+ * logged as I<i> with 1 iteration); every tick ends with one ghost exchange entered by all ranks.  No other waiting between
+ * ranks.  Needs the blocks of a box numbered x fastest (rank = bx + px (by + py bz), as ffm_plume_create_block's callers number
+ * them): anything else is FFM_ERR_UNSUPPORTED, never a silent fall-back.  The plume's rays are always `Gauss upwind`.  On a
+ * single block both modes are the direction-ordered solve.  Also read from FFM_PLUME_RADIATION_ORDERING at creation.           */
+int ffm_plume_set_radiation_ordering(ffm_plume *plume, int mode);
+/* tests: the system of one ray in the case's present state, assembled by the operator chain (fused 0) or by
+ * ffm_fvdom_ray_assemble_d (fused 1): diag, source [owned cells, natural order], upper, lower [faces, the case's face order].
+ * Overwrites the driver's matrix work arrays (what the next equation of a step assembles into anyway): call it between
+ * ffm_plume_step calls only, never from inside one.                                                                          */
+int ffm_plume_ray_system(ffm_plume *plume, int ray, int fused, double *diag, double *upper, double *lower, double *source);
 /* tests: a start state and boundary values other than the quiescent ambient / pure-fuel inflow -- Y[5] and h as cell fields in
  * natural blockMesh order, Yamb / Yin the inletOutlet and inlet values of the species, hAmb the inletOutlet value of h; redoes
  * the hydrostatic initialisation (solver/phrghEqn.H).  Single block; after steps, a restart from time 0.                                  */
