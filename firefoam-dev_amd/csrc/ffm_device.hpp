@@ -1,6 +1,10 @@
-// ffm_device.hpp -- device-side helpers shared by the kernels (wave64 only).
+// ffm_device.hpp -- device-side helpers shared by the kernels (wave64 only), and the host-side launch grid of the element kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "ffm_internal.hpp"
+
+// grid of the grid-stride element kernels: 256 threads per block, at most RED_BLOCKS blocks
+static inline int sgrid(long n) { long g = (n + 255) / 256; return (int)std::max(1L, std::min(g, (long)RED_BLOCKS)); }
 
 // wave64 butterfly-free, order-fixed reductions: lane 0 ends with the result.
 __device__ __forceinline__ double wave_sum(double v)

@@ -35,9 +35,6 @@
 #include <numeric>
 #include <unordered_map>
 
-extern "C" int ffm_solve_internal_i(ffm_ldu *A, int solver, int precond, double tol, double relTol, int minIter, int maxIter, int nSweeps,
-                                    double *psi, const double *source, ffm_perf *perf);
-
 namespace {
 
 constexpr double GREAT_ = 1e15;

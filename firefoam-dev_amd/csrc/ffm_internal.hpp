@@ -271,6 +271,8 @@ static inline int ffm_tile_label(int a, int b)
 }
 struct LduView;
 LduView ffm_view(const ffm_ldu *A);
+const int *ffm_mesh_bcells(const ffm_mesh *m);                 // ffm_fv.hip: face cell of every boundary face (device)
+const double *ffm_mesh_geom(const ffm_mesh *m, int which);     // ... and the mesh's device geometry arrays
 // ---- internal helpers shared between translation units -------------------
 int ffm_ldu_work(ffm_ldu *A, int idx, double **out);           // lazily allocated N-vectors
 int ffm_to_internal(ffm_ldu *A, const double *x_d, int slot, const double **out);
@@ -319,6 +321,9 @@ bool ffm_tile_multi_usable(const ffm_ldu *A);
 int ffm_tile_precond_multi(ffm_ldu *A, int precond, int n, const double *const *rD, const double *const *r, double *const *w);
 int ffm_tile_calc_rD_multi(ffm_ldu *A, int n, const double *const *diag, double *const *D);
 int ffm_k_spmv_multi(ffm_ldu *A, int n, const double *const *diag, const double *const *x, double *const *y, double *const *sumA);
+// ffm_solve_d on internal (native-order) vectors, no caller-order staging (ffm_solve.hip; GAMG's coarsest level)
+extern "C" int ffm_solve_internal_i(ffm_ldu *A, int solver, int precond, double tol, double relTol, int minIter, int maxIter, int nSweeps,
+                                    double *psi, const double *source, ffm_perf *perf);
 int ffm_gs_smooth_i(ffm_ldu *A, bool sym, int nSweeps, double *psi, const double *b);
 int ffm_halo_exchange(ffm_ldu *A, const double *x);
 int ffm_ghost_exchange(ffm_ldu *A, double *x);                 // refresh x[nOwned..nCells) from the neighbour ranks          // pack x[faceCells], exchange into haloRecv

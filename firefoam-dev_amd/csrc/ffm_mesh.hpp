@@ -38,7 +38,6 @@ static inline MeshView mview(const ffm_mesh *m)
     return q;
 }
 
-static inline int sgrid(long n) { long g = (n + 255) / 256; return (int)std::max(1L, std::min(g, (long)RED_BLOCKS)); }
 #define GRID_STRIDE(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 #define LAUNCH(kern, n, ...) hipLaunchKernelGGL(kern, dim3(sgrid(n)), dim3(256), 0, m->ctx->stream, __VA_ARGS__)
 // Cell-row kernels walk the matrix' XCD-aware row schedule (chunks of 256 rows; entry i is served by a workgroup with

@@ -552,7 +552,6 @@ __global__ void k_pyro_diff_no(int nCol, int nLay, PyroConst k, const double *__
     }
     out[c] = m;
 }
-extern "C" int ffm_reduce_max(ffm_ctx *, const double *, long, double *);
 extern "C" int ffm_pyro_diff_no(ffm_pyro *P, double deltaT, double *out)
 {
     if (!P || !out) return FFM_ERR_ARG;

@@ -29,7 +29,6 @@
 #include <cmath>
 #include <cstring>
 
-static inline int sgrid(long n) { long g = (n + 255) / 256; return (int)std::max(1L, std::min(g, (long)RED_BLOCKS)); }
 
 // --------------------------------------------------------------- scalar ops ---
 enum {

@@ -10,7 +10,7 @@ def load(path):
     rows.sort()
     return rows
 def last_step(rows):
-    marker = "ffm_plume_step::{lambda(long)#1}"
+    marker = "u_eqn(ffm_plume*)::{lambda(long)#1}"
     starts = [i for i, r in enumerate(rows) if marker in r[2]]
     return rows[starts[-1]:] if starts else rows
 fe, wr = load(sys.argv[1]), load(sys.argv[2])

@@ -1,10 +1,10 @@
 """Per-kernel totals of the LAST time step in a rocprofv3 kernel trace (the --stats table mixes in the start-up).
 usage: step_breakdown.py <..._kernel_trace.csv> [marker-substring | --tail-ms MS]
-The step is taken to start at the last kernel whose name contains the marker (default: the first lambda of ffm_plume_step), or to be
+The step is taken to start at the last kernel whose name contains the marker (default: the first lambda of u_eqn, the first element-wise pass of a step), or to be
 the last MS milliseconds of the trace (scripts/class_layer_probe.py writes that figure)."""
 import csv, sys, collections
 path = sys.argv[1]
-marker = sys.argv[2] if len(sys.argv) > 2 else "ffm_plume_step::{lambda(long)#1}"
+marker = sys.argv[2] if len(sys.argv) > 2 else "u_eqn(ffm_plume*)::{lambda(long)#1}"
 rows = []
 with open(path) as f:
     for r in csv.DictReader(f):
