@@ -221,6 +221,10 @@ def lib():
         "ffm_fvm_HbyA3": ([vp, dp, dp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(vp)], C.c_int),
         "ffm_fvc_flux_rho": ([vp, dp, dp, dp, dp, dp], C.c_int),
         "ffm_fvm_pressure_eqn": ([vp, C.c_double] + [dp] * 6 + [C.c_double] + [dp] * 9, C.c_int),
+        "ffm_fvc_ddt_corr": ([vp, C.c_double] + [dp] * 6, C.c_int),
+        "ffm_fvc_rho_eqn": ([vp, C.c_double] + [dp] * 4, C.c_int),
+        "ffm_fvc_div_phiK_terms": ([vp, C.c_int] + [C.c_double] * 4 + [dp] * 14, C.c_int),
+        "ffm_fvdom_ray_assemble_d": ([vp, hp] + [C.c_double] * 3 + [dp] * 9, C.c_int),
         "ffm_mesh_nboundary": ([vp], C.c_int),
         "ffm_mesh_nnative": ([vp], C.c_int),
         "ffm_faces_to_native": ([vp, hp, dp], C.c_int),

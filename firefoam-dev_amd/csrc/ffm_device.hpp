@@ -97,16 +97,17 @@ __device__ __forceinline__ int face_of(const LduView &v, int cell, int slot) { r
 // predicated, fully unrolled loads (W = compile-time bound on the slot count), so that the
 // index loads of all slots are in flight together and the dependent gathers likewise: a row
 // costs two memory round trips instead of two per slot.  Padding slots point at harmless
-// addresses (own cell, face 0) and are masked out of the arithmetic.
+// addresses (own cell, face 0) and are masked out of the arithmetic.  s0: the first slot to load (a kernel that walks a wide row
+// in chunks of W slots).
 template <int W> struct RowEnt { int nb[W]; int f[W]; bool on[W]; };
 
 // NT: index streams are read once per kernel -- load them non-temporally so they do not evict the gather targets
 // (x, coefficients) from the XCD's L2
 template <int W, bool NT = false>
-__device__ __forceinline__ void load_lower(const LduView &v, int c, RowEnt<W> &R)
+__device__ __forceinline__ void load_lower(const LduView &v, int c, RowEnt<W> &R, int s0 = 0)
 {
     const int sl = c >> 6, lane = c & 63;
-    const int lb = lo_base(v, sl), lw = lo_width(v, sl);
+    const int lb = lo_base(v, sl) + s0 * 64, lw = lo_width(v, sl) - s0;
     int e[W];
 #pragma unroll
     for (int s = 0; s < W; s++) e[s] = (s < lw) ? (NT ? __builtin_nontemporal_load(&v.loEnt[lb + s * 64 + lane]) : v.loEnt[lb + s * 64 + lane]) : -1;
@@ -120,10 +121,10 @@ __device__ __forceinline__ void load_lower(const LduView &v, int c, RowEnt<W> &R
 
 // MASK_GHOST: drop upper neighbours that are ghost cells (index >= v.N): block-Jacobi sweeps
 template <int W, bool MASK_GHOST = false, bool NT = false>
-__device__ __forceinline__ void load_upper(const LduView &v, int c, RowEnt<W> &R)
+__device__ __forceinline__ void load_upper(const LduView &v, int c, RowEnt<W> &R, int s0 = 0)
 {
     const int sl = c >> 6, lane = c & 63;
-    const int ub = up_base(v, sl), uw = up_width(v, sl);
+    const int ub = up_base(v, sl) + s0 * 64, uw = up_width(v, sl) - s0;
 #pragma unroll
     for (int s = 0; s < W; s++) {
         const int idx = ub + s * 64 + lane;

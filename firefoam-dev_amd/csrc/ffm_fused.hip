@@ -220,51 +220,59 @@ __device__ __forceinline__ double mv_limiter(int scheme, double twoByk, double l
 // Every face is written by its UPWIND cell (the owner when the flux is positive, else the neighbour): the limiter needs the upwind
 // cell's gradient of every field, which that cell holds itself -- only the other cell's value is gathered (8 B per field and face
 // instead of 32).  P / N keep their owner / neighbour meaning, so the arithmetic is that of the owner-face loop, bit for bit.
+// The faces of a row do not depend on each other, so a row wider than 8 slots is walked in chunks of 8: with all 2 x 32 faces of
+// the W = 32 instantiation live across the field loop (64 predicates, 320 doubles: 512 registers, 2.2 KB of scratch, some 450
+// spilled scalar registers) the kernel's weights were wrong and differed from launch to launch.
 template <int W>
 __global__ __launch_bounds__(256) void k_mv_weights(MeshView q, MvWeights a)
 {
+    constexpr int CH = W < 8 ? W : 8;
     CELL_SCHED(ci, q) {
         const int c = (int)ci;
-        RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
         const double cx = a.Cx[c], cy = a.Cy[c], cz = a.Cz[c];
-        double fl[2 * W], lim[2 * W], dx[2 * W], dy[2 * W], dz[2 * W];
-        bool mine[2 * W], ghostUp[W];       // ghostUp: the upwind cell is a ghost cell (a cut face of a decomposed mesh, owned by c): c writes it too
-#pragma unroll
-        for (int s = 0; s < W; s++) {
-            // lower face: owner = L.nb[s], neighbour = c; upwind is c when the flux is not positive.  d = C[neighbour] - C[owner]
-            fl[s] = L.on[s] ? a.phi[L.f[s]] : 0.0; mine[s] = L.on[s] && !(fl[s] > 0);
-            dx[s] = cx - a.Cx[L.nb[s]]; dy[s] = cy - a.Cy[L.nb[s]]; dz[s] = cz - a.Cz[L.nb[s]];
-            // upper face: owner = c, neighbour = U.nb[s]; upwind is c when the flux is positive
-            fl[W + s] = U.on[s] ? a.phi[U.f[s]] : 0.0; mine[W + s] = U.on[s] && fl[W + s] > 0;
-            ghostUp[s] = U.on[s] && !(fl[W + s] > 0) && U.nb[s] >= q.v.N;
-            dx[W + s] = a.Cx[U.nb[s]] - cx; dy[W + s] = a.Cy[U.nb[s]] - cy; dz[W + s] = a.Cz[U.nb[s]] - cz;
-            lim[s] = lim[W + s] = 1.0;
-        }
 #pragma unroll 1
-        for (int i = 0; i < a.nf; i++) {
-            const double *__restrict__ vf = a.vf[i];
-            const double vc = vf[c], gxc = a.gx[i][c], gyc = a.gy[i][c], gzc = a.gz[i][c];
-            const int sch = a.scheme[i];
+        for (int s0 = 0; s0 < W; s0 += CH) {
+            if (W > CH && s0 > 0 && s0 >= max(lo_width(q.v, c >> 6), up_width(q.v, c >> 6))) break;     // no slots left in this slice (one wave)
+            RowEnt<CH> L, U; load_lower<CH>(q.v, c, L, s0); load_upper<CH>(q.v, c, U, s0);
+            double fl[2 * CH], lim[2 * CH], dx[2 * CH], dy[2 * CH], dz[2 * CH];
+            bool mine[2 * CH], ghostUp[CH];     // ghostUp: the upwind cell is a ghost cell (a cut face of a decomposed mesh, owned by c): c writes it too
 #pragma unroll
-            for (int s = 0; s < W; s++) {
-                if (mine[s]) {          // P = owner's value (the other cell), N = c's
-                    const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[s], vf[L.nb[s]], vc, dx[s] * gxc + dy[s] * gyc + dz[s] * gzc);
-                    lim[s] = i == 0 ? l : fmin(lim[s], l);
-                }
-                if (mine[W + s]) {      // P = c's value, N = the other cell's
-                    const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[W + s], vc, vf[U.nb[s]], dx[W + s] * gxc + dy[W + s] * gyc + dz[W + s] * gzc);
-                    lim[W + s] = i == 0 ? l : fmin(lim[W + s], l);
-                } else if (ghostUp[s]) {
-                    const int n = U.nb[s];
-                    const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[W + s], vc, vf[n], dx[W + s] * a.gx[i][n] + dy[W + s] * a.gy[i][n] + dz[W + s] * a.gz[i][n]);
-                    lim[W + s] = i == 0 ? l : fmin(lim[W + s], l);
+            for (int s = 0; s < CH; s++) {
+                // lower face: owner = L.nb[s], neighbour = c; upwind is c when the flux is not positive.  d = C[neighbour] - C[owner]
+                fl[s] = L.on[s] ? a.phi[L.f[s]] : 0.0; mine[s] = L.on[s] && !(fl[s] > 0);
+                dx[s] = cx - a.Cx[L.nb[s]]; dy[s] = cy - a.Cy[L.nb[s]]; dz[s] = cz - a.Cz[L.nb[s]];
+                // upper face: owner = c, neighbour = U.nb[s]; upwind is c when the flux is positive
+                fl[CH + s] = U.on[s] ? a.phi[U.f[s]] : 0.0; mine[CH + s] = U.on[s] && fl[CH + s] > 0;
+                ghostUp[s] = U.on[s] && !(fl[CH + s] > 0) && U.nb[s] >= q.v.N;
+                dx[CH + s] = a.Cx[U.nb[s]] - cx; dy[CH + s] = a.Cy[U.nb[s]] - cy; dz[CH + s] = a.Cz[U.nb[s]] - cz;
+                lim[s] = lim[CH + s] = 1.0;
+            }
+#pragma unroll 1
+            for (int i = 0; i < a.nf; i++) {
+                const double *__restrict__ vf = a.vf[i];
+                const double vc = vf[c], gxc = a.gx[i][c], gyc = a.gy[i][c], gzc = a.gz[i][c];
+                const int sch = a.scheme[i];
+#pragma unroll
+                for (int s = 0; s < CH; s++) {
+                    if (mine[s]) {          // P = owner's value (the other cell), N = c's
+                        const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[s], vf[L.nb[s]], vc, dx[s] * gxc + dy[s] * gyc + dz[s] * gzc);
+                        lim[s] = i == 0 ? l : fmin(lim[s], l);
+                    }
+                    if (mine[CH + s]) {     // P = c's value, N = the other cell's
+                        const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[CH + s], vc, vf[U.nb[s]], dx[CH + s] * gxc + dy[CH + s] * gyc + dz[CH + s] * gzc);
+                        lim[CH + s] = i == 0 ? l : fmin(lim[CH + s], l);
+                    } else if (ghostUp[s]) {
+                        const int n = U.nb[s];
+                        const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[CH + s], vc, vf[n], dx[CH + s] * a.gx[i][n] + dy[CH + s] * a.gy[i][n] + dz[CH + s] * a.gz[i][n]);
+                        lim[CH + s] = i == 0 ? l : fmin(lim[CH + s], l);
+                    }
                 }
             }
-        }
 #pragma unroll
-        for (int s = 0; s < W; s++) {
-            if (mine[s]) { const int e = L.f[s]; const double p0 = fl[s] >= 0 ? 1.0 : 0.0; a.out[e] = lim[s] * q.w[e] + (1.0 - lim[s]) * p0; }
-            if (mine[W + s] || ghostUp[s]) { const int e = U.f[s]; const double p0 = fl[W + s] >= 0 ? 1.0 : 0.0; a.out[e] = lim[W + s] * q.w[e] + (1.0 - lim[W + s]) * p0; }
+            for (int s = 0; s < CH; s++) {
+                if (mine[s]) { const int e = L.f[s]; const double p0 = fl[s] >= 0 ? 1.0 : 0.0; a.out[e] = lim[s] * q.w[e] + (1.0 - lim[s]) * p0; }
+                if (mine[CH + s] || ghostUp[s]) { const int e = U.f[s]; const double p0 = fl[CH + s] >= 0 ? 1.0 : 0.0; a.out[e] = lim[CH + s] * q.w[e] + (1.0 - lim[CH + s]) * p0; }
+            }
         }
     }
 }

@@ -258,15 +258,22 @@ def grad(mesh, vf, bvals):
     return out
 
 
-def reconstruct(mesh, ssf, bssf):
-    """fvc::reconstruct(ssf) = inv(surfaceSum(Sf (x) Sf/magSf)) & surfaceSum((Sf/magSf)*ssf)."""
-    N = mesh.nCells
-    T = np.zeros((N, 3, 3)); v = np.zeros((N, 3))
+def reconstruct_tensor(mesh):
+    """T = surfaceSum(Sf (x) Sf/magSf), the cell tensor fvc::reconstruct inverts: [nCells][3][3]."""
+    T = np.zeros((mesh.nCells, 3, 3))
     for a in range(3):
-        v[:, a] = surface_sum(mesh, mesh.Sf[:, a] / mesh.magSf * ssf, [p.Sf[:, a] / p.magSf * b for p, b in zip(mesh.patches, bssf)])
         for b_ in range(3):
             T[:, a, b_] = surface_sum(mesh, mesh.Sf[:, a] * mesh.Sf[:, b_] / mesh.magSf,
                                       [p.Sf[:, a] * p.Sf[:, b_] / p.magSf for p in mesh.patches])
+    return T
+
+
+def reconstruct(mesh, ssf, bssf):
+    """fvc::reconstruct(ssf) = inv(surfaceSum(Sf (x) Sf/magSf)) & surfaceSum((Sf/magSf)*ssf)."""
+    N = mesh.nCells
+    T = reconstruct_tensor(mesh); v = np.zeros((N, 3))
+    for a in range(3):
+        v[:, a] = surface_sum(mesh, mesh.Sf[:, a] / mesh.magSf * ssf, [p.Sf[:, a] / p.magSf * b for p, b in zip(mesh.patches, bssf)])
     # 2-D / 1-D meshes (empty patches): OpenFOAM's inv(tensorField) finds the missing directions from the first cell, adds 1 on
     # those diagonals before inverting and takes it off afterwards (src/OpenFOAM/fields/Fields/symmTensorField/symmTensorField.C)
     scale = (T[0] ** 2).sum()

@@ -5,10 +5,15 @@ Bars: the row kernels (Amul, Tmul, sumA, residual) and every sweep (DIC/DILU rec
 precondition, Gauss-Seidel) accumulate each row in the reference's face order with FMA
 contraction off, so they must be BIT-EXACT.  Solvers contain dot products (tree sums on the
 GPU, serial sums on the CPU), so residual histories agree to ~1e-12 relative; iteration counts
-must be identical and converged fields agree to 1e-8 rel-L2 (north_star tolerance)."""
+must be identical and converged fields agree to 1e-8 rel-L2 (north_star tolerance).
+
+Row-width buckets (FFM_DISPATCH_W of csrc/ffm_device.hpp): the boxes, the chain and the plane run W = 3, the relabelled DAG mesh
+W = 8 with non-uniform slices; the merged meshes `w4`, `w16u14`, `w32l30` and `w32multi` (tests/merged_mesh.py) run W = 4, 16 and 32
+of every row kernel and sweep against the serial face loop, bit for bit."""
 import numpy as np
 import pytest
 
+import merged_mesh as MM
 from common import laplacian_like, random_dag_mesh, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -27,9 +32,11 @@ def meshes(O):
 @pytest.fixture(scope="module", params=["hex_natural", "hex_levelmajor", "dag_random", "chain", "plane",
                                         "hex_levelmajor_t41", "hex_natural_t29", "plane_t17",
                                         "hex_natural_t37", "dag_random_t23", "chain_t64", "plane_t50", "hex_natural_t500", "hex_tiles_t0",
-                                        "hex_natural_lv", "hex_levelmajor_lv", "chain_lv", "plane_lv", "hex_big", "hex_big_lv", "hex_baffled_t0"])
+                                        "hex_natural_lv", "hex_levelmajor_lv", "chain_lv", "plane_lv", "hex_big", "hex_big_lv", "hex_baffled_t0",
+                                        "w4", "w16u14", "w32l30", "w32multi", "w16u14_lv", "w32l30_lv", "w16u14_t0"])
 def case(request, O, ffm, ctx):
-    """`_tNN`: tiled wavefront sweep on chunks of NN cells, so that the cross-workgroup hand-off (mailboxes, LDS ring
+    """`w*`: the merged meshes of tests/merged_mesh.py in their own numbering (one row of 4, 14, 30 or 24 faces among rows of 3 or 4:
+    the W = 4, 16 and 32 instantiations of the row kernels and sweeps, non-uniform slice widths).  `_tNN`: tiled wavefront sweep on chunks of NN cells, so that the cross-workgroup hand-off (mailboxes, LDS ring
     wrap-around) is exercised on small meshes too (t0: a 2-D tile hint).  `_lv`: level-scheduled sweeps.  No suffix: the
     default (tiled sweeps on detected boxes and hinted meshes, level-scheduled otherwise)."""
     import os
@@ -65,6 +72,22 @@ def _make_case(name, grp, O, ffm, ctx):
         hint = ((c // nx) % ny) // 3 + 10 * ((c // (nx * ny)) // 3)      # 3x3 tiles of cell columns (j,k)
         A = ffm.lduMatrix(ctx, N, l, u, groupHint=hint)
         assert A.sweep_mode == 2
+        yield name, N, l, u, A
+        A.close()
+        return
+    elif name in MM.CASES:
+        m = MM.case(name)
+        N, l, u = m.nCells, m.l.astype(np.int32), m.u.astype(np.int32)
+        # the row-width instantiation the case is named after, from the addressing the library is given
+        assert MM.widths(l, u) == MM.CASES[name][4:6] and MM.bucket(max(np.bincount(l).max(), np.bincount(u).max())) == MM.CASES[name][6]
+        if grp == "0":
+            # a 2-D tile hint as `hex_tiles` builds it, from the cells' (j, k): more than 3 owned upper neighbours make the tile plan
+            # unusable, the handle falls back to the level-scheduled sweeps
+            j, k = np.floor(m.C[:, 1] / 0.1).astype(int), np.floor(m.C[:, 2] / 0.1).astype(int)
+            A = ffm.lduMatrix(ctx, N, l, u, groupHint=j // 3 + 10 * (k // 3))
+            assert A.sweep_mode != 2
+        else:
+            A = ffm.lduMatrix(ctx, N, l, u)
         yield name, N, l, u, A
         A.close()
         return
@@ -260,3 +283,21 @@ def test_dataflow_sweeps_bit_exact(O, ffm, ctx, monkeypatch):
                 got = A.smooth(ctx.to_device(psi0), ctx.to_device(b), nSweeps=2, smoother="symGaussSeidel" if sym else "GaussSeidel")
                 assert np.array_equal(got.cpu().numpy(), Ao.gs_smooth(psi0, b, nSweeps=2, sym=sym))
         A.close()
+
+
+@pytest.mark.parametrize("name,message", [("u18", "a cell owns more than 16 faces towards owned cells"),
+                                          ("l34", r"a cell has \d+ upper / 34 lower faces \(> 32\): not supported by the sliced layout")])
+def test_too_wide_rows_are_refused(O, ffm, ctx, name, message):
+    """a cell with more than 16 owned upper faces (the packed lower entry has 4 bits for the owner's slot) or more than 32 faces on one
+    side (the widest instantiation) is refused by ffm_ldu_create with FFM_ERR_UNSUPPORTED before anything is launched, and the
+    context goes on working"""
+    m = MM.case(name)
+    assert MM.widths(m.l, m.u) == MM.REFUSED[name][4:6]
+    with pytest.raises(ffm.FfmError, match=r"failed \(-5\): " + message):
+        ffm.lduMatrix(ctx, m.nCells, m.l, m.u)
+    N, l, u = O.hex_ldu(9, 7, 8)
+    diag, up, lo = laplacian_like(O, N, l, u, seed=3, asym=0.35, shift=0.05)
+    A = ffm.lduMatrix(ctx, N, l, u).set_coeffs(diag, up, lo)
+    x = 2 * O.hash_u(0xF4, np.arange(N)) - 0.7
+    assert np.array_equal(A.Amul(ctx.to_device(x)).cpu().numpy(), O.Ldu(N, l, u).set_coeffs(diag, up, lo).amul(x))
+    A.close()

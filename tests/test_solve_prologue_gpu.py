@@ -7,7 +7,8 @@ calcReciprocalD stores 1/D itself).
     among them).
 (b) PCG + DIC and PBiCGStab + DILU / DIC, one solve at a time and through ffm_solve_multi_d (PBiCGStab: lock step), against the oracle
     with the bars of test_ldu_gpu.py::test_solver_parity: equal iteration counts, initial residual to 1e-12 relative, final residual
-    to 5 % + 2e-12 (tree sums against serial sums), fields to 1e-8 rel-L2.  One system starts from its solution: no iteration, the
+    to 5 % + 2e-12 (tree sums against serial sums), fields to 1e-8 rel-L2.  The merged meshes `w4`, `w16u14`, `w32l30`, `w32multi`
+    (tests/merged_mesh.py) bring the W = 4, 16 and 32 instantiations of k_flow_sweep and of the prologue's row kernels.  One system starts from its solution: no iteration, the
     field untouched (its residual is rounding noise of the Amul, so only `below the tolerance` is asked of it); the lock-step lanes
     stop at different iterations."""
 import os
@@ -21,7 +22,8 @@ from test_ldu_gpu import _make_case
 pytestmark = pytest.mark.gpu
 
 CASES = ["hex_natural", "hex_levelmajor", "dag_random", "chain", "plane", "hex_levelmajor_t41", "hex_natural_t29", "plane_t17",
-         "hex_natural_t37", "dag_random_t23", "chain_t64", "plane_t50", "hex_natural_t500", "hex_tiles_t0", "hex_big", "hex_baffled_t0"]
+         "hex_natural_t37", "dag_random_t23", "chain_t64", "plane_t50", "hex_natural_t500", "hex_tiles_t0", "hex_big", "hex_baffled_t0",
+         "w4", "w16u14", "w32l30", "w32multi"]
 
 
 @pytest.fixture(scope="module", params=CASES)
