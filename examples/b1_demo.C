@@ -584,10 +584,10 @@ extern "C" int b1_thermo_handle(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, ffm_t
 // (cells + boundary faces), emission E, absorption a, wall emissivities, fvDOMCoeffs nPhi / nTheta / maxIter / convergence and the
 // div(Ji,Ii_h) scheme (0 upwind, 5 linearUpwind); Ii by PBiCGStab + DILU to IiTol.  Out: I [nRay][N], G [N], qin / qem / qr [B],
 // iters[nCalls] = iterations of fvDOM::calculate per call, nSolves = number of ray solves of the LAST call.  Returns nRay.
-// tests/test_fvdom_gpu.py compares with oracle/fvdom.py.
-extern "C" int b1_fvdom(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, int emptyDirections, int nPhi, int nTheta, int maxIter, double tolerance, int scheme,
-                        double a, double IiTol, const double* T, const double* Tb, const double* E, const double* emissivity, int nCalls,
-                        double* IOut, double* GOut, double* qinOut, double* qemOut, double* qrOut, int* iters, int* nSolves)
+// tests/test_fvdom_gpu.py compares with oracle/fvdom.py.  b1_fvdom_ordered: the same through the flow-ordered exact ray solves.
+static int b1_fvdom_run(bool ordered, ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, int emptyDirections, int nPhi, int nTheta, int maxIter, double tolerance,
+                        int scheme, double a, double IiTol, const double* T, const double* Tb, const double* E, const double* emissivity, int nCalls,
+                        double* IOut, double* GOut, double* qinOut, double* qemOut, double* qrOut, int* iters, int* nSolves, int* maxSolveIterations)
 {
     fvMesh mesh(ctx, ldu, msh, 1.0);
     for (int d = 0; d < 3; d++) if (emptyDirections & (1 << d)) mesh.solutionD[d] = -1;
@@ -601,18 +601,38 @@ extern "C" int b1_fvdom(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, int emptyDire
     std::vector<double> zeroB(B, 0.0);
     fvDOM dom(mesh, Tf, nPhi, nTheta, 1, a, 5.670367e-8, 1.0, 1.0, zeroB.data());
     dom.setIteration(maxIter, tolerance);
+    dom.setOrderedSolves(ordered);
     dom.emissivity().assignHost(emissivity);
-    const bool quiet = std::getenv("FFM_FOAM_QUIET") != nullptr; (void)quiet;
+    int maxIts = 0;
     for (int c = 0; c < nCalls; c++) {
         mesh.log.clear();
         dom.correct();
         iters[c] = dom.lastIterations_;
+        for (const solverPerformance& sp : mesh.log) maxIts = std::max(maxIts, sp.nIterations);
     }
     *nSolves = (int)mesh.log.size();
+    if (maxSolveIterations) *maxSolveIterations = maxIts;
     for (label i = 0; i < dom.nRay(); i++) dom.I_[i].v.toHost(IOut + (size_t)i*N);
     dom.G_.v.toHost(GOut); dom.qin_.toHost(qinOut); dom.qem_.toHost(qemOut); dom.qr_.toHost(qrOut);
     FFM_FOAM_CHK(ffm_ctx_sync(ctx));
     return dom.nRay();
+}
+extern "C" int b1_fvdom(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, int emptyDirections, int nPhi, int nTheta, int maxIter, double tolerance, int scheme,
+                        double a, double IiTol, const double* T, const double* Tb, const double* E, const double* emissivity, int nCalls,
+                        double* IOut, double* GOut, double* qinOut, double* qemOut, double* qrOut, int* iters, int* nSolves)
+{
+    return b1_fvdom_run(false, ctx, ldu, msh, emptyDirections, nPhi, nTheta, maxIter, tolerance, scheme, a, IiTol, T, Tb, E, emissivity, nCalls, IOut, GOut,
+                        qinOut, qemOut, qrOut, iters, nSolves, nullptr);
+}
+// the same with fvDOM::setOrderedSolves(true): every ray by one exact forward substitution in the order of its own matrix (IiTol is
+// not used).  maxSolveIterations = the largest iteration count of any ray solve of all calls: 1.  tests/test_fvdom_ordered_gpu.py
+extern "C" int b1_fvdom_ordered(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, int emptyDirections, int nPhi, int nTheta, int maxIter, double tolerance,
+                                int scheme, double a, double IiTol, const double* T, const double* Tb, const double* E, const double* emissivity,
+                                int nCalls, double* IOut, double* GOut, double* qinOut, double* qemOut, double* qrOut, int* iters, int* nSolves,
+                                int* maxSolveIterations)
+{
+    return b1_fvdom_run(true, ctx, ldu, msh, emptyDirections, nPhi, nTheta, maxIter, tolerance, scheme, a, IiTol, T, Tb, E, emissivity, nCalls, IOut, GOut,
+                        qinOut, qemOut, qrOut, iters, nSolves, maxSolveIterations);
 }
 
 // ---- Time::setDeltaT / operator++ of include/ffmFoam.H (Time::adjustDeltaT with writeControl adjustableRunTime) stepped n times with the

@@ -258,6 +258,11 @@ def lib():
         "ffm_plume_ray_system": ([vp, C.c_int, C.c_int, hp, hp, hp, hp], C.c_int),
         "ffm_ray_schedule": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, hp, ip, C.c_int], C.c_int),
         "ffm_ray_octant": ([hp], C.c_int),
+        "ffm_flow_levels": ([C.c_int, C.c_int, ip, ip, hp, hp, ip, ip], C.c_int),
+        "ffm_flow_order_create": ([vp, C.POINTER(vp)], C.c_int),
+        "ffm_flow_order_nlevels": ([vp], C.c_int),
+        "ffm_flow_order_destroy": ([vp], C.c_int),
+        "ffm_solve_ordered_d": ([vp, vp, dp, dp, C.POINTER(Perf)], C.c_int),
         "ffm_plume_set_initial_state": ([vp, C.POINTER(C.c_void_p), hp, hp, hp, C.c_double], C.c_int),
         "ffm_plume_override_mv_weights": ([vp, hp], C.c_int),
         "ffm_plume_ncells": ([vp], C.c_int),
@@ -318,6 +323,41 @@ def ray_schedule(grid, block, dAve):
     ticks = np.full(max(n, 1), -1, dtype=np.int32)
     _check(min(lib().ffm_ray_schedule(*args, len(d), _hp(d), _ip(ticks), n), 0), "ffm_ray_schedule")
     return ticks[:n], n
+
+
+def flow_levels(nCells, lowerAddr, upperAddr, upper, lower):
+    """(order, nLevels): the cells of a matrix with at most one non-zero off-diagonal per face (an upwind ray equation) in the
+    level-major order of their dependencies, under which the matrix is triangular (ffm_flow_levels; host code, no GPU).
+    FfmError where the non-zero entries form a cycle."""
+    l = np.ascontiguousarray(lowerAddr, np.int32)
+    u = np.ascontiguousarray(upperAddr, np.int32)
+    up = np.ascontiguousarray(upper, np.float64)
+    lo = np.ascontiguousarray(lower, np.float64)
+    if not (len(l) == len(u) == len(up) == len(lo)):
+        raise FfmError("flow_levels: lowerAddr, upperAddr, upper and lower must have one entry per face")
+    order = np.empty(max(int(nCells), 1), np.int32)
+    nLev = C.c_int(0)
+    _check(lib().ffm_flow_levels(int(nCells), len(l), _ip(l), _ip(u), _hp(up), _hp(lo), _ip(order), C.byref(nLev)),
+           "ffm_flow_levels")
+    return order[:int(nCells)], nLev.value
+
+
+class FlowOrder:
+    """The dependency order of the coefficients an lduMatrix held when this was made (ffm_flow_order): lduMatrix.flow_order()"""
+
+    def __init__(self, A):
+        h = C.c_void_p()
+        _check(lib().ffm_flow_order_create(A.h, C.byref(h)), "ffm_flow_order_create")
+        self.h = h
+
+    @property
+    def nLevels(self):
+        return lib().ffm_flow_order_nlevels(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ffm_flow_order_destroy(self.h)
+            self.h = None
 
 
 def tile_hint_from_centres(C_, tileCells=0):
@@ -685,6 +725,20 @@ class lduMatrix:
         perf = Perf()
         _check(lib().ffm_solve_d(self.h, SOLVERS[solver], p, tolerance, relTol, minIter, maxIter, nSweeps,
                                  C.c_void_p(psi.data_ptr()), C.c_void_p(source.data_ptr()), C.byref(perf)), "ffm_solve_d")
+        return perf.as_dict()
+
+    def flow_order(self):
+        """the dependency order of the coefficients the matrix holds now (an upwind ray matrix): .nLevels, .close()"""
+        self.ctx._ready()
+        return FlowOrder(self)
+
+    def solve_ordered(self, order, psi, source):
+        """psi = A^-1 source by one forward substitution in `order` (ffm_solve_ordered_d), psi updated in place; FfmError, psi
+        untouched, where the order does not fit the coefficients the matrix holds now.  Returns the perf dict."""
+        self.ctx._ready()
+        perf = Perf()
+        _check(lib().ffm_solve_ordered_d(self.h, order.h, C.c_void_p(psi.data_ptr()), C.c_void_p(source.data_ptr()), C.byref(perf)),
+               "ffm_solve_ordered_d")
         return perf.as_dict()
 
     def solve_multi(self, diags, upper, lower, psis, sources, solver="PBiCGStab", preconditioner="DILU", tolerance=1e-6, relTol=0.0,

@@ -37,3 +37,62 @@ extern "C" int ffm_ray_schedule(int px, int py, int pz, int bx, int by, int bz, 
     }
     return t0;
 }
+
+// ---------------------------------------------------------------------------------------------- flow order of a ray matrix ---
+// An upwind ray matrix has at most one non-zero off-diagonal coefficient per face, so its rows form a dependency graph: row u[f]
+// needs cell l[f] where lower[f] != 0, row l[f] needs cell u[f] where upper[f] != 0, a face with two zeros is no edge.  Where
+// that graph has no cycle the matrix is triangular under the level-major cell order found here (level = longest dependency
+// path; ascending cell index inside a level), and one forward substitution in that order is the exact solve
+// (ffm_solve_ordered_d).  Kahn's algorithm, O(nCells + nFaces), one thread.  A cycle -- a face with two non-zero coefficients
+// is the shortest -- is refused.
+#include <vector>
+void ffm_set_error(const char *fmt, ...);
+
+extern "C" int ffm_flow_levels(int nCells, int nFaces, const int *lowerAddr, const int *upperAddr, const double *upper, const double *lower,
+                               int *order, int *nLevels)
+{
+    if (nCells < 0 || nFaces < 0 || (nFaces && (!lowerAddr || !upperAddr || !upper || !lower)) || (nCells && !order) || !nLevels) return FFM_ERR_ARG;
+    const int N = nCells, F = nFaces;
+    for (int f = 0; f < F; f++)
+        if (lowerAddr[f] < 0 || lowerAddr[f] >= N || upperAddr[f] < 0 || upperAddr[f] >= N) {
+            ffm_set_error("ffm_flow_levels: face %d joins cells %d and %d of %d", f, lowerAddr[f], upperAddr[f], N);
+            return FFM_ERR_ARG;
+        }
+    // successors of every cell (the rows that need it), CSR
+    std::vector<int> start(N + 1, 0), indeg(N, 0);
+    for (int f = 0; f < F; f++) {
+        if (lower[f] != 0) { start[lowerAddr[f] + 1]++; indeg[upperAddr[f]]++; }
+        if (upper[f] != 0) { start[upperAddr[f] + 1]++; indeg[lowerAddr[f]]++; }
+    }
+    for (int c = 0; c < N; c++) start[c + 1] += start[c];
+    std::vector<int> succ(start[N]), fill(start.begin(), start.end() - 1);
+    for (int f = 0; f < F; f++) {
+        if (lower[f] != 0) succ[fill[lowerAddr[f]]++] = upperAddr[f];
+        if (upper[f] != 0) succ[fill[upperAddr[f]]++] = lowerAddr[f];
+    }
+    std::vector<int> lev(N, 0), queue;
+    queue.reserve(N);
+    for (int c = 0; c < N; c++) if (!indeg[c]) queue.push_back(c);
+    int nLev = 0;
+    for (size_t q = 0; q < queue.size(); q++) {
+        const int c = queue[q];
+        nLev = nLev > lev[c] + 1 ? nLev : lev[c] + 1;
+        for (int k = start[c]; k < start[c + 1]; k++) {
+            const int r = succ[k];
+            if (lev[r] < lev[c] + 1) lev[r] = lev[c] + 1;
+            if (--indeg[r] == 0) queue.push_back(r);
+        }
+    }
+    if ((int)queue.size() != N) {
+        ffm_set_error("ffm_flow_levels: the non-zero off-diagonal coefficients form a cycle through %d of %d cells: "
+                      "the matrix is not triangular under any cell order", N - (int)queue.size(), N);
+        return FFM_ERR_UNSUPPORTED;
+    }
+    // level-major, ascending cell index inside a level
+    std::vector<int> pos(nLev + 1, 0);
+    for (int c = 0; c < N; c++) pos[lev[c] + 1]++;
+    for (int i = 0; i < nLev; i++) pos[i + 1] += pos[i];
+    for (int c = 0; c < N; c++) order[pos[lev[c]]++] = c;
+    *nLevels = nLev;
+    return FFM_OK;
+}

@@ -869,6 +869,206 @@ extern "C" int ffm_solve_triangular_rows_d(ffm_ldu *A, double *psi_d, const doub
     return FFM_OK;
 }
 
+// ------------------------------------------------------------------ flow-ordered exact solve ---
+// A matrix with at most one non-zero off-diagonal coefficient per face and no cycle among them (an upwind ray equation,
+// fvm::div(Ji, Ii) + fvm::Sp(k omega, Ii), on any mesh with planar faces) is triangular under the level-major order of its own
+// dependency graph (ffm_flow_levels, ffm_rays.cpp).  ffm_flow_order keeps that order on the device: int[N], 4 N bytes, in the
+// matrix's internal cell numbering.  ffm_solve_ordered_d is one dataflow sweep in that order -- the machinery of k_flow_sweep:
+// chunks of 256 positions by ticket, published values, bounded waits -- in which a row waits for the cells of its non-zero
+// entries only, lower faces then upper faces in face order, one division: bitwise the serial forward substitution.
+// The order is never trusted: a pass over the rows first checks, against the coefficients the matrix holds now, that the column
+// of every non-zero entry stands earlier in the order than its row, and the sweep is launched only where no row fails -- a row
+// then waits only for positions of its own or an earlier chunk, whose workgroups are running or done.
+struct ffm_flow_order {
+    ffm_ctx *ctx = nullptr;
+    int N = 0, nLevels = 0;
+    int *order = nullptr;          // [N] device: position -> internal cell
+};
+
+struct OrderedArgs {
+    LduView v;
+    int N, nap;
+    const int *order;
+    const double *upper, *lower, *diag, *source;
+    double *psi, *mf;
+    unsigned int *ticket;
+};
+
+__global__ void k_order_pos(long n, const int *__restrict__ order, int *__restrict__ pos)
+{ GRID_STRIDE(p, n) pos[order[p]] = (int)p; }
+
+// rows with a non-zero entry whose column does not stand earlier in the order: block partial counts
+template <int W>
+__global__ __launch_bounds__(256) void k_order_check(LduView v, const double *__restrict__ upper, const double *__restrict__ lower,
+                                                     const int *__restrict__ pos, double *__restrict__ partials)
+{
+    __shared__ double sm[4];
+    double bad = 0.0;
+    GRID_STRIDE(i, (long)v.N) {
+        const int c = (int)i;
+        RowEnt<W> L, U; load_lower<W>(v, c, L); load_upper<W>(v, c, U);
+        const int pc = pos[c];
+#pragma unroll
+        for (int s = 0; s < W; s++) {
+            if (L.on[s] && lower[L.f[s]] != 0.0 && !(pos[L.nb[s]] < pc)) bad += 1.0;
+            if (U.on[s] && upper[U.f[s]] != 0.0 && !(pos[U.nb[s]] < pc)) bad += 1.0;
+        }
+    }
+    const double r = block_sum(bad, sm);
+    if (threadIdx.x == 0) partials[blockIdx.x] = r;
+}
+
+template <int W>
+__global__ __launch_bounds__(FLOW_T) void k_flow_ordered(OrderedArgs a)
+{
+    __shared__ unsigned shTicket;
+    if (threadIdx.x == 0) shTicket = atomicAdd(&a.ticket[0], 1u);
+    __syncthreads();
+    const int p = (int)shTicket * FLOW_T + threadIdx.x;
+    if (p >= a.N) return;
+    const int c = a.order[p];
+    unsigned spins = 0;
+    RowEnt<W> L, U; load_lower<W>(a.v, c, L); load_upper<W>(a.v, c, U);
+    double al[W], au[W], pl[W], pu[W];
+#pragma unroll
+    for (int s = 0; s < W; s++) {
+        al[s] = a.lower[L.f[s]]; au[s] = a.upper[U.f[s]];
+        L.on[s] = L.on[s] && al[s] != 0.0; U.on[s] = U.on[s] && au[s] != 0.0;      // a zero entry is no dependency: not waited for
+        pl[s] = 0.0; pu[s] = 0.0;
+    }
+    const double bc = a.source[c], dg = a.diag[c];
+    bool done = false; do { if (!done) {
+        bool ready = true;
+#pragma unroll
+        for (int s = 0; s < W; s++) {
+            if (L.on[s]) { pl[s] = s_ld(&a.mf[L.nb[s]]); ready = ready && !f_pending(pl[s]); }
+            if (U.on[s]) { pu[s] = s_ld(&a.mf[U.nb[s]]); ready = ready && !f_pending(pu[s]); }
+        }
+        if (ready) {
+            double val = bc;
+#pragma unroll
+            for (int s = 0; s < W; s++) if (L.on[s]) val -= al[s] * pl[s];
+#pragma unroll
+            for (int s = 0; s < W; s++) if (U.on[s]) val -= au[s] * pu[s];
+            val /= dg;
+            a.psi[c] = val;
+            f_st(&a.mf[c], val);
+            done = true;
+        } else done = f_give_up(spins, a.ticket, a.nap);
+    } } while (__ballot(!done) != 0ull);
+}
+
+static bool ordered_single_rank(const ffm_ldu *A)
+{ return A->nOwned == A->nCells && A->ifaces.empty() && A->ghNbrRank.empty(); }
+
+extern "C" int ffm_flow_order_create(ffm_ldu *A, ffm_flow_order **out)
+{
+    if (!A || !out) { ffm_set_error("ffm_flow_order_create: null argument"); return FFM_ERR_ARG; }
+    *out = nullptr;
+    if (!ordered_single_rank(A)) {
+        ffm_set_error("ffm_flow_order_create: single rank only (the matrix has ghost cells, processor interfaces or a ghost exchange)");
+        return FFM_ERR_UNSUPPORTED;
+    }
+    FFM_HIP(hipSetDevice(A->ctx->device));
+    const int N = A->nOwned, nS = A->nSlices, T = A->upTotal;
+    // the off-diagonals the matrix holds, once, as the faces of the internal numbering in the caller's face order of every row
+    std::vector<int> upOff((size_t)nS + 1, 0), upNbr((size_t)T);
+    std::vector<double> up((size_t)T), lo((size_t)T);
+    FFM_TRY(ffm_d2h(A->ctx, upOff.data(), A->upOff, sizeof(int) * ((size_t)nS + 1)));
+    FFM_TRY(ffm_d2h(A->ctx, upNbr.data(), A->upNbr, sizeof(int) * (size_t)T));
+    FFM_TRY(ffm_d2h(A->ctx, up.data(), A->upper, sizeof(double) * (size_t)T));
+    if (A->lower != A->upper) FFM_TRY(ffm_d2h(A->ctx, lo.data(), A->lower, sizeof(double) * (size_t)T)); else lo = up;
+    std::vector<int> l, u; std::vector<double> cu, cl;
+    l.reserve(A->nFaces); u.reserve(A->nFaces); cu.reserve(A->nFaces); cl.reserve(A->nFaces);
+    for (int sl = 0; sl < nS; sl++) {
+        const int base = upOff[sl], w = (upOff[sl + 1] - base) >> 6;
+        for (int lane = 0; lane < 64; lane++) for (int s = 0; s < w; s++) {
+            const int e = base + s * 64 + lane, n = upNbr[e];
+            if (n < 0) continue;
+            l.push_back(sl * 64 + lane); u.push_back(n); cu.push_back(up[e]); cl.push_back(lo[e]);
+        }
+    }
+    std::vector<int> order((size_t)std::max(N, 1));
+    int nLev = 0;
+    FFM_TRY(ffm_flow_levels(N, (int)l.size(), l.data(), u.data(), cu.data(), cl.data(), order.data(), &nLev));
+    ffm_flow_order *o = new ffm_flow_order;
+    o->ctx = A->ctx; o->N = N; o->nLevels = nLev;
+    if (hipMalloc((void **)&o->order, sizeof(int) * (size_t)std::max(N, 1)) != hipSuccess) { delete o; ffm_set_error("ffm_flow_order_create: out of device memory"); return FFM_ERR_HIP; }
+    const int rc = ffm_h2d(A->ctx, o->order, order.data(), sizeof(int) * (size_t)N);
+    if (rc != FFM_OK) { hipFree(o->order); delete o; return rc; }
+    *out = o;
+    return FFM_OK;
+}
+extern "C" int ffm_flow_order_nlevels(const ffm_flow_order *o) { return o ? o->nLevels : FFM_ERR_ARG; }
+extern "C" int ffm_flow_order_destroy(ffm_flow_order *o)
+{
+    if (!o) return FFM_OK;
+    hipSetDevice(o->ctx->device);
+    hipStreamSynchronize(o->ctx->stream);
+    hipFree(o->order);
+    delete o;
+    return FFM_OK;
+}
+
+extern "C" int ffm_solve_ordered_d(ffm_ldu *A, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out)
+{
+    if (!A || !o || !psi_d || !source_d || !out) { ffm_set_error("ffm_solve_ordered_d: null argument"); return FFM_ERR_ARG; }
+    if (!ordered_single_rank(A)) {
+        ffm_set_error("ffm_solve_ordered_d: single rank only (the matrix has ghost cells, processor interfaces or a ghost exchange)");
+        return FFM_ERR_UNSUPPORTED;
+    }
+    if (o->ctx != A->ctx || o->N != A->nOwned) { ffm_set_error("ffm_solve_ordered_d: the order belongs to another matrix (%d cells, matrix %d)", o->N, A->nOwned); return FFM_ERR_UNSUPPORTED; }
+    memset(out, 0, sizeof(*out));
+    FFM_HIP(hipSetDevice(A->ctx->device));
+    ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned;
+    // ---- 1. the order against the coefficients the matrix holds now; nothing else is launched before the count is back
+    double *posBuf;
+    FFM_TRY(ffm_ldu_work(A, 23, &posBuf));
+    int *pos = (int *)posBuf;
+    const int g = sgrid(N);
+    hipLaunchKernelGGL(k_order_pos, dim3(g), dim3(256), 0, s, N, o->order, pos);
+    FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_order_check<W>, dim3(g), dim3(256), 0, s, ffm_view(A), A->upper, A->lower, pos, c->partials_d));
+    FFM_HIP(hipGetLastError());
+    FFM_TRY(partial_sum_to(c, g, S_TMP0));
+    FFM_TRY(ffm_read_scalars(c));
+    if (!(c->scal_h[S_TMP0] == 0.0)) {
+        ffm_set_error("ffm_solve_ordered_d: %.0f non-zero entries do not precede their rows in this order (a stale order, the order of "
+                      "another matrix, or a matrix that is not triangular): nothing solved", c->scal_h[S_TMP0]);
+        return FFM_ERR_UNSUPPORTED;
+    }
+    // ---- 2. the sweep, on the internal numbering
+    const double *si = source_d; double *pi = psi_d;
+    if (!A->identity) {
+        FFM_TRY(ffm_to_internal(A, source_d, 1, &si));
+        const double *pin; FFM_TRY(ffm_to_internal(A, psi_d, 2, &pin)); pi = A->permIn[2];
+    }
+    double *sumA, *Apsi, *rA;
+    FFM_TRY(ffm_ldu_work(A, 1, &sumA)); FFM_TRY(ffm_ldu_work(A, 2, &Apsi)); FFM_TRY(ffm_ldu_work(A, 3, &rA));
+    FFM_TRY(scalar_op(c, OP_RESET));
+    FFM_TRY(ffm_k_spmv_sumA_rows(A, pi, Apsi, sumA));
+    FFM_TRY(norm_and_initial(A, pi, si, Apsi, sumA, rA, out, nullptr, nullptr, true));
+    OrderedArgs a{};
+    a.v = ffm_view(A); a.N = A->nOwned; a.nap = 1; a.order = o->order;
+    a.upper = A->upper; a.lower = A->lower; a.diag = A->diag; a.source = si; a.psi = pi; a.ticket = A->sweepTicket;
+    FFM_TRY(ffm_ldu_work(A, 20, &a.mf));
+    hipLaunchKernelGGL(k_flow_fill, dim3(g), dim3(256), 0, s, N, a.mf, (double *)nullptr, (double *)nullptr, a.ticket);
+    const int nChunk = (A->nOwned + FLOW_T - 1) / FLOW_T;
+    if (nChunk > 0) FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_flow_ordered<W>, dim3(nChunk), dim3(FLOW_T), 0, s, a));
+    FFM_HIP(hipGetLastError());
+    // ---- 3. what the solve left
+    FFM_TRY(ffm_k_residual_rows(A, pi, si, rA));
+    FFM_TRY(ffm_k_summag(c, rA, N, S_TMP0));
+    FFM_TRY(scalar_op(c, OP_RES));
+    FFM_TRY(ffm_k_summag(c, si, N, S_TMP1));
+    if (!A->identity) FFM_TRY(ffm_from_internal(A, pi, psi_d));
+    FFM_TRY(ffm_read_scalars(c));
+    out->initialResidual = c->scal_h[S_RES0]; out->finalResidual = c->scal_h[S_RES];
+    out->nIterations = 1; out->singular = 0;
+    out->converged = (c->scal_h[S_TMP0] <= 1e-10 * c->scal_h[S_TMP1]) ? 1 : 0;      // (false for NaN too)
+    FFM_TRY(ffm_sweep_check_abort(A));
+    return FFM_OK;
+}
+
 // ------------------------------------------------------------------ several systems with common off-diagonals ---
 // fvMatrix::solveSegregated of a vector equation and the species loop under a multivariateSelection scheme solve systems that differ in
 // the diagonal and the right-hand side only.  PBiCGStab + DILU (or DIC) of nSys <= FFM_TILE_MAXSYS such systems run in lock step: every

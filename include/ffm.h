@@ -519,6 +519,33 @@ int ffm_ray_octant(const double *d3);
  * substitution was the solve (0: the matrix is not triangular in this order).  Vectors in the library's cell order.           */
 int ffm_solve_triangular_rows_d(ffm_ldu *ldu, double *psi_d, const double *source_d, ffm_perf *out);
 
+/* ------------------------------------------------------- flow-ordered exact solve (N1) */
+/* The dependency order of a matrix with at most one non-zero off-diagonal coefficient per face -- an upwind ray equation
+ * fvm::div(Ji, Ii) + fvm::Sp(k omega, Ii) (radiativeIntensityRay.C:267-322; `upwind`, or `linearUpwind`, whose implicit part is
+ * upwind) on any mesh.  Row upperAddr[f] needs cell lowerAddr[f] where lower[f] != 0, row lowerAddr[f] needs cell upperAddr[f]
+ * where upper[f] != 0; a face with two zeros is no edge.  order[nCells]: the cells level-major (level = longest dependency
+ * path, level 0 first, ascending cell index inside a level); under it the matrix is triangular.  Pure host code, O(cells +
+ * faces).  FFM_ERR_UNSUPPORTED (and a message) where the non-zero entries form a cycle; a face with two non-zero coefficients
+ * is one.                                                                                                                   */
+int ffm_flow_levels(int nCells, int nFaces, const int *lowerAddr, const int *upperAddr, const double *upper, const double *lower,
+                    int *order /* [nCells] */, int *nLevels);
+/* The same order of the coefficients the matrix holds now (set or bound), kept on the device: int[nCells], 4 nCells bytes per
+ * order.  Creating one downloads the off-diagonal coefficients once (set-up cost, like an agglomeration).  Single rank: a
+ * matrix with ghost cells, processor interfaces or a ghost exchange is refused (FFM_ERR_UNSUPPORTED), as is a cyclic one.   */
+typedef struct ffm_flow_order ffm_flow_order;
+int ffm_flow_order_create(ffm_ldu *ldu, ffm_flow_order **out);
+int ffm_flow_order_nlevels(const ffm_flow_order *o);
+int ffm_flow_order_destroy(ffm_flow_order *o);
+/* psi = A^-1 source as ONE forward substitution in that order: per row, source minus the lower faces' then the upper faces'
+ * terms in face order (zero coefficients skipped), one division -- bit for bit the serial loop, whatever the matrix's sweep
+ * mode.  Before anything else a pass over the rows checks the order against the coefficients the matrix holds NOW: if the
+ * column of some non-zero entry does not stand earlier than its row (a stale order, another matrix's order, a cycle) the call
+ * returns FFM_ERR_UNSUPPORTED and psi_d is untouched.  out: nIterations 1, OpenFOAM's normalised residuals of the start value
+ * and of the result; converged = 1 only where sum |source - A psi| <= 1e-10 sum |source| (the rule of
+ * ffm_solve_triangular_rows_d).  Vectors in the caller's cell numbering: where the library renumbered the cells
+ * (ffm_ldu_is_native_order() == 0) they go through the permutation the other solvers use.  Single rank only.              */
+int ffm_solve_ordered_d(ffm_ldu *ldu, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out);
+
 /* ------------------------------------------------------- synthetic plume case */
 /* Host-side driver (C++ over the entry points above) of one fireFoam time step on
  * the synthetic buoyant-plume box of SURVEY 8(d): rhoEqn, UEqn, YEEqn, 2 x pEqn in
