@@ -216,6 +216,10 @@ def lib():
         "ffm_ue_buoyancy_flux": ([vp, dp, dp, dp, dp], C.c_int),
         "ffm_pc_phiHbyA": ([vp, dp, dp, dp, dp, dp, dp, dp, dp], C.c_int),
         "ffm_pc_flux": ([vp, dp, dp, dp, dp, dp, dp, dp, dp, dp], C.c_int),
+        "ffm_pc_face_fluxes": ([vp] + [dp] * 10, C.c_int),
+        "ffm_pc_finish": ([vp, C.c_double, C.c_double] + [dp] * 9 + [C.POINTER(vp)] + [dp] * 4 + [C.POINTER(vp)] + [dp] * 4, C.c_int),
+        "ffm_ue_buoyancy_source3": ([vp, dp, dp, dp, dp, C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)], C.c_int),
+        "ffm_fvm_transport_scheme": ([vp, C.c_double, dp, dp, C.c_int, dp, C.c_int, dp, dp, dp], C.c_int),
         "ffm_fvc_div_dev2T_gradU": ([vp, C.POINTER(vp), dp, dp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)], C.c_int),
         "ffm_les_keqn_G": ([vp, C.POINTER(vp), dp, dp], C.c_int),
         "ffm_fvm_HbyA3": ([vp, dp, dp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(vp)], C.c_int),

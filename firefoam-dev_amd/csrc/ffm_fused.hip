@@ -916,6 +916,191 @@ extern "C" int ffm_pc_flux(ffm_mesh *m, const double *upper, const double *lower
     return FFM_OK;
 }
 
+// ---- passes that form a face field where it is used instead of writing it for the next kernel to read once ----------------------
+//   ffm_pc_face_fluxes       rhorAUf = interpolate(rho*rAU), phig, phiHbyA: k_interpolate + k_pc_phig + k_pc_phiHbyA in one owner-row
+//                            pass (all three stored: the matrix, the flux update and the second corrector read them)
+//   ffm_pc_finish            everything after the p_rgh solve on a single block, one pass over the cells: p_rghEqn.flux(), phi,
+//                            fvc::reconstruct of (flux + phig)/rhorAUf, U, K, p, dpdt and rhoEqn.H; no flux, t or reconstruct field
+//   ffm_ue_buoyancy_source3  UEqn's buoyancy term: k_ue_buoyancy_flux + k_reconstruct + k_add_boundary per component in one cell pass
+// A face value that both cells of a face need is formed by both from the same operands in the same roles (owner P, neighbour N), with
+// the expression of the kernel that used to store it: both get the same bits.
+__global__ __launch_bounds__(256) void k_pc_face_fluxes(MeshView q, const double *__restrict__ rhorAU, const double *__restrict__ ghf,
+                                                        const double *__restrict__ rho, const double *__restrict__ vx,
+                                                        const double *__restrict__ vy, const double *__restrict__ vz,
+                                                        const double *__restrict__ dc, double *__restrict__ rhorAUf,
+                                                        double *__restrict__ phig, double *__restrict__ phiHbyA)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci; const double aP = rhorAU[c], rP = rho[c]; const double Px = rP * vx[c], Py = rP * vy[c], Pz = rP * vz[c];
+        PC_ALL_SLOTS(q, c, e, nb) {
+            if (nb < 0) { rhorAUf[e] = 0.0; phig[e] = 0.0; phiHbyA[e] = 0.0; continue; }       // padding entries hold 0
+            const double w = q.w[e], rN = rho[nb];
+            const double rf = w * aP + (1.0 - w) * rhorAU[nb];                                  // k_interpolate, the mesh's weights
+            const double sg = q.delta[e] * (rN - rP), pg = -rf * ghf[e] * sg * q.magSf[e];      // k_pc_phig
+            const double fl = (w * Px + (1.0 - w) * (rN * vx[nb])) * q.Sfx[e] + (w * Py + (1.0 - w) * (rN * vy[nb])) * q.Sfy[e] + (w * Pz + (1.0 - w) * (rN * vz[nb])) * q.Sfz[e];
+            rhorAUf[e] = rf; phig[e] = pg;
+            phiHbyA[e] = (fl + rf * dc[e]) + pg;                                                // k_pc_phiHbyA
+        }
+    }
+}
+extern "C" int ffm_pc_face_fluxes(ffm_mesh *m, const double *rhorAU, const double *ghf, const double *rho, const double *vx, const double *vy,
+                                  const double *vz, const double *ddtCorr, double *rhorAUf, double *phig, double *phiHbyA)
+{
+    CHECK_M(m);
+    if (!rhorAU || !ghf || !rho || !vx || !vy || !vz || !ddtCorr || !rhorAUf || !phig || !phiHbyA) return FFM_ERR_ARG;
+    LAUNCH_CELLS(k_pc_face_fluxes, mview(m), rhorAU, ghf, rho, vx, vy, vz, ddtCorr, rhorAUf, phig, phiHbyA);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// the row walk of the two cell passes below: k_reconstruct's three sums over a face value t -- lower entries, owned entries, then (by
+// the caller) the patch faces
+struct RecSum { double x, y, z; };
+__device__ __forceinline__ void rec_add(const MeshView &q, int e, double t, RecSum &v)
+{
+    const double mg = q.magSf[e];
+    v.x += q.Sfx[e] / mg * t; v.y += q.Sfy[e] / mg * t; v.z += q.Sfz[e] / mg * t;
+}
+
+struct PcFinish {
+    const double *upper, *lower, *prgh, *phiHbyA, *phig, *rhorAUf, *phib, *tb, *rAU, *H[3], *gh, *p0, *rho0, *invT, *bMagSf;
+    double *phi, *U[3], *K, *p, *dpdt, *rho;
+    double rdt, pRef; long invStride;
+};
+template <int W>
+__global__ __launch_bounds__(256) void k_pc_finish(MeshView q, PcFinish a)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci; const long N = a.invStride;
+        RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
+        const double P = a.prgh[c];
+        RecSum v = {0.0, 0.0, 0.0};
+        double acc = 0.0, pe[W];
+#pragma unroll
+        for (int s = 0; s < W; s++) if (L.on[s]) {            // owner = L.nb[s], neighbour = c
+            const int e = L.f[s]; const double raf = a.rhorAUf[e];
+            const double f = a.upper[e] * P - a.lower[e] * a.prgh[L.nb[s]];
+            acc = acc - (a.phiHbyA[e] + f);
+            rec_add(q, e, raf != 0.0 ? (f + a.phig[e]) / raf : 0.0, v);
+        }
+#pragma unroll
+        for (int s = 0; s < W; s++) {
+            pe[s] = 0.0;
+            if (U.on[s]) {
+                const int e = U.f[s]; const double raf = a.rhorAUf[e];
+                const double f = a.upper[e] * a.prgh[U.nb[s]] - a.lower[e] * P;
+                pe[s] = a.phiHbyA[e] + f;
+                acc += pe[s];
+                rec_add(q, e, raf != 0.0 ? (f + a.phig[e]) / raf : 0.0, v);
+            }
+        }
+        const int j = q.cellB[c];
+        if (j >= 0) for (int t = q.bcStart[j]; t < q.bcStart[j + 1]; t++) {
+            const int k = q.bcItem[t]; const double b = a.tb[k], mg = a.bMagSf[k];
+            v.x += q.bSfx[k] / mg * b; v.y += q.bSfy[k] / mg * b; v.z += q.bSfz[k] / mg * b;
+            acc += a.phib[k];
+        }
+        const double xx = a.invT[c], xy = a.invT[N + c], xz = a.invT[2 * N + c], yy = a.invT[3 * N + c], yz = a.invT[4 * N + c], zz = a.invT[5 * N + c];
+        const double rx = xx * v.x + xy * v.y + xz * v.z, ry = xy * v.x + yy * v.y + yz * v.z, rz = xz * v.x + yz * v.y + zz * v.z;
+        const double r = a.rAU[c];
+        const double u0 = a.H[0][c] + r * rx, u1 = a.H[1][c] + r * ry, u2 = a.H[2][c] + r * rz;
+        a.U[0][c] = u0; a.U[1][c] = u1; a.U[2][c] = u2;
+        a.K[c] = 0.5 * ((u0 * u0 + u1 * u1) + u2 * u2);
+        const double pp = P + a.rho[c] * a.gh[c] + a.pRef;                       // (the density before rhoEqn.H)
+        a.p[c] = pp; a.dpdt[c] = a.rdt * (pp - a.p0[c]);
+        const double V = q.V[c], div = acc / V;
+        a.rho[c] = (a.rdt * a.rho0[c] * V - V * div) / (a.rdt * V);
+        // the owner stores phi for every slot of its slice row, 0 in the padding entries
+        const int sl = c >> 6, ub = up_base(q.v, sl) + (c & 63), uw = up_width(q.v, sl);
+#pragma unroll
+        for (int s = 0; s < W; s++) if (s < uw) a.phi[ub + s * 64] = pe[s];
+    }
+}
+extern "C" int ffm_pc_finish(ffm_mesh *m, double rDeltaT, double pRef, const double *upper, const double *lower, const double *p_rgh,
+                             const double *phiHbyA, const double *phig, const double *rhorAUf, const double *phi_b, const double *t_b,
+                             const double *rAU, const double *const *HbyA, const double *gh, const double *p0, const double *rho0,
+                             double *phi_f, double *const *U, double *K, double *p, double *dpdt, double *rho)
+{
+    CHECK_M(m);
+    if (!upper || !lower || !p_rgh || !phiHbyA || !phig || !rhorAUf || !rAU || !HbyA || !gh || !p0 || !rho0 || !phi_f || !U || !K || !p ||
+        !dpdt || !rho || rho == rho0 || (m->B && (!phi_b || !t_b))) return FFM_ERR_ARG;
+    PcFinish a;
+    for (int d = 0; d < 3; d++) { if (!HbyA[d] || !U[d]) return FFM_ERR_ARG; a.H[d] = HbyA[d]; a.U[d] = U[d]; }
+    a.upper = upper; a.lower = lower; a.prgh = p_rgh; a.phiHbyA = phiHbyA; a.phig = phig; a.rhorAUf = rhorAUf; a.phib = phi_b; a.tb = t_b;
+    a.rAU = rAU; a.gh = gh; a.p0 = p0; a.rho0 = rho0; a.invT = m->invT; a.bMagSf = m->bMagSf;
+    a.phi = phi_f; a.K = K; a.p = p; a.dpdt = dpdt; a.rho = rho; a.rdt = rDeltaT; a.pRef = pRef; a.invStride = m->N;
+    // rows wider than 8 entries would spill the per-face registers to scratch: the caller runs the passes this one replaces there
+    if (m->A->maxW > 8) return FFM_ERR_UNSUPPORTED;
+    if (m->A->maxW <= 3) LAUNCH_CELLS(k_pc_finish<3>, mview(m), a);
+    else if (m->A->maxW <= 4) LAUNCH_CELLS(k_pc_finish<4>, mview(m), a);
+    else LAUNCH_CELLS(k_pc_finish<8>, mview(m), a);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+struct UeBuoyancy {
+    const double *ghf, *rho, *prgh, *tb, *ic[3], *bc[3], *diag, *src[3], *invT, *bMagSf;
+    double *diagOut[3], *srcOut[3];
+    long invStride;
+};
+template <int W>
+__global__ __launch_bounds__(256) void k_ue_buoyancy_source3(MeshView q, UeBuoyancy a)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci; const long N = a.invStride;
+        RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
+        const double rC = a.rho[c], pC = a.prgh[c];
+        RecSum v = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < W; s++) if (L.on[s]) {            // owner = L.nb[s], neighbour = c
+            const int e = L.f[s], o = L.nb[s];
+            const double sgr = q.delta[e] * (rC - a.rho[o]), sgp = q.delta[e] * (pC - a.prgh[o]);
+            rec_add(q, e, (-a.ghf[e] * sgr - sgp) * q.magSf[e], v);
+        }
+#pragma unroll
+        for (int s = 0; s < W; s++) if (U.on[s]) {
+            const int e = U.f[s], n = U.nb[s];
+            const double sgr = q.delta[e] * (a.rho[n] - rC), sgp = q.delta[e] * (a.prgh[n] - pC);
+            rec_add(q, e, (-a.ghf[e] * sgr - sgp) * q.magSf[e], v);
+        }
+        double bd[3] = {0.0, 0.0, 0.0}, bs[3] = {0.0, 0.0, 0.0};
+        const double d0 = a.diag[c];
+#pragma unroll
+        for (int d = 0; d < 3; d++) { bd[d] = d0; bs[d] = a.src[d][c]; }
+        const int j = q.cellB[c];
+        if (j >= 0) for (int t = q.bcStart[j]; t < q.bcStart[j + 1]; t++) {
+            const int k = q.bcItem[t]; const double b = a.tb[k], mg = a.bMagSf[k];
+            v.x += q.bSfx[k] / mg * b; v.y += q.bSfy[k] / mg * b; v.z += q.bSfz[k] / mg * b;
+#pragma unroll
+            for (int d = 0; d < 3; d++) { bd[d] += a.ic[d][k]; bs[d] += a.bc[d][k]; }
+        }
+        const double xx = a.invT[c], xy = a.invT[N + c], xz = a.invT[2 * N + c], yy = a.invT[3 * N + c], yz = a.invT[4 * N + c], zz = a.invT[5 * N + c];
+        const double rec[3] = {xx * v.x + xy * v.y + xz * v.z, xy * v.x + yy * v.y + yz * v.z, xz * v.x + yz * v.y + zz * v.z};
+        const double V = q.V[c];
+#pragma unroll
+        for (int d = 0; d < 3; d++) { a.diagOut[d][c] = bd[d]; a.srcOut[d][c] = bs[d] + V * rec[d]; }
+    }
+}
+extern "C" int ffm_ue_buoyancy_source3(ffm_mesh *m, const double *ghf, const double *rho, const double *p_rgh, const double *t_b,
+                                       const double *const *ic, const double *const *bc, const double *diag, const double *const *source,
+                                       double *const *diagOut, double *const *sourceOut)
+{
+    CHECK_M(m);
+    if (!ghf || !rho || !p_rgh || !diag || !source || !diagOut || !sourceOut || (m->B && (!t_b || !ic || !bc))) return FFM_ERR_ARG;
+    UeBuoyancy a;
+    for (int d = 0; d < 3; d++) {
+        if (!source[d] || !diagOut[d] || !sourceOut[d] || (m->B && (!ic[d] || !bc[d]))) return FFM_ERR_ARG;
+        a.ic[d] = m->B ? ic[d] : nullptr; a.bc[d] = m->B ? bc[d] : nullptr; a.src[d] = source[d]; a.diagOut[d] = diagOut[d]; a.srcOut[d] = sourceOut[d];
+    }
+    a.ghf = ghf; a.rho = rho; a.prgh = p_rgh; a.tb = t_b; a.diag = diag; a.invT = m->invT; a.bMagSf = m->bMagSf; a.invStride = m->N;
+    if (m->A->maxW > 8) return FFM_ERR_UNSUPPORTED;             // (as ffm_pc_finish)
+    if (m->A->maxW <= 3) LAUNCH_CELLS(k_ue_buoyancy_source3<3>, mview(m), a);
+    else if (m->A->maxW <= 4) LAUNCH_CELLS(k_ue_buoyancy_source3<4>, mview(m), a);
+    else LAUNCH_CELLS(k_ue_buoyancy_source3<8>, mview(m), a);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
 // p_rghEqn of solver/pEqn.H:28-36 in one pass over the rows:
 //     fvm::ddt(psi, p_rgh) + fvc::ddt(psi, rho)*gh + fvc::ddt(psi)*pRef + fvc::div(phiHbyA) - fvm::laplacian(rhorAUf, p_rgh)
 // i.e. the laplacian coefficients (k_fvm_transport), fvc::div(phiHbyA) (k_face_sum), the three explicit terms (one source
@@ -939,7 +1124,8 @@ __global__ __launch_bounds__(256) void k_p_rgh_eqn(MeshView q, PEqn a)
             const int e = U.f[s];
             const double g = a.gamma[e] * q.magSf[e] * q.delta[e];
             dLap -= g;
-            a.upper[e] = -g; a.lower[e] = -g;
+            a.upper[e] = -g;
+            if (a.lower) a.lower[e] = -g;
         }
 #pragma unroll
         for (int s = 0; s < W; s++) if (L.on[s]) acc = acc - a.phiHbyA[L.f[s]];
@@ -965,7 +1151,8 @@ extern "C" int ffm_fvm_pressure_eqn(ffm_mesh *m, double rDeltaT, const double *p
                                     double *sourceOut)
 {
     CHECK_M(m);
-    if (!psi || !psi0 || !p0 || !rho || !rho0 || !gh || !gamma_f || !phiHbyA_f || !upper || !lower || !diagOut || !sourceOut ||
+    // lower == NULL: the matrix is symmetric (lower = upper) and the caller reads `upper` in both roles
+    if (!psi || !psi0 || !p0 || !rho || !rho0 || !gh || !gamma_f || !phiHbyA_f || !upper || !diagOut || !sourceOut ||
         (m->B && (!phiHbyA_b || !ic || !bc))) return FFM_ERR_ARG;
     PEqn a{psi, psi0, p0, rho, rho0, gh, gamma_f, phiHbyA_f, phiHbyA_b, ic, bc, upper, lower, diagOut, sourceOut, rDeltaT, pRef};
     FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_p_rgh_eqn<W>, mview(m), a));

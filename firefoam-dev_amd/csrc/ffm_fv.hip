@@ -483,9 +483,16 @@ __global__ void k_reconstruct(MeshView q, long invStride, const double *__restri
 // (any bracket may be absent: pass NULL).  Face coefficients are written by the owner row; the
 // diagonal applies negSumDiag per term in the reference's face order and then combines the terms
 // in the order ddt + div - laplacian, exactly as the reference's tmp<fvMatrix> algebra does.
-template <int W>
+// SCHEME: the convection weights are not read from wf but formed per face from phi and the mesh weight (k_limited_weights' expressions for
+// upwind 0, linear 1 and LUST 4: scheme_weight) -- by both cells of a face from the same operands, so both get the same bits
+__device__ __forceinline__ double scheme_weight(int scheme, double flux, double wlin)
+{
+    const double p0 = flux >= 0 ? 1.0 : 0.0;
+    return scheme == 0 ? p0 : scheme == 1 ? wlin : 0.75 * wlin + 0.25 * p0;
+}
+template <int W, bool SCHEME = false>
 __global__ void k_fvm_transport(MeshView q, double rDeltaT, const double *__restrict__ rho, const double *__restrict__ phi,
-                                const double *__restrict__ wf, const double *__restrict__ gamma, double lapSign,
+                                const double *__restrict__ wf, int scheme, const double *__restrict__ gamma, double lapSign,
                                 double *__restrict__ diag, double *__restrict__ upper, double *__restrict__ lower)
 {
     CELL_SCHED(ci, q) {
@@ -496,7 +503,7 @@ __global__ void k_fvm_transport(MeshView q, double rDeltaT, const double *__rest
 #pragma unroll
         for (int s = 0; s < W; s++) if (L.on[s]) {
             const int e = L.f[s];
-            if (phi) { const double f = phi[e]; const double lo = -wf[e] * f; dDiv -= (lo + f); }
+            if (phi) { const double f = phi[e]; const double lo = -(SCHEME ? scheme_weight(scheme, f, q.w[e]) : wf[e]) * f; dDiv -= (lo + f); }
             if (gamma) dLap -= gamma[e] * q.magSf[e] * q.delta[e];
         }
         // faces owned by c: write coefficients, diag -= lower[f]
@@ -504,7 +511,7 @@ __global__ void k_fvm_transport(MeshView q, double rDeltaT, const double *__rest
         for (int s = 0; s < W; s++) if (U.on[s]) {
             const int e = U.f[s];
             double lo = 0.0, up = 0.0;
-            if (phi) { const double f = phi[e]; lo = -wf[e] * f; up = lo + f; dDiv -= lo; }
+            if (phi) { const double f = phi[e]; lo = -(SCHEME ? scheme_weight(scheme, f, q.w[e]) : wf[e]) * f; up = lo + f; dDiv -= lo; }
             if (gamma) {
                 const double g = gamma[e] * q.magSf[e] * q.delta[e];
                 dLap -= g;
@@ -799,7 +806,17 @@ extern "C" int ffm_fvm_transport(ffm_mesh *m, double rDeltaT, const double *rho,
     CHECK_M(m);
     // upper == NULL: no face coefficients wanted (a pure ddt term has none); lower == NULL: a symmetric result (no convection), lower = upper
     if (!diag || ((phi_f || gamma_f) && !upper) || (phi_f && (!w_f || !lower))) return FFM_ERR_ARG;
-    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_fvm_transport<W>, mview(m), rDeltaT, rho, phi_f, w_f, gamma_f, (double)laplacianSign, diag, upper, lower));
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_fvm_transport<W>, mview(m), rDeltaT, rho, phi_f, w_f, 0, gamma_f, (double)laplacianSign, diag, upper, lower));
+    DONE();
+}
+// ffm_fvm_transport with the convection weights of a scheme that needs phi and the mesh weights only (0 upwind, 1 linear, 4 LUST: what
+// ffm_fv_limited_weights gives for them) formed where they are used: no weight field is written or read
+extern "C" int ffm_fvm_transport_scheme(ffm_mesh *m, double rDeltaT, const double *rho, const double *phi_f, int scheme,
+                                        const double *gamma_f, int laplacianSign, double *diag, double *upper, double *lower)
+{
+    CHECK_M(m);
+    if ((scheme != 0 && scheme != 1 && scheme != 4) || !phi_f || !diag || !upper || !lower) return FFM_ERR_ARG;
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_fvm_transport<W, true>), mview(m), rDeltaT, rho, phi_f, nullptr, scheme, gamma_f, (double)laplacianSign, diag, upper, lower));
     DONE();
 }
 extern "C" int ffm_fvm_boundary_coeffs(ffm_mesh *m, const double *phib, const double *gammab, int laplacianSign, const double *f,

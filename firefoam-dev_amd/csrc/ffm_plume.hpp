@@ -46,27 +46,29 @@ struct ffm_plume {
     double *fU[3], *refU[3], *fS, *refS, *fP, *refP, *gradP, *zeroB, *oneB;
     double *fStaticU[3], *fStaticS, *fStaticH, *fH, *refY[NSP], *refH;      // static templates (-1 = inletOutlet)
     // matrix + work
-    double *diag, *upper, *lower, *src[3], *ic[3], *bc[3], *dWork, *sWork;
+    double *diag, *upper, *lower, *src[3], *ic[3], *bc[3], *dWork, *sWork;       // (the fused p_rghEqn is symmetric and writes no `lower`)
     double *UdW[3], *UsW[3];               // diagonal + source of the three components (one lock-step solve)
     // Scratch: cell [N], face [nNat] and patch-face [B] fields.  A stage names the slots it uses in one block at its head; a value that
     // lives from one stage into a later one has a member of its own (next line).  `->`: must survive calls into other stages / the library.
+    // (ops): the per-operator form only (FFM_PLUME_UNFUSED); (ops, blocks): that form and the fused one on a decomposed box -- the fused
+    // single-block step forms the value where it is used and leaves the slot alone.
     //   wN[0]    hydrostatic_init, rho_eqn_ops: div | e_eqn: ddtK -> | p_corrector: rAU -> (read for the last time before pc_flux_U's rho_eqn)
     //   wN[1-3]  u_source_ops, scalar_transport, mv_weights_ops, e_K_terms: a gradient | p_corrector: rhorAU, HbyA[0-1] ->
     //   wN[4]    u_source_ops: divc | e_eqn: divK -> (scalar_transport reads it before it writes its source sum here) | p_corrector: HbyA[2] ->
-    //   wN[5-7]  u_eqn, pc_flux_U: reconstruct(...) -> | e_eqn: [5] -dpdt -> | pc_phig_flux_ops: rho*HbyA
+    //   wN[5-7]  u_eqn (ops), pc_flux_U (ops, blocks): reconstruct(...) -> | e_eqn: [5] -dpdt -> | pc_phig_flux_ops: rho*HbyA
     //   wN[8-10] wFuel, Qdot, Yt: standin_combustion -> species_eqns, radiation_correct, e_eqn | pc_ddtCorr_ops: rho0*U0 | pc_p_rgh_eqn_ops: [8] div
     //   wN[11]   species_eqns_ops: nu_i*wFuel
     //   wF[0]    hydrostatic_init: rhof | u_eqn: muf | alphaEff_f: standin_combustion -> species_eqns, e_eqn | p_corrector: rhorAUf ->
     //   wF[1]    hydrostatic_init, u_buoyancy, pc_phig_flux_ops: snGrad(rho) | mv_weights_ops: limiter
     //   wF[2]    hydrostatic_init: phig | u_buoyancy: snGrad(p_rgh) | p_corrector: phig ->
-    //   wF[3]    u_eqn: LUST weights -> | scalar_transport, e_K_terms_ops: a field's own weights | p_corrector: phiHbyA ->
-    //   wF[4]    u_buoyancy: reconstruct's argument, then u_source_ops: phi*correction | e_K_terms_ops: phi*Kf | pc_ddtCorr_ops: flux(rho0*U0),
-    //            then p_corrector: p_rghEqn.flux() ->      wF[5]  pc_flux_U: reconstruct's argument
+    //   wF[3]    u_eqn (ops): LUST weights -> | scalar_transport, e_K_terms_ops: a field's own weights | p_corrector: phiHbyA ->
+    //   wF[4]    u_buoyancy (ops): reconstruct's argument, then u_source_ops: phi*correction | e_K_terms_ops: phi*Kf | pc_ddtCorr_ops: flux(rho0*U0),
+    //            then p_corrector (ops, blocks): p_rghEqn.flux() ->      wF[5]  pc_flux_U (ops, blocks): reconstruct's argument
     //   wB[0]    hydrostatic_init: rhob | e_K_terms: Kb, then (after Kb's last reader) plume_rad_fraction: burner flux | p_corrector: rhorAUfb ->
     //   wB[1-3]  Ub: U_boundary -> the end of the stage that called it (u_eqn, e_K_terms, p_corrector); in between hydrostatic_init: [1] fTop |
     //            mv_weights: [1] inert specie's, [3] h's patch values | scalar_transport: [2] patch values
     //   wB[4]    u_eqn: mub -> | alphaEff_b: standin_combustion -> species_eqns, e_eqn | p_corrector: rhob ->
-    //   wB[5]    u_buoyancy: reconstruct's argument | e_K_terms_ops: phib*Kb | p_corrector: phiHbyAb ->
+    //   wB[5]    u_buoyancy: reconstruct's argument -> u_eqn's source pass (after u_sources) | e_K_terms_ops: phib*Kb | p_corrector: phiHbyAb ->
     //   wB[6]    u_buoyancy: rhob | pc_p_rgh_eqn: constrainPressure gradient (until bc_p_rgh), then pc_flux_U: reconstruct's argument
     //   wB[7]    u_buoyancy: p_rgh patch values | p_corrector: p_rghEqn.flux() on the patches
     double *wN[12], *wF[6], *wB[8];

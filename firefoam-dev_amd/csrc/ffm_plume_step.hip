@@ -71,7 +71,9 @@ static int rho_eqn(ffm_plume *P)
 }
 
 // ---------------- UEqn.H
-// rec = reconstruct((-ghf*snGrad(rho) - snGrad(p_rgh))*magSf); the per-operator form's three launches stand between the patch kernels
+// rec = reconstruct((-ghf*snGrad(rho) - snGrad(p_rgh))*magSf); the per-operator form's three launches stand between the patch kernels.
+// The fused form stops at the patch part tb: u_eqn forms the face flux, reconstructs it and adds it to the sources in one cell pass
+// (ffm_ue_buoyancy_source3), after u_sources
 static int u_buoyancy(ffm_plume *P, double *const rec[3])
 {
     ffm_mesh *m = P->mesh; const bool ops = !P->fused;
@@ -84,9 +86,8 @@ static int u_buoyancy(ffm_plume *P, double *const rec[3])
     if (ops) FFM_TRY(ffm_fvc_snGrad(m, P->p_rgh, sgp));
     FFM_TRY(ffm_fvc_snGrad_b(m, P->p_rgh, pb, tb));
     if (ops) forN(P, P->nNat, [=] __device__(long e) { t[e] = (-ghf[e] * sgr[e] - sgp[e]) * magSf[e]; });
-    else FFM_TRY(ffm_ue_buoyancy_flux(m, ghf, P->rho, P->p_rgh, t));
     forN(P, P->B, [=] __device__(long k) { tb[k] = -tb[k] * bMag[k]; });
-    return ffm_fvc_reconstruct(m, t, tb, rec[0], rec[1], rec[2]);
+    return ops ? ffm_fvc_reconstruct(m, t, tb, rec[0], rec[1], rec[2]) : FFM_OK;
 }
 
 // ddt + the explicit LUST correction of component c, one operator per launch: gaussConvectionScheme::fvmDiv with a corrected() scheme,
@@ -123,21 +124,26 @@ static int u_sources(ffm_plume *P, const double *mub)
 
 static int u_eqn(ffm_plume *P)
 {
-    ffm_mesh *m = P->mesh; const int N = P->N;
+    ffm_mesh *m = P->mesh; const int N = P->N; const bool ops = !P->fused;
     double *wU = P->wF[3], *muf = P->wF[0], *mub = P->wB[4], *rec[3] = {P->wN[5], P->wN[6], P->wN[7]};
     FFM_TRY(update_bcs(P));
     FFM_TRY(U_boundary(P));
-    // div(phi,U) Gauss LUST grad(U) (cases/steckler/system/fvSchemes:32): LUST weights for the implicit part; the explicit
-    // correction goes into the source (u_sources)
-    FFM_TRY(ffm_fv_limited_weights(m, 4, 1.0, 0.0, 1.0, P->phi, nullptr, nullptr, nullptr, nullptr, wU));
+    // div(phi,U) Gauss LUST grad(U) (cases/steckler/system/fvSchemes:32): LUST weights for the implicit part -- a function of phi and the
+    // mesh weights alone, formed inside the assembly pass by the fused form; the explicit correction goes into the source (u_sources)
+    if (ops) FFM_TRY(ffm_fv_limited_weights(m, 4, 1.0, 0.0, 1.0, P->phi, nullptr, nullptr, nullptr, nullptr, wU));
     forN(P, P->nNat, [=] __device__(long e) { muf[e] = MU; });
     forN(P, P->B, [=] __device__(long k) { mub[k] = MU; });
-    FFM_TRY(ffm_fvm_transport(m, P->rdt, P->rho, P->phi, wU, muf, -1, P->Udiag, P->Uupper, P->Ulower));
+    if (ops) FFM_TRY(ffm_fvm_transport(m, P->rdt, P->rho, P->phi, wU, muf, -1, P->Udiag, P->Uupper, P->Ulower));
+    else FFM_TRY(ffm_fvm_transport_scheme(m, P->rdt, P->rho, P->phi, 4, muf, -1, P->Udiag, P->Uupper, P->Ulower));
     FFM_TRY(u_buoyancy(P, rec));
     FFM_TRY(u_sources(P, mub));
-    // fvMatrix::solveSegregated: the three components share the face coefficients -- one lock-step solve (ffm_solve_multi_d)
+    // fvMatrix::solveSegregated: the three components share the face coefficients -- one lock-step solve (ffm_solve_multi_d).
+    // UdW = Udiag + sum ic, UsW = Usrc + sum bc + V*rec; Usrc, Uic and Ubc stay as they are for the correctors.  The fused form: one
+    // cell pass from rho, p_rgh and u_buoyancy's patch part, no face flux and no rec (a hex block's rows have at most 6 entries, see
+    // rho_eqn: no FFM_ERR_UNSUPPORTED from it here)
     const char *nm[3] = {"Ux", "Uy", "Uz"};
-    for (int c = 0; c < 3; c++) FFM_TRY(ffm_fvm_add_boundary(m, P->Uic[c], P->Ubc[c], P->Udiag, P->Usrc[c], rec[c], P->UdW[c], P->UsW[c]));
+    if (ops) { for (int c = 0; c < 3; c++) FFM_TRY(ffm_fvm_add_boundary(m, P->Uic[c], P->Ubc[c], P->Udiag, P->Usrc[c], rec[c], P->UdW[c], P->UsW[c])); }
+    else FFM_TRY(ffm_ue_buoyancy_source3(m, P->ghf, P->rho, P->p_rgh, P->wB[5], P->Uic, P->Ubc, P->Udiag, P->Usrc, P->UdW, P->UsW));
     FFM_TRY(solve_named_multi(P, 3, nm, 1e-6, P->UdW, P->Uupper, P->Ulower, P->U, P->UsW));
     for (int c = 0; c < 3; c++) FFM_TRY(HX(P, P->U[c]));
     double *K = P->K; const double *U0 = P->U[0], *U1 = P->U[1], *U2 = P->U[2];
@@ -428,13 +434,13 @@ static int pc_HbyA_ops(ffm_plume *P, const PCorr &w)
     return FFM_OK;
 }
 // rho = thermo.rho(); rAU = 1/UEqn.A(); rhorAUf = interpolate(rho*rAU); HbyA = rAU*UEqn.H().  On a single block (no ghost refresh of rAU
-// in between) the first three are one pass, inside that of UEqn.A()
+// in between) the first three are one pass, inside that of UEqn.A().  The fused form leaves rhorAUf to pc_phiHbyA's face pass
 static int pc_rAU_HbyA(ffm_plume *P, const PCorr &w)
 {
     ffm_mesh *m = P->mesh; const bool ops = !P->fused;
     if (ops || !P->oneBlock) FFM_TRY(pc_rAU_ops(P, w));
     else FFM_TRY(ffm_fvm_rAU(m, 3, P->Udiag, P->Uic[0], P->Uic[1], P->Uic[2], P->psi, P->p, P->rho, w.rAU, w.rhorAU));
-    FFM_TRY(ffm_fvc_interpolate(m, nullptr, w.rhorAU, w.rhorAUf));
+    if (ops) FFM_TRY(ffm_fvc_interpolate(m, nullptr, w.rhorAU, w.rhorAUf));
     zg(P, w.rhorAUfb, w.rhorAU);
     if (ops) return pc_HbyA_ops(P, w);
     FFM_TRY(ffm_fvm_HbyA3(m, P->Uupper, P->Ulower, P->Usrc, P->Uic, P->Ubc, P->U, w.rAU, w.HbyA));
@@ -473,12 +479,12 @@ static int pc_ddtCorr_ops(ffm_plume *P, const PCorr &w, bool evalDdtCorr)
 }
 // phig = -rhorAUf*ghf*snGrad(rho)*magSf; phiHbyA = fvc::flux(rho*HbyA) + rhorAUf*fvc::ddtCorr(rho, U, phi) + phig: interior by linear interpolation; boundary
 // rho_b*HbyA_b.Sf with constrainHbyA.  ddtCorr reads old-time fields only: evaluated in the first corrector of a step, while phi
-// still holds the old-time flux (pc_flux overwrites it), and reused by the second.
+// still holds the old-time flux (pc_flux overwrites it), and reused by the second.  The fused form: rhorAUf, phig and phiHbyA of the
+// internal faces in one owner-row pass (ffm_pc_face_fluxes), after the patch part
 static int pc_phiHbyA(ffm_plume *P, const PCorr &w)
 {
     ffm_mesh *m = P->mesh; const bool ops = !P->fused;
     if (ops) FFM_TRY(pc_phig_flux_ops(P, w));
-    else FFM_TRY(ffm_pc_phig(m, w.rhorAUf, P->ghf, P->rho, w.phig));
     {
         const double *bSx = ffm_mesh_geom(m, 6), *bSy = ffm_mesh_geom(m, 7), *bSz = ffm_mesh_geom(m, 8);
         const int *fc = ffm_mesh_bcells(m); const double *kind = P->kind_d, *rhob = w.rhob; double *phiHbyAb = w.phiHbyAb;
@@ -493,7 +499,7 @@ static int pc_phiHbyA(ffm_plume *P, const PCorr &w)
     P->ddtCorrValid = true;
     if (ops) return pc_ddtCorr_ops(P, w, evalDdtCorr);
     if (evalDdtCorr) FFM_TRY(ffm_fvc_ddt_corr(m, P->rdt, P->rho0, P->U0[0], P->U0[1], P->U0[2], P->phi, P->ddtCorrF));
-    return ffm_pc_phiHbyA(m, P->rho, w.HbyA[0], w.HbyA[1], w.HbyA[2], w.rhorAUf, P->ddtCorrF, w.phig, w.phiHbyA);
+    return ffm_pc_face_fluxes(m, w.rhorAU, P->ghf, P->rho, w.HbyA[0], w.HbyA[1], w.HbyA[2], P->ddtCorrF, w.rhorAUf, w.phig, w.phiHbyA);
 }
 
 static int pc_p_rgh_eqn_ops(ffm_plume *P, const PCorr &w)
@@ -526,40 +532,39 @@ static int pc_p_rgh_eqn(ffm_plume *P, const PCorr &w, bool final)
     FFM_TRY(bc_p_rgh(P, grads, w.rhob));
     if (ops) FFM_TRY(ffm_fvm_transport(m, P->rdt, P->psi, nullptr, nullptr, w.rhorAUf, -1, P->diag, P->upper, P->lower));
     FFM_TRY(ffm_fvm_boundary_coeffs(m, nullptr, w.rhorAUfb, -1, P->fP, P->refP, P->gradP, P->ic[0], P->bc[0]));
+    // (the fused form writes no `lower`: the matrix is symmetric, the solve and pc_flux_U read `upper` in both roles)
     FFM_TRY(!ops ? ffm_fvm_pressure_eqn(m, P->rdt, P->psi, P->psi0, P->p_rgh0, P->rho, P->rho0, P->gh, PREF, w.rhorAUf, w.phiHbyA, w.phiHbyAb,
-                                            P->ic[0], P->bc[0], P->upper, P->lower, P->dWork, P->sWork)
+                                            P->ic[0], P->bc[0], P->upper, nullptr, P->dWork, P->sWork)
                      : pc_p_rgh_eqn_ops(P, w));
     FFM_TRY(solve_named(P, "p_rgh", FFM_PCG, FFM_DIC, 1e-6, final ? 0.0 : 0.01, P->dWork, P->upper, nullptr, P->p_rgh, P->sWork));
     return HX(P, P->p_rgh);
 }
 
 // phi = phiHbyA + p_rghEqn.flux(); U = HbyA + rAU*reconstruct((p_rghEqn.flux() + phig)/rhorAUf), K = 0.5 magSqr(U), p = p_rgh + rho*gh + pRef,
-// dpdt = fvc::ddt(p), and rhoEqn.H after p.  On a single block U, K, p and dpdt are one pass over the cells (rhoEqn.H, solver/pEqn.H:46-48,
-// reads none of them); the per-operator form refreshes U's ghost cells and takes K and dpdt after rhoEqn.H
+// dpdt = fvc::ddt(p), and rhoEqn.H after p.  On a single block the fused form is one pass over the cells after the patch part
+// (ffm_pc_finish: the flux, phi, reconstruct, U, K, p, dpdt and rhoEqn.H, which reads none of them; no flux, t or rec field; a hex
+// block's rows have at most 6 entries, see rho_eqn); on a decomposed block U's ghost cells are refreshed before K.  The per-operator
+// form takes K and dpdt after rhoEqn.H
 static int pc_flux_U(ffm_plume *P, const PCorr &w)
 {
     ffm_mesh *m = P->mesh; const int N = P->N; const double rdt = P->rdt; const bool ops = !P->fused;
     double *t = P->wF[5], *tb = P->wB[6];
     double *phi = P->phi, *phib = P->phib; const double *phiHbyA = w.phiHbyA, *fl = w.fl, *phig = w.phig, *rhorAUf = w.rhorAUf;
     const double *phiHbyAb = w.phiHbyAb, *flb = w.flb, *rhorAUfb = w.rhorAUfb;
-    FFM_TRY(ffm_fvm_flux(m, P->upper, P->lower, P->ic[0], P->bc[0], P->p_rgh, ops ? w.fl : nullptr, w.flb));
+    const double *lower = ops ? P->lower : P->upper;
+    FFM_TRY(ffm_fvm_flux(m, P->upper, lower, P->ic[0], P->bc[0], P->p_rgh, ops ? w.fl : nullptr, w.flb));
+    if (!ops && P->oneBlock) {
+        forN(P, P->B, [=] __device__(long k) { phib[k] = phiHbyAb[k] + flb[k]; tb[k] = flb[k] / rhorAUfb[k]; });
+        return ffm_pc_finish(m, rdt, PREF, P->upper, lower, P->p_rgh, phiHbyA, phig, rhorAUf, phib, tb, w.rAU, w.HbyA, P->gh, P->p0, P->rho0,
+                             phi, P->U, P->K, P->p, P->dpdt, P->rho);
+    }
     if (ops) forN(P, P->nNat, [=] __device__(long e) { phi[e] = phiHbyA[e] + fl[e]; t[e] = rhorAUf[e] != 0.0 ? (fl[e] + phig[e]) / rhorAUf[e] : 0.0; });
-    else FFM_TRY(ffm_pc_flux(m, P->upper, P->lower, P->p_rgh, phiHbyA, phig, rhorAUf, w.fl, phi, t));
+    else FFM_TRY(ffm_pc_flux(m, P->upper, lower, P->p_rgh, phiHbyA, phig, rhorAUf, w.fl, phi, t));
     forN(P, P->B, [=] __device__(long k) { phib[k] = phiHbyAb[k] + flb[k]; tb[k] = flb[k] / rhorAUfb[k]; });
     FFM_TRY(ffm_fvc_reconstruct(m, t, tb, w.rec[0], w.rec[1], w.rec[2]));
     const double *rAU = w.rAU, *rx = w.rec[0], *ry = w.rec[1], *rz = w.rec[2], *h0 = w.HbyA[0], *h1 = w.HbyA[1], *h2 = w.HbyA[2];
     double *U0 = P->U[0], *U1 = P->U[1], *U2 = P->U[2], *K = P->K, *dpdt = P->dpdt, *p = P->p;
     const double *rho = P->rho, *p_rgh = P->p_rgh, *gh = P->gh, *p0 = P->p0;
-    if (!ops && P->oneBlock) {
-        forN(P, N, [=] __device__(long i) {
-            const double a = h0[i] + rAU[i] * rx[i], b = h1[i] + rAU[i] * ry[i], c = h2[i] + rAU[i] * rz[i];
-            U0[i] = a; U1[i] = b; U2[i] = c;
-            K[i] = 0.5 * ((a * a + b * b) + c * c);
-            const double pp = p_rgh[i] + rho[i] * gh[i] + PREF;
-            p[i] = pp; dpdt[i] = rdt * (pp - p0[i]);
-        });
-        return rho_eqn(P);
-    }
     forN(P, P->nOwn, [=] __device__(long i) {
         const double a = h0[i] + rAU[i] * rx[i], b = h1[i] + rAU[i] * ry[i], c = h2[i] + rAU[i] * rz[i];
         U0[i] = a; U1[i] = b; U2[i] = c;

@@ -355,6 +355,11 @@ int ffm_fv_linear_upwind_correction(ffm_mesh *m, const double *phi_f, const doub
 int ffm_fvm_transport(ffm_mesh *m, double rDeltaT, const double *rho,
                       const double *phi_f, const double *w_f, const double *gamma_f,
                       int laplacianSign, double *diag, double *upper, double *lower);
+/* the same with the convection weights of a scheme that needs only phi and the mesh's linear weights formed where they are used, no
+ * weight field: scheme 0 upwind, 1 linear, 4 LUST (any other: FFM_ERR_ARG).  Bitwise equal to ffm_fv_limited_weights(scheme) +
+ * ffm_fvm_transport. */
+int ffm_fvm_transport_scheme(ffm_mesh *m, double rDeltaT, const double *rho, const double *phi_f, int scheme,
+                             const double *gamma_f, int laplacianSign, double *diag, double *upper, double *lower);
 /* internalCoeffs / boundaryCoeffs of the same terms for a patch field in
  * `mixed` form (valueFraction f, refValue, refGradient); fixedValue,
  * zeroGradient, fixedGradient, inletOutlet are special cases               */
@@ -389,7 +394,8 @@ int ffm_fvm_HbyA3(ffm_mesh *m, const double *upper, const double *lower, const d
 /* p_rghEqn of solver/pEqn.H:28-36 in one pass: fvm::ddt(psi, p_rgh) + fvc::ddt(psi, rho)*gh + fvc::ddt(psi)*pRef +
  * fvc::div(phiHbyA) - fvm::laplacian(gamma, p_rgh) with its boundary coefficients (internalCoeffs / boundaryCoeffs from
  * ffm_fvm_boundary_coeffs) already added: upper / lower [native faces], diagOut / sourceOut [cells] are what the solver takes.
- * Bitwise equal to ffm_fvm_transport + ffm_fvc_surface_integrate + the three source updates + ffm_fvm_add_boundary. */
+ * Bitwise equal to ffm_fvm_transport + ffm_fvc_surface_integrate + the three source updates + ffm_fvm_add_boundary.
+ * lower may be NULL: the matrix is symmetric (lower = upper), and a caller that reads `upper` in both roles needs no second array. */
 int ffm_fvm_pressure_eqn(ffm_mesh *m, double rDeltaT, const double *psi, const double *psi0, const double *p0,
                          const double *rho, const double *rho0, const double *gh, double pRef, const double *gamma_f,
                          const double *phiHbyA_f, const double *phiHbyA_b, const double *internalCoeffs,
@@ -404,6 +410,25 @@ int ffm_pc_flux(ffm_mesh *m, const double *upper, const double *lower, const dou
                 const double *rhorAUf, double *flux_f, double *phi_f, double *t_f);
 /* solver/UEqn.H:23-29: the face flux of fvc::reconstruct, t = (-ghf*fvc::snGrad(rho) - fvc::snGrad(p_rgh))*magSf, in one pass */
 int ffm_ue_buoyancy_flux(ffm_mesh *m, const double *ghf, const double *rho, const double *p_rgh, double *t_f);
+/* Passes that form a face field where it is used instead of storing it for one reader; each bitwise equal to the chain it replaces.
+ * ffm_pc_face_fluxes: rhorAUf = ffm_fvc_interpolate(NULL, rhorAU), then ffm_pc_phig and ffm_pc_phiHbyA from it, in one owner-row pass;
+ *   all three are stored, padding entries of the native layout get 0.
+ * ffm_pc_finish (single block): everything after the p_rgh solve in one pass over the cells -- ffm_pc_flux (upper/lower/p_rgh ->
+ *   phi_f, stored by the owner, padding 0; the flux and t = (flux + phig)/rhorAUf are not stored), ffm_fvc_reconstruct of t with the
+ *   patch part t_b, U = HbyA + rAU*rec, K = 0.5 magSqr(U), p = p_rgh + rho*gh + pRef (the rho that comes in), dpdt = rDeltaT*(p - p0),
+ *   then ffm_fvc_rho_eqn from phi_f / phi_b and rho0 into rho.  HbyA, U: three device pointers.  upper and lower may be one array.
+ * ffm_ue_buoyancy_source3: ffm_ue_buoyancy_flux + ffm_fvc_reconstruct (patch part t_b) + ffm_fvm_add_boundary per component with the
+ *   reconstructed vector as the explicit source: diagOut_c = diag + sum ic_c, sourceOut_c = source_c + sum bc_c + V*rec_c.
+ * The two cell passes return FFM_ERR_UNSUPPORTED, nothing launched, on meshes with more than 8 lower or upper neighbours per cell. */
+int ffm_pc_face_fluxes(ffm_mesh *m, const double *rhorAU, const double *ghf, const double *rho, const double *vx, const double *vy,
+                       const double *vz, const double *ddtCorr, double *rhorAUf, double *phig, double *phiHbyA);
+int ffm_pc_finish(ffm_mesh *m, double rDeltaT, double pRef, const double *upper, const double *lower, const double *p_rgh,
+                  const double *phiHbyA, const double *phig, const double *rhorAUf, const double *phi_b, const double *t_b,
+                  const double *rAU, const double *const *HbyA, const double *gh, const double *p0, const double *rho0,
+                  double *phi_f, double *const *U, double *K, double *p, double *dpdt, double *rho);
+int ffm_ue_buoyancy_source3(ffm_mesh *m, const double *ghf, const double *rho, const double *p_rgh, const double *t_b,
+                            const double *const *internalCoeffs, const double *const *boundaryCoeffs, const double *diag,
+                            const double *const *source, double *const *diagOut, double *const *sourceOut);
 /* fvc::flux(rho*v) on the internal faces (solver/pEqn.H:15 fvc::flux(rho*HbyA); the old-time flux of fvc::ddtCorr) without
  * storing the product fields; bitwise equal to ffm_fvc_flux of the products */
 int ffm_fvc_flux_rho(ffm_mesh *m, const double *rho, const double *vx, const double *vy, const double *vz, double *out_f);
