@@ -1,25 +1,14 @@
 // ffm_internal.hpp -- private structures of libffm.so (not part of the C ABI).
 #pragma once
-#include <ctime>
-#include <cstdio>
-#include <cstdlib>
 #include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 #include <tuple>
-#include <vector>
-#include <thread>
-#include <algorithm>
 #include <unordered_map>
 
-#include "../../include/ffm.h"
+#include "ffm_host.hpp"          // ffm_set_error, FFM_TRY, ffm_parallel_for, the set-up timers, LduAnalysis / LduLayout
 
 struct ncclComm;
 struct ffm_tile_plan;
-
-void ffm_set_error(const char *fmt, ...);
 
 #define FFM_HIP(call)                                                            \
     do {                                                                         \
@@ -29,12 +18,6 @@ void ffm_set_error(const char *fmt, ...);
                           hipGetErrorString(e_));                                \
             return FFM_ERR_HIP;                                                  \
         }                                                                        \
-    } while (0)
-
-#define FFM_TRY(call)                                                            \
-    do {                                                                         \
-        int r_ = (call);                                                         \
-        if (r_ != FFM_OK) return r_;                                             \
     } while (0)
 
 // Fixed reduction geometry: every dot product is a two-stage, atomics-free,
@@ -120,18 +103,6 @@ template <class T, class Al> inline int ffm_upload_vec(ffm_ctx *c, T **d, const 
     return ffm_h2d(c, *d, v.data(), sizeof(T) * v.size());
 }
 #pragma GCC poison hipMemcpy hipMemset
-
-// Host set-up loops over cells / faces (renumbered addressing, geometry in the native layout, the reconstruction tensors): independent
-// iterations split over the host's cores (at most 16 threads; FFM_HOST_THREADS overrides; below 1M iterations: the caller's thread)
-template <class Fn> inline void ffm_parallel_for(long n, Fn fn, long serialBelow = 1L << 20)
-{
-    static const int nT = [] { const char *e = getenv("FFM_HOST_THREADS"); int t = e ? atoi(e) : (int)std::thread::hardware_concurrency(); return std::max(1, std::min(t, 16)); }();
-    if (n < serialBelow || nT == 1) { fn(0L, n); return; }
-    std::vector<std::thread> th;
-    const long chunk = (n + nT - 1) / nT;
-    for (int t = 0; t < nT; t++) { const long lo = t * chunk, hi = std::min(n, lo + chunk); if (lo < hi) th.emplace_back([=] { fn(lo, hi); }); }
-    for (auto &x : th) x.join();
-}
 
 // Host set-up arrays of many GB (geometry of a 400^3 box) whose elements are not value-initialised on allocation: they are filled
 // with ffm_parallel_for, so the first touch of their pages is spread over the host threads instead of falling on one
@@ -247,28 +218,6 @@ struct ffm_ldu {
     ffm_tile_plan *tile = nullptr;                // tiled wavefront plan (sweepMode == 2)
 };
 
-// FFM_TIMING=1: wall time of the host-side set-up stages to stderr
-struct FfmStageTimer {
-    const char *what; double t0; bool on;
-    static double now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
-    explicit FfmStageTimer(const char *w) : what(w), t0(now()), on(getenv("FFM_TIMING") != nullptr) {}
-    ~FfmStageTimer() { if (on) fprintf(stderr, "ffm timing: %-28s %.2f s\n", what, now() - t0); }
-};
-// the same in laps: lap("x") prints the time since the previous lap (FFM_TIMING=2)
-struct FfmLapTimer {
-    const char *what; double t0; bool on;
-    explicit FfmLapTimer(const char *w) : what(w), t0(FfmStageTimer::now()), on(getenv("FFM_TIMING") != nullptr && atoi(getenv("FFM_TIMING")) >= 2) {}
-    void lap(const char *stage) { if (!on) return; const double t = FfmStageTimer::now(); fprintf(stderr, "ffm timing:   %s: %-30s %.2f s\n", what, stage, t - t0); t0 = t; }
-};
-// edge of the 2-D tiles of cell columns, in cells: detected blockMesh boxes, the plume's group hint, ffm_tile_hint_from_centres
-constexpr int TILE_EDGE = 16;
-// label of the 2-D tile (a, b) of cell columns.  Ties between tiles that are ready at the same time are broken by label
-// (ffm_ldu.hip: topological ranking), so the label orders the tickets: anti-diagonal major = the order of the sweep's wavefront
-static inline int ffm_tile_label(int a, int b)
-{
-    a = a < 2047 ? a : 2047; b = b < 2047 ? b : 2047;
-    return (a + b) * 4096 + b;
-}
 struct LduView;
 LduView ffm_view(const ffm_ldu *A);
 const int *ffm_mesh_bcells(const ffm_mesh *m);                 // ffm_fv.hip: face cell of every boundary face (device)
@@ -292,7 +241,6 @@ void ffm_comm_finalize_i(ffm_ctx *ctx);
 int ffm_precond_setup_i(ffm_ldu *A, int precond);
 int ffm_precond_apply_i(ffm_ldu *A, int precond, bool transpose, const double *r, double *w);
 int ffm_tile_build(ffm_ldu *A, const std::vector<int> &lev, const std::vector<int> &bl, const std::vector<int> &grpCell);
-bool ffm_tile_feasible(int nOwn, int F, const int *l, const int *u);
 int ffm_tile_calc_rD(ffm_ldu *A);
 int ffm_sweep_check_abort(ffm_ldu *A);                   // abort word of the tiled and the dataflow sweeps (ffm_solve.hip)
 int ffm_tile_gs_ghost_terms(ffm_ldu *A, const double *psi, double *bP);

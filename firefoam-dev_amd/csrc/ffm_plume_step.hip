@@ -63,7 +63,7 @@ static int rho_eqn_ops(ffm_plume *P)
 }
 // fvm::ddt(rho) + fvc::div(phi) == 0  -> diagonal: rho = (rdt*rho0*V - V*div(phi))/(rdt*V).  The one-pass kernel refuses only rows
 // wider than 16 entries; the rows of a hex block have at most 6 (three faces towards owned cells and one cut face per coupled side
-// that a corner cell touches: ffm_ldu.hip counts both into maxW), so no FFM_ERR_UNSUPPORTED comes back from it here.
+// that a corner cell touches: ffm_ldu_analysis.cpp counts both into maxW), so no FFM_ERR_UNSUPPORTED comes back from it here.
 static int rho_eqn(ffm_plume *P)
 {
     FFM_TRY(P->fused ? ffm_fvc_rho_eqn(P->mesh, P->rdt, P->phi, P->phib, P->rho0, P->rho) : rho_eqn_ops(P));

@@ -31,7 +31,7 @@
 constexpr int T_RING = 4096;        // doubles (power of two)
 constexpr int T_ENT = 256;          // max cells per entry = workgroup size
 constexpr int T_THREADS = 256;
-constexpr int T_W = 3;              // neighbour slots per cell and direction (hexahedra: 3)
+constexpr int T_W = FFM_TILE_W;     // neighbour slots per cell and direction (ffm_host.hpp: ffm_tile_feasible tests it on the host)
 constexpr int T_PF = 8;             // entries fetched ahead of the one being computed
 constexpr int T_PM = 3;             // mailbox values are loaded this many entries ahead (2 <= T_PM < T_PF)
 constexpr int T_XMAX = 64;          // max external references per entry (one lane of the mail wave each; power of two)
@@ -116,18 +116,6 @@ void ffm_tile_free(ffm_ldu *A)
 bool ffm_tile_usable(const ffm_ldu *A) { return A->tile && A->tile->usable; }
 
 template <class T> static int upv(ffm_ctx *c, T **d, const std::vector<T> &v) { return ffm_upload_vec(c, d, v); }
-
-// The tiled sweeps need at most T_W lower and T_W upper neighbours per owned cell (ghost neighbours not counted) and,
-// inside every group, a backward order that is the reverse of the forward order (LduAnalysis::bwdIsReverse).
-bool ffm_tile_feasible(int nOwn, int F, const int *l, const int *u)
-{
-    std::vector<unsigned char> nl(nOwn, 0), nu(nOwn, 0);
-    for (int f = 0; f < F; f++) {
-        if (u[f] >= nOwn) continue;
-        if (++nu[l[f]] > T_W || ++nl[u[f]] > T_W) return false;
-    }
-    return true;
-}
 
 // Build one direction.  fwd: neighbours = lower entries (cells with smaller index); bwd: upper slots.  Neighbours that are
 // ghost cells are dropped (block-Jacobi sweeps ignore them); the remaining ones keep their order, which is the order of
