@@ -267,6 +267,10 @@ def lib():
         "ffm_flow_order_nlevels": ([vp], C.c_int),
         "ffm_flow_order_destroy": ([vp], C.c_int),
         "ffm_solve_ordered_d": ([vp, vp, dp, dp, C.POINTER(Perf)], C.c_int),
+        "ffm_flow_stages": ([C.c_int, C.c_int, C.c_int, ip, ip, hp, hp, ip, ip, ip, ip], C.c_int),
+        "ffm_flow_order_create_staged": ([vp, C.POINTER(vp)], C.c_int),
+        "ffm_flow_order_nstages": ([vp], C.c_int),
+        "ffm_solve_ordered_staged_d": ([vp, vp, dp, dp, C.POINTER(Perf)], C.c_int),
         "ffm_plume_set_initial_state": ([vp, C.POINTER(C.c_void_p), hp, hp, hp, C.c_double], C.c_int),
         "ffm_plume_override_mv_weights": ([vp, hp], C.c_int),
         "ffm_plume_ncells": ([vp], C.c_int),
@@ -346,17 +350,45 @@ def flow_levels(nCells, lowerAddr, upperAddr, upper, lower):
     return order[:int(nCells)], nLev.value
 
 
-class FlowOrder:
-    """The dependency order of the coefficients an lduMatrix held when this was made (ffm_flow_order): lduMatrix.flow_order()"""
+def flow_stages(nOwned, nGhost, lowerAddr, upperAddr, upper, lower, ghostStage):
+    """(stage, order, nLevels) of one rank's sub-domain of a decomposed upwind ray matrix (ffm_flow_stages; host code, no GPU, no
+    communication): nOwned cells with rows followed by nGhost ghost cells whose stages on their own ranks are ghostStage.
+    FfmError where the non-zero entries form a cycle among the owned cells."""
+    l = np.ascontiguousarray(lowerAddr, np.int32)
+    u = np.ascontiguousarray(upperAddr, np.int32)
+    up = np.ascontiguousarray(upper, np.float64)
+    lo = np.ascontiguousarray(lower, np.float64)
+    gs = np.ascontiguousarray(ghostStage, np.int32)
+    if not (len(l) == len(u) == len(up) == len(lo)) or len(gs) != int(nGhost):
+        raise FfmError("flow_stages: lowerAddr, upperAddr, upper and lower must have one entry per face, ghostStage one per ghost cell")
+    stage = np.empty(max(int(nOwned), 1), np.int32)
+    order = np.empty(max(int(nOwned), 1), np.int32)
+    nLev = C.c_int(0)
+    _check(lib().ffm_flow_stages(int(nOwned), int(nGhost), len(l), _ip(l), _ip(u), _hp(up), _hp(lo), _ip(gs), _ip(stage), _ip(order),
+                                 C.byref(nLev)), "ffm_flow_stages")
+    return stage[:int(nOwned)], order[:int(nOwned)], nLev.value
 
-    def __init__(self, A):
+
+class FlowOrder:
+    """The dependency order of the coefficients an lduMatrix held when this was made (ffm_flow_order): lduMatrix.flow_order(), or
+    lduMatrix.flow_order_staged() on one rank of a decomposed matrix (collective)"""
+
+    def __init__(self, A, staged=False):
         h = C.c_void_p()
-        _check(lib().ffm_flow_order_create(A.h, C.byref(h)), "ffm_flow_order_create")
+        if staged:
+            _check(lib().ffm_flow_order_create_staged(A.h, C.byref(h)), "ffm_flow_order_create_staged")
+        else:
+            _check(lib().ffm_flow_order_create(A.h, C.byref(h)), "ffm_flow_order_create")
         self.h = h
 
     @property
     def nLevels(self):
         return lib().ffm_flow_order_nlevels(self.h)
+
+    @property
+    def nStages(self):
+        """stages over all ranks of a staged order (one sweep launch each, nStages - 1 ghost exchanges per solve); 0: single rank"""
+        return lib().ffm_flow_order_nstages(self.h)
 
     def close(self):
         if getattr(self, "h", None):
@@ -743,6 +775,20 @@ class lduMatrix:
         perf = Perf()
         _check(lib().ffm_solve_ordered_d(self.h, order.h, C.c_void_p(psi.data_ptr()), C.c_void_p(source.data_ptr()), C.byref(perf)),
                "ffm_solve_ordered_d")
+        return perf.as_dict()
+
+    def flow_order_staged(self):
+        """FlowOrder of one rank of a decomposed matrix (ffm_flow_order_create_staged): COLLECTIVE, every rank calls it; .nStages"""
+        self.ctx._ready()
+        return FlowOrder(self, staged=True)
+
+    def solve_ordered_staged(self, order, psi, source):
+        """psi = A^-1 source over all ranks, stage by stage in `order` (ffm_solve_ordered_staged_d; COLLECTIVE), psi [owned + ghost]
+        updated in place; FfmError on EVERY rank, psi untouched, where the order does not fit the coefficients held now on any rank"""
+        self.ctx._ready()
+        perf = Perf()
+        _check(lib().ffm_solve_ordered_staged_d(self.h, order.h, C.c_void_p(psi.data_ptr()), C.c_void_p(source.data_ptr()), C.byref(perf)),
+               "ffm_solve_ordered_staged_d")
         return perf.as_dict()
 
     def solve_multi(self, diags, upper, lower, psis, sources, solver="PBiCGStab", preconditioner="DILU", tolerance=1e-6, relTol=0.0,

@@ -135,18 +135,18 @@ int ffm_allreduce_slots(ffm_ctx *c, int firstSlot, int n)
     return FFM_OK;
 }
 
-int ffm_allreduce_minmax(ffm_ctx *c, int slot, int isMax)
+int ffm_allreduce_minmax(ffm_ctx *c, int slot, int isMax, int n)
 {
     if (c->nRanks <= 1 && !c->comm) return FFM_OK;
     if (c->comm) {
-        FFM_NCCL(ncclAllReduce(c->scal_d + slot, c->scal_d + slot, 1, ncclDouble, isMax ? ncclMax : ncclMin, (ncclComm_t)c->comm, c->stream));
+        FFM_NCCL(ncclAllReduce(c->scal_d + slot, c->scal_d + slot, n, ncclDouble, isMax ? ncclMax : ncclMin, (ncclComm_t)c->comm, c->stream));
         return FFM_OK;
     }
     if (!c->hostAllreduce) { ffm_set_error("nRanks>1 but no communicator attached"); return FFM_ERR_COMM; }
-    FFM_HIP(hipMemcpyAsync(c->scal_h + slot, c->scal_d + slot, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FFM_HIP(hipMemcpyAsync(c->scal_h + slot, c->scal_d + slot, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     FFM_HIP(hipStreamSynchronize(c->stream));
-    c->hostAllreduce(c->hostUser, c->scal_h + slot, 1, isMax ? 2 : 1);
-    FFM_HIP(hipMemcpyAsync(c->scal_d + slot, c->scal_h + slot, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    c->hostAllreduce(c->hostUser, c->scal_h + slot, n, isMax ? 2 : 1);
+    FFM_HIP(hipMemcpyAsync(c->scal_d + slot, c->scal_h + slot, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     FFM_HIP(hipStreamSynchronize(c->stream));
     return FFM_OK;
 }

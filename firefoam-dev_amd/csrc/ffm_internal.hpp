@@ -236,7 +236,7 @@ int ffm_k_spmv_sumA(ffm_ldu *A, const double *x, double *y, double *s);
 int ffm_halo_update(ffm_ldu *A, const double *x, double *y, const double *coeffs, double sign);  // exchange + apply
 int ffm_halo_apply(ffm_ldu *A, double *y, const double *coeffs, const double *vals /*null => 1*/, double sign);
 int ffm_allreduce_slots(ffm_ctx *ctx, int firstSlot, int n);   // sum over ranks, in stream
-int ffm_allreduce_minmax(ffm_ctx *ctx, int slot, int isMax);
+int ffm_allreduce_minmax(ffm_ctx *ctx, int slot, int isMax, int n = 1);   // min or max over ranks of n slots, in stream
 void ffm_comm_finalize_i(ffm_ctx *ctx);
 int ffm_precond_setup_i(ffm_ldu *A, int precond);
 int ffm_precond_apply_i(ffm_ldu *A, int precond, bool transpose, const double *r, double *w);

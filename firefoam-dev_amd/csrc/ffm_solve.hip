@@ -883,6 +883,11 @@ struct ffm_flow_order {
     ffm_ctx *ctx = nullptr;
     int N = 0, nLevels = 0;
     int *order = nullptr;          // [N] device: position -> internal cell
+    // the staged form of a decomposed matrix (ffm_flow_order_create_staged; nStages == 0: a single-rank order)
+    int nGhost = 0, nStages = 0;   // nStages: over all ranks, the same on every rank
+    std::vector<int> stageStart;   // [nStages + 1] host: stage s = the positions [stageStart[s], stageStart[s + 1]) of order
+    int *stage = nullptr;          // [N] device: stage of every owned cell (internal numbering)
+    int *ghostStage = nullptr;     // [nGhost] device: stage of every ghost cell on the rank that owns it
 };
 
 struct OrderedArgs {
@@ -961,24 +966,17 @@ __global__ __launch_bounds__(FLOW_T) void k_flow_ordered(OrderedArgs a)
 static bool ordered_single_rank(const ffm_ldu *A)
 { return A->nOwned == A->nCells && A->ifaces.empty() && A->ghNbrRank.empty(); }
 
-extern "C" int ffm_flow_order_create(ffm_ldu *A, ffm_flow_order **out)
+// the off-diagonals the matrix holds, once, as the faces of the internal numbering in the caller's face order of every row
+// (columns >= nOwned: ghost cells)
+static int download_faces(ffm_ldu *A, std::vector<int> &l, std::vector<int> &u, std::vector<double> &cu, std::vector<double> &cl)
 {
-    if (!A || !out) { ffm_set_error("ffm_flow_order_create: null argument"); return FFM_ERR_ARG; }
-    *out = nullptr;
-    if (!ordered_single_rank(A)) {
-        ffm_set_error("ffm_flow_order_create: single rank only (the matrix has ghost cells, processor interfaces or a ghost exchange)");
-        return FFM_ERR_UNSUPPORTED;
-    }
-    FFM_HIP(hipSetDevice(A->ctx->device));
-    const int N = A->nOwned, nS = A->nSlices, T = A->upTotal;
-    // the off-diagonals the matrix holds, once, as the faces of the internal numbering in the caller's face order of every row
+    const int nS = A->nSlices, T = A->upTotal;
     std::vector<int> upOff((size_t)nS + 1, 0), upNbr((size_t)T);
     std::vector<double> up((size_t)T), lo((size_t)T);
     FFM_TRY(ffm_d2h(A->ctx, upOff.data(), A->upOff, sizeof(int) * ((size_t)nS + 1)));
     FFM_TRY(ffm_d2h(A->ctx, upNbr.data(), A->upNbr, sizeof(int) * (size_t)T));
     FFM_TRY(ffm_d2h(A->ctx, up.data(), A->upper, sizeof(double) * (size_t)T));
     if (A->lower != A->upper) FFM_TRY(ffm_d2h(A->ctx, lo.data(), A->lower, sizeof(double) * (size_t)T)); else lo = up;
-    std::vector<int> l, u; std::vector<double> cu, cl;
     l.reserve(A->nFaces); u.reserve(A->nFaces); cu.reserve(A->nFaces); cl.reserve(A->nFaces);
     for (int sl = 0; sl < nS; sl++) {
         const int base = upOff[sl], w = (upOff[sl + 1] - base) >> 6;
@@ -988,6 +986,21 @@ extern "C" int ffm_flow_order_create(ffm_ldu *A, ffm_flow_order **out)
             l.push_back(sl * 64 + lane); u.push_back(n); cu.push_back(up[e]); cl.push_back(lo[e]);
         }
     }
+    return FFM_OK;
+}
+
+extern "C" int ffm_flow_order_create(ffm_ldu *A, ffm_flow_order **out)
+{
+    if (!A || !out) { ffm_set_error("ffm_flow_order_create: null argument"); return FFM_ERR_ARG; }
+    *out = nullptr;
+    if (!ordered_single_rank(A)) {
+        ffm_set_error("ffm_flow_order_create: single rank only (the matrix has ghost cells, processor interfaces or a ghost exchange)");
+        return FFM_ERR_UNSUPPORTED;
+    }
+    FFM_HIP(hipSetDevice(A->ctx->device));
+    const int N = A->nOwned;
+    std::vector<int> l, u; std::vector<double> cu, cl;
+    FFM_TRY(download_faces(A, l, u, cu, cl));
     std::vector<int> order((size_t)std::max(N, 1));
     int nLev = 0;
     FFM_TRY(ffm_flow_levels(N, (int)l.size(), l.data(), u.data(), cu.data(), cl.data(), order.data(), &nLev));
@@ -1005,7 +1018,7 @@ extern "C" int ffm_flow_order_destroy(ffm_flow_order *o)
     if (!o) return FFM_OK;
     hipSetDevice(o->ctx->device);
     hipStreamSynchronize(o->ctx->stream);
-    hipFree(o->order);
+    hipFree(o->order); hipFree(o->stage); hipFree(o->ghostStage);
     delete o;
     return FFM_OK;
 }
@@ -1066,6 +1079,256 @@ extern "C" int ffm_solve_ordered_d(ffm_ldu *A, const ffm_flow_order *o, double *
     out->nIterations = 1; out->singular = 0;
     out->converged = (c->scal_h[S_TMP0] <= 1e-10 * c->scal_h[S_TMP1]) ? 1 : 0;      // (false for NaN too)
     FFM_TRY(ffm_sweep_check_abort(A));
+    return FFM_OK;
+}
+
+// ------------------------------------------------------------------ flow-ordered exact solve, decomposed ---
+// On a decomposed mesh the cells' dependency graph is still acyclic, the ranks' is not (rank A feeds B across one cut face, B
+// feeds A across another), so the order is staged by cells: stage = the largest number of rank crossings on any upstream path
+// (ffm_flow_stages, ffm_rays.cpp).  The rows of stage s need owned cells of stage <= s and ghost cells of stage < s:
+// every rank solves its stage-s rows in one dataflow sweep -- k_flow_ordered's machinery over the positions of the stage, a ghost
+// column read from psi's ghost entry, which the exchange behind the stage before filled -- then all ranks refresh psi's ghost
+// entries once, and stage s + 1 follows: nStages - 1 exchanges per solve.  Every decision a rank takes on what it alone sees (a
+// local cycle, a row the order does not fit, the abort word) is all-reduced first, so all ranks leave a call the same way.
+static bool ordered_decomposed(const ffm_ldu *A)
+{
+    // a ghost exchange, or a rank of several that has no neighbour (and then no ghost cell)
+    return A->ifaces.empty() && (!A->ghNbrRank.empty() || (A->ctx->nRanks > 1 && A->nCells == A->nOwned));
+}
+// v[0 .. n) -> their sum (isMax 0) or maximum (1) over the ranks; n <= 4
+static int allreduce_host_values(ffm_ctx *c, double *v, int n, int isMax)
+{
+    if (c->nRanks <= 1 && !c->comm) return FFM_OK;
+    FFM_TRY(ffm_h2d(c, c->scal_d + S_TMP0, v, sizeof(double) * n));
+    FFM_TRY(isMax ? ffm_allreduce_minmax(c, S_TMP0, 1, n) : ffm_allreduce_slots(c, S_TMP0, n));
+    return ffm_d2h(c, v, c->scal_d + S_TMP0, sizeof(double) * n);
+}
+__global__ void k_int_to_double(long n, const int *__restrict__ a, double *__restrict__ x)
+{ GRID_STRIDE(i, n) x[i] = (double)a[i]; }
+__global__ void k_double_to_int(long n, const double *__restrict__ x, int *__restrict__ a)
+{ GRID_STRIDE(i, n) a[i] = (int)x[i]; }
+
+extern "C" int ffm_flow_order_create_staged(ffm_ldu *A, ffm_flow_order **out)
+{
+    if (!A || !out) { ffm_set_error("ffm_flow_order_create_staged: null argument"); return FFM_ERR_ARG; }
+    *out = nullptr;
+    if (!ordered_decomposed(A)) {
+        ffm_set_error("ffm_flow_order_create_staged: needs a matrix with a ghost exchange (ffm_ldu_set_ghost_exchange) and no processor "
+                      "interfaces; ffm_flow_order_create is the single-rank form");
+        return FFM_ERR_UNSUPPORTED;
+    }
+    FFM_HIP(hipSetDevice(A->ctx->device));
+    ffm_ctx *c = A->ctx; hipStream_t s = c->stream;
+    const int N = A->nOwned, nG = A->nCells - A->nOwned;
+    std::vector<int> l, u; std::vector<double> cu, cl;
+    FFM_TRY(download_faces(A, l, u, cu, cl));
+    double *x;                                             // the stages as a cell field: what the ghost exchange moves
+    FFM_TRY(ffm_ldu_work(A, 23, &x));
+    ffm_flow_order *o = new ffm_flow_order;
+    o->ctx = c; o->N = N; o->nGhost = nG;
+    // from here on every rank takes every step: what fails locally is carried in `fail` to the all-reduce of the round
+    int fail = FFM_OK;
+    if (hipMalloc((void **)&o->order, sizeof(int) * (size_t)std::max(N, 1)) != hipSuccess || hipMalloc((void **)&o->stage, sizeof(int) * (size_t)std::max(N, 1)) != hipSuccess ||
+        hipMalloc((void **)&o->ghostStage, sizeof(int) * (size_t)std::max(nG, 1)) != hipSuccess) {
+        ffm_set_error("ffm_flow_order_create_staged: out of device memory"); fail = FFM_ERR_HIP;
+    }
+    double total = (double)nG;                             // a path with more rank crossings than there are ghost cells revisits one
+    int rc = allreduce_host_values(c, &total, 1, 0);
+    std::vector<int> order((size_t)std::max(N, 1)), stage((size_t)std::max(N, 1), 0), ghostStage((size_t)std::max(nG, 1), 0), got((size_t)std::max(nG, 1), 0);
+    int nLev = 0, nStages = 0;
+    bool anyFail = false, cycle = false;
+    while (rc == FFM_OK) {
+        if (fail == FFM_OK) fail = ffm_flow_stages(N, nG, (int)l.size(), l.data(), u.data(), cu.data(), cl.data(), ghostStage.data(), stage.data(), order.data(), &nLev);
+        int top = -1;
+        for (int i = 0; i < N; i++) top = std::max(top, stage[i]);
+        // the owned cells' stages to the neighbours' ghost cells: one ghost exchange of a double field (small integers: exact)
+        if (fail == FFM_OK) rc = ffm_h2d(c, o->stage, stage.data(), sizeof(int) * (size_t)N);
+        if (rc != FFM_OK) break;
+        if (fail == FFM_OK && N) hipLaunchKernelGGL(k_int_to_double, dim3(sgrid(N)), dim3(256), 0, s, (long)N, o->stage, x);
+        else if ((rc = ffm_dzero(c, x, sizeof(double) * (size_t)A->nCells)) != FFM_OK) break;
+        if ((rc = ffm_ghost_exchange(A, x)) != FFM_OK) break;
+        bool changed = false;
+        if (fail == FFM_OK && nG) {
+            hipLaunchKernelGGL(k_double_to_int, dim3(sgrid(nG)), dim3(256), 0, s, (long)nG, x + N, o->ghostStage);
+            if ((rc = ffm_d2h(c, got.data(), o->ghostStage, sizeof(int) * (size_t)nG)) != FFM_OK) break;
+            changed = got != ghostStage;
+            ghostStage = got;
+        }
+        double v[3] = {changed ? 1.0 : 0.0, fail != FFM_OK ? 1.0 : 0.0, (double)top};
+        if ((rc = allreduce_host_values(c, v, 3, 1)) != FFM_OK) break;
+        anyFail = v[1] != 0.0; cycle = v[2] > total; nStages = (int)v[2] + 1;
+        if (anyFail || cycle || v[0] == 0.0) break;
+    }
+    if (rc == FFM_OK && hipGetLastError() != hipSuccess) { ffm_set_error("ffm_flow_order_create_staged: a kernel launch failed"); rc = FFM_ERR_HIP; }
+    if (rc == FFM_OK && fail != FFM_OK) rc = fail;        // (ffm_flow_stages has set the message)
+    else if (rc == FFM_OK && anyFail) { ffm_set_error("ffm_flow_order_create_staged: refused on another rank (a cycle among its cells, or out of memory)"); rc = FFM_ERR_UNSUPPORTED; }
+    else if (rc == FFM_OK && cycle) {
+        ffm_set_error("ffm_flow_order_create_staged: a stage above the %.0f ghost cells of all ranks: the non-zero off-diagonal coefficients "
+                      "form a cycle through several ranks", total);
+        rc = FFM_ERR_UNSUPPORTED;
+    }
+    if (rc == FFM_OK) {
+        o->nLevels = nLev; o->nStages = nStages;
+        o->stageStart.assign((size_t)nStages + 1, 0);
+        for (int i = 0; i < N; i++) o->stageStart[stage[i] + 1]++;
+        for (int k = 0; k < nStages; k++) o->stageStart[k + 1] += o->stageStart[k];
+        rc = ffm_h2d(c, o->order, order.data(), sizeof(int) * (size_t)N);
+    }
+    if (rc != FFM_OK) { ffm_flow_order_destroy(o); return rc; }
+    *out = o;
+    return FFM_OK;
+}
+extern "C" int ffm_flow_order_nstages(const ffm_flow_order *o) { return o ? o->nStages : FFM_ERR_ARG; }
+
+// k_order_check for a staged order: non-zero entries whose owned column does not stand earlier than the row or has a later stage,
+// or whose ghost column's stage is not below the row's
+template <int W>
+__global__ __launch_bounds__(256) void k_order_check_staged(LduView v, const double *__restrict__ upper, const double *__restrict__ lower,
+                                                            const int *__restrict__ pos, const int *__restrict__ stage,
+                                                            const int *__restrict__ ghostStage, double *__restrict__ partials)
+{
+    __shared__ double sm[4];
+    double bad = 0.0;
+    GRID_STRIDE(i, (long)v.N) {
+        const int c = (int)i;
+        RowEnt<W> L, U; load_lower<W>(v, c, L); load_upper<W>(v, c, U);
+        const int pc = pos[c], sc = stage[c];
+#pragma unroll
+        for (int s = 0; s < W; s++) {
+            if (L.on[s] && lower[L.f[s]] != 0.0 && !(pos[L.nb[s]] < pc && stage[L.nb[s]] <= sc)) bad += 1.0;
+            if (U.on[s] && upper[U.f[s]] != 0.0) {
+                const int n = U.nb[s];
+                if (n < v.N ? !(pos[n] < pc && stage[n] <= sc) : !(ghostStage[n - v.N] < sc)) bad += 1.0;
+            }
+        }
+    }
+    const double r = block_sum(bad, sm);
+    if (threadIdx.x == 0) partials[blockIdx.x] = r;
+}
+
+// k_flow_ordered over the positions [p0, p1) of one stage: a row waits on the published array for its owned columns only (cells
+// of this launch's earlier positions, or of an earlier launch: published then); a ghost column is psi's ghost entry as the
+// exchange behind an earlier stage left it, a plain load -- a kernel boundary lies in between
+template <int W>
+__global__ __launch_bounds__(FLOW_T) void k_flow_ordered_stage(OrderedArgs a, int p0, int p1)
+{
+    __shared__ unsigned shTicket;
+    if (threadIdx.x == 0) shTicket = atomicAdd(&a.ticket[0], 1u);
+    __syncthreads();
+    const int p = p0 + (int)shTicket * FLOW_T + threadIdx.x;
+    if (p >= p1) return;
+    const int c = a.order[p];
+    unsigned spins = 0;
+    RowEnt<W> L, U; load_lower<W>(a.v, c, L); load_upper<W>(a.v, c, U);
+    double al[W], au[W], pl[W], pu[W];
+    bool own[W];
+#pragma unroll
+    for (int s = 0; s < W; s++) {
+        al[s] = a.lower[L.f[s]]; au[s] = a.upper[U.f[s]];
+        L.on[s] = L.on[s] && al[s] != 0.0; U.on[s] = U.on[s] && au[s] != 0.0;      // a zero entry is no dependency: not waited for
+        own[s] = U.on[s] && U.nb[s] < a.N;
+        pl[s] = 0.0; pu[s] = (U.on[s] && !own[s]) ? a.psi[U.nb[s]] : 0.0;
+    }
+    const double bc = a.source[c], dg = a.diag[c];
+    bool done = false; do { if (!done) {
+        bool ready = true;
+#pragma unroll
+        for (int s = 0; s < W; s++) {
+            if (L.on[s]) { pl[s] = s_ld(&a.mf[L.nb[s]]); ready = ready && !f_pending(pl[s]); }
+            if (own[s]) { pu[s] = s_ld(&a.mf[U.nb[s]]); ready = ready && !f_pending(pu[s]); }
+        }
+        if (ready) {
+            double val = bc;
+#pragma unroll
+            for (int s = 0; s < W; s++) if (L.on[s]) val -= al[s] * pl[s];
+#pragma unroll
+            for (int s = 0; s < W; s++) if (U.on[s]) val -= au[s] * pu[s];
+            val /= dg;
+            a.psi[c] = val;
+            f_st(&a.mf[c], val);
+            done = true;
+        } else done = f_give_up(spins, a.ticket, a.nap);
+    } } while (__ballot(!done) != 0ull);
+}
+
+extern "C" int ffm_solve_ordered_staged_d(ffm_ldu *A, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out)
+{
+    if (!A || !o || !psi_d || !source_d || !out) { ffm_set_error("ffm_solve_ordered_staged_d: null argument"); return FFM_ERR_ARG; }
+    if (!ordered_decomposed(A)) {
+        ffm_set_error("ffm_solve_ordered_staged_d: needs a matrix with a ghost exchange (ffm_ldu_set_ghost_exchange) and no processor "
+                      "interfaces; ffm_solve_ordered_d is the single-rank form");
+        return FFM_ERR_UNSUPPORTED;
+    }
+    memset(out, 0, sizeof(*out));
+    FFM_HIP(hipSetDevice(A->ctx->device));
+    ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned;
+    // ---- 1. the order against the coefficients the matrix holds now, over all ranks; nothing else is launched or exchanged before
+    const bool mine = o->ctx == A->ctx && o->N == A->nOwned && o->nGhost == A->nCells - A->nOwned && o->nStages > 0;
+    const int g = sgrid(N);
+    double v[3] = {1.0, (double)o->nStages, -(double)o->nStages};
+    if (mine) {
+        double *posBuf;
+        FFM_TRY(ffm_ldu_work(A, 23, &posBuf));
+        int *pos = (int *)posBuf;
+        hipLaunchKernelGGL(k_order_pos, dim3(g), dim3(256), 0, s, N, o->order, pos);
+        FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_order_check_staged<W>, dim3(g), dim3(256), 0, s, ffm_view(A), A->upper, A->lower, pos, o->stage, o->ghostStage, c->partials_d));
+        FFM_HIP(hipGetLastError());
+        FFM_TRY(partial_sum_to(c, g, S_TMP0));
+        FFM_TRY(ffm_read_scalars(c));
+        v[0] = c->scal_h[S_TMP0];
+    }
+    const double bad = v[0];
+    FFM_TRY(allreduce_host_values(c, v, 3, 1));
+    if (!(v[0] == 0.0) || v[1] != -v[2]) {
+        if (!mine) ffm_set_error("ffm_solve_ordered_staged_d: the order belongs to another matrix (%d cells, %d ghost cells, %d stages; matrix %d, %d): nothing solved",
+                                 o->N, o->nGhost, o->nStages, A->nOwned, A->nCells - A->nOwned);
+        else if (!(bad == 0.0)) ffm_set_error("ffm_solve_ordered_staged_d: %.0f non-zero entries do not precede their rows in this order or reach a ghost cell of a "
+                                              "stage not below their row's (a stale order, the order of another matrix, or a matrix that is not triangular): nothing solved", bad);
+        else if (v[1] != -v[2]) ffm_set_error("ffm_solve_ordered_staged_d: the ranks' orders have %.0f to %.0f stages (orders of different matrices): nothing solved", -v[2], v[1]);
+        else ffm_set_error("ffm_solve_ordered_staged_d: the order was refused on another rank: nothing solved");
+        return FFM_ERR_UNSUPPORTED;
+    }
+    // ---- 2. the stages, on the internal numbering
+    const double *si = source_d; double *pi = psi_d;
+    if (!A->identity) {
+        FFM_TRY(ffm_to_internal(A, source_d, 1, &si));
+        const double *pin; FFM_TRY(ffm_to_internal(A, psi_d, 2, &pin)); pi = A->permIn[2];
+    }
+    double *sumA, *Apsi, *rA;
+    FFM_TRY(ffm_ldu_work(A, 1, &sumA)); FFM_TRY(ffm_ldu_work(A, 2, &Apsi)); FFM_TRY(ffm_ldu_work(A, 3, &rA));
+    FFM_TRY(scalar_op(c, OP_RESET));
+    FFM_TRY(ffm_k_spmv_sumA(A, pi, Apsi, sumA));
+    FFM_TRY(norm_and_initial(A, pi, si, Apsi, sumA, rA, out));
+    OrderedArgs a{};
+    a.v = ffm_view(A); a.N = A->nOwned; a.nap = 1; a.order = o->order;
+    a.upper = A->upper; a.lower = A->lower; a.diag = A->diag; a.source = si; a.psi = pi; a.ticket = A->sweepTicket;
+    FFM_TRY(ffm_ldu_work(A, 20, &a.mf));
+    hipLaunchKernelGGL(k_flow_fill, dim3(g), dim3(256), 0, s, N, a.mf, (double *)nullptr, (double *)nullptr, a.ticket);
+    for (int st = 0; st < o->nStages; st++) {
+        const int p0 = o->stageStart[st], p1 = o->stageStart[st + 1], nChunk = (p1 - p0 + FLOW_T - 1) / FLOW_T;
+        if (nChunk > 0) {
+            if (st > 0) FFM_TRY(ffm_dzero(c, a.ticket, sizeof(unsigned int)));          // the ticket counter; the abort word stays
+            FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_flow_ordered_stage<W>, dim3(nChunk), dim3(FLOW_T), 0, s, a, p0, p1));
+            FFM_HIP(hipGetLastError());
+        }
+        if (st + 1 < o->nStages) FFM_TRY(ffm_ghost_exchange(A, pi));                    // every rank, also one whose stage was empty
+    }
+    // ---- 3. what the solve left (the residual's Amul refreshes psi's ghost entries: they hold the neighbours' results on return)
+    FFM_TRY(ffm_k_residual(A, pi, si, rA));
+    FFM_TRY(ffm_k_summag(c, rA, N, S_TMP0));
+    FFM_TRY(ffm_k_summag(c, si, N, S_TMP1));
+    FFM_TRY(ffm_allreduce_slots(c, S_TMP0, 2));
+    FFM_TRY(scalar_op(c, OP_RES));
+    if (!A->identity) FFM_TRY(ffm_from_internal(A, pi, psi_d));
+    FFM_TRY(ffm_read_scalars(c));
+    out->initialResidual = c->scal_h[S_RES0]; out->finalResidual = c->scal_h[S_RES];
+    out->nIterations = 1; out->singular = 0;
+    out->converged = (c->scal_h[S_TMP0] <= 1e-10 * c->scal_h[S_TMP1]) ? 1 : 0;      // (false for NaN too)
+    const int rcAbort = ffm_sweep_check_abort(A);
+    double ab = rcAbort != FFM_OK ? 1.0 : 0.0;
+    FFM_TRY(allreduce_host_values(c, &ab, 1, 1));
+    if (rcAbort != FFM_OK) return rcAbort;
+    if (ab != 0.0) { ffm_set_error("ffm_solve_ordered_staged_d: a dataflow sweep timed out on another rank"); return FFM_ERR_HIP; }
     return FFM_OK;
 }
 

@@ -571,6 +571,48 @@ int ffm_flow_order_destroy(ffm_flow_order *o);
  * (ffm_ldu_is_native_order() == 0) they go through the permutation the other solvers use.  Single rank only.              */
 int ffm_solve_ordered_d(ffm_ldu *ldu, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out);
 
+/* ------------------------------------------------------- flow-ordered exact solve on a decomposed mesh, any partition */
+/* The ranks' dependency graph of a ray is cyclic on general partitions (rank A feeds B across one cut face, B feeds A across
+ * another); the cells' is not.  So every cell gets a STAGE: the largest number of rank crossings on any upstream path to it.
+ * The rows of stage s need owned cells of stage <= s and ghost cells of stage < s, so a rank solves its stage-s rows exactly in
+ * one sweep, all ranks exchange ghost values once, and stage s + 1 follows.
+ * ffm_flow_stages is one rank's share of that analysis: pure host code, no GPU, no communication.  The rank's sub-domain in the
+ * form of ffm_ldu_create_ext: cells [0, nOwned) have rows, cells [nOwned, nOwned + nGhost) are ghost cells, sources whose stage
+ * on their own rank is ghostStage[].  Edges as in ffm_flow_levels, rows for owned cells only.  stage[c] = max over the cells u
+ * row c needs of stage[u] (u owned) or ghostStage[u - nOwned] + 1 (u a ghost cell); 0 without any.  order[nOwned]: the owned
+ * cells stage-major, inside a stage level-major by the levels of ffm_flow_levels on the owned sub-graph (ascending cell index
+ * inside a level): every non-zero owned column stands before its row.  nLevels: the level count of the owned sub-graph.
+ * FFM_ERR_UNSUPPORTED where the non-zero entries form a cycle among the owned cells (a cycle through several ranks is not
+ * visible to one of them: ffm_flow_order_create_staged).                                                                    */
+int ffm_flow_stages(int nOwned, int nGhost, int nFaces, const int *lowerAddr, const int *upperAddr, const double *upper, const double *lower,
+                    const int *ghostStage /* [nGhost] */, int *stage /* [nOwned] */, int *order /* [nOwned] */, int *nLevels);
+/* COLLECTIVE: every rank of the communicator calls it, for a matrix with ghost cells and a ghost exchange (ffm_ldu_create_ext +
+ * ffm_ldu_set_ghost_exchange; no processor interfaces).  The staged order of the coefficients the matrix holds now as the least
+ * fixpoint over the ranks: all ghost stages 0, ffm_flow_stages, one ghost exchange of the stages, one all-reduce of "some ghost
+ * stage changed", until none did -- at most (stage count + 1) rounds, every rank the same number.  A stage above the number of
+ * ghost cells of all ranks is a cycle through several ranks; that, and a failure on any one rank (a cycle among its own cells,
+ * out of memory), makes EVERY rank return an error (FFM_ERR_UNSUPPORTED for the cycles), none leaves while another waits.
+ * The order keeps order[nOwned], stage[nOwned] and ghostStage[nGhost] on the device.  A matrix without a ghost exchange is
+ * refused (ffm_flow_order_create is the single-rank entry point), except the rank of a larger communicator that has no
+ * neighbour.  ffm_flow_order_nlevels: the levels of this rank's owned sub-graph; ffm_flow_order_destroy as for any order.    */
+int ffm_flow_order_create_staged(ffm_ldu *ldu, ffm_flow_order **out);
+/* the stage count over all ranks, the same on every rank (0 for an order of ffm_flow_order_create): a solve costs one sweep
+ * launch per stage on every rank and (stage count - 1) ghost exchanges -- 2 to 5 on RCB-like partitions of the test meshes,
+ * tens to hundreds on the jagged ones of graph growing (README.md)                                                          */
+int ffm_flow_order_nstages(const ffm_flow_order *o);
+/* COLLECTIVE.  psi = A^-1 source over all ranks, stage by stage: per stage one sweep of this rank's rows of that stage (no
+ * launch where it has none) -- a row as in ffm_solve_ordered_d: source minus the lower faces' then the upper faces' terms in the
+ * rank's own face order, zero coefficients skipped, ghost columns read from psi's ghost entries, one division -- and after every
+ * stage but the last one ghost refresh of psi, entered by every rank.  First of all the order is checked against the
+ * coefficients the matrix holds NOW (every non-zero owned column earlier in the order and of a stage <= the row's, every
+ * non-zero ghost column of a stage < the row's) and the failure count is all-reduced with the stage counts: if any row on any
+ * rank fails, or the ranks' orders differ in their stage count, ALL ranks return FFM_ERR_UNSUPPORTED with psi_d untouched,
+ * before any sweep or exchange.  out: nIterations 1; OpenFOAM's normalised residuals of the start value and of the result and
+ * converged (the rule of ffm_solve_ordered_d) with the sums over all ranks, the same on every rank.  A sweep that timed out on
+ * any rank makes all ranks return FFM_ERR_HIP.  Vectors in the caller's numbering, owned + ghost entries; on return psi's ghost
+ * entries hold the neighbour ranks' results.                                                                              */
+int ffm_solve_ordered_staged_d(ffm_ldu *ldu, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out);
+
 /* ------------------------------------------------------- synthetic plume case */
 /* Host-side driver (C++ over the entry points above) of one fireFoam time step on
  * the synthetic buoyant-plume box of SURVEY 8(d): rhoEqn, UEqn, YEEqn, 2 x pEqn in
