@@ -371,7 +371,9 @@ def flow_stages(nOwned, nGhost, lowerAddr, upperAddr, upper, lower, ghostStage):
 
 class FlowOrder:
     """The dependency order of the coefficients an lduMatrix held when this was made (ffm_flow_order): lduMatrix.flow_order(), or
-    lduMatrix.flow_order_staged() on one rank of a decomposed matrix (collective)"""
+    lduMatrix.flow_order_staged() on one rank of a decomposed matrix (collective).  One kind of object: the single-rank order is the
+    staged one without ghost cells and with one stage; it reports nStages 0 and fits solve_ordered only, a staged one
+    solve_ordered_staged only"""
 
     def __init__(self, A, staged=False):
         h = C.c_void_p()

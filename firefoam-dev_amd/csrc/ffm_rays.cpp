@@ -48,85 +48,28 @@ extern "C" int ffm_ray_schedule(int px, int py, int pz, int bx, int by, int bz, 
 #include <vector>
 void ffm_set_error(const char *fmt, ...);
 
-extern "C" int ffm_flow_levels(int nCells, int nFaces, const int *lowerAddr, const int *upperAddr, const double *upper, const double *lower,
-                               int *order, int *nLevels)
+// Kahn over one rank's rows: nOwned cells with rows, nGhost ghost cells (indices nOwned ..) that are sources of the stage another
+// rank found.  Finds level (longest dependency path in the owned sub-graph) and stage (below) of every owned cell and the order
+// stage-major, level-major inside a stage, ascending cell index inside a level.  Without ghost cells every stage is 0 and the order
+// is the level-major one.  `who`: the public function, for the messages, which speak of ghost cells where `staged`; stage may be null.
+static int flow_kahn(const char *who, bool staged, int nOwned, int nGhost, int nFaces, const int *lowerAddr, const int *upperAddr, const double *upper,
+                     const double *lower, const int *ghostStage, int *stage, int *order, int *nLevels)
 {
-    if (nCells < 0 || nFaces < 0 || (nFaces && (!lowerAddr || !upperAddr || !upper || !lower)) || (nCells && !order) || !nLevels) return FFM_ERR_ARG;
-    const int N = nCells, F = nFaces;
-    for (int f = 0; f < F; f++)
-        if (lowerAddr[f] < 0 || lowerAddr[f] >= N || upperAddr[f] < 0 || upperAddr[f] >= N) {
-            ffm_set_error("ffm_flow_levels: face %d joins cells %d and %d of %d", f, lowerAddr[f], upperAddr[f], N);
-            return FFM_ERR_ARG;
-        }
-    // successors of every cell (the rows that need it), CSR
-    std::vector<int> start(N + 1, 0), indeg(N, 0);
-    for (int f = 0; f < F; f++) {
-        if (lower[f] != 0) { start[lowerAddr[f] + 1]++; indeg[upperAddr[f]]++; }
-        if (upper[f] != 0) { start[upperAddr[f] + 1]++; indeg[lowerAddr[f]]++; }
-    }
-    for (int c = 0; c < N; c++) start[c + 1] += start[c];
-    std::vector<int> succ(start[N]), fill(start.begin(), start.end() - 1);
-    for (int f = 0; f < F; f++) {
-        if (lower[f] != 0) succ[fill[lowerAddr[f]]++] = upperAddr[f];
-        if (upper[f] != 0) succ[fill[upperAddr[f]]++] = lowerAddr[f];
-    }
-    std::vector<int> lev(N, 0), queue;
-    queue.reserve(N);
-    for (int c = 0; c < N; c++) if (!indeg[c]) queue.push_back(c);
-    int nLev = 0;
-    for (size_t q = 0; q < queue.size(); q++) {
-        const int c = queue[q];
-        nLev = nLev > lev[c] + 1 ? nLev : lev[c] + 1;
-        for (int k = start[c]; k < start[c + 1]; k++) {
-            const int r = succ[k];
-            if (lev[r] < lev[c] + 1) lev[r] = lev[c] + 1;
-            if (--indeg[r] == 0) queue.push_back(r);
-        }
-    }
-    if ((int)queue.size() != N) {
-        ffm_set_error("ffm_flow_levels: the non-zero off-diagonal coefficients form a cycle through %d of %d cells: "
-                      "the matrix is not triangular under any cell order", N - (int)queue.size(), N);
-        return FFM_ERR_UNSUPPORTED;
-    }
-    // level-major, ascending cell index inside a level
-    std::vector<int> pos(nLev + 1, 0);
-    for (int c = 0; c < N; c++) pos[lev[c] + 1]++;
-    for (int i = 0; i < nLev; i++) pos[i + 1] += pos[i];
-    for (int c = 0; c < N; c++) order[pos[lev[c]]++] = c;
-    *nLevels = nLev;
-    return FFM_OK;
-}
-
-// ------------------------------------------------------------------------------- stages of a ray matrix on one rank's sub-domain ---
-// The decomposed form of the order above.  A rank holds rows for its nOwned cells; its nGhost ghost cells (indices nOwned ..) are
-// sources whose stage another rank found.  The stage of a cell is the largest number of rank crossings on any upstream path to it:
-// stage[c] = max over the cells u that row c needs of stage[u] (u owned) or ghostStage[u] + 1 (u a ghost cell), 0 without any.  All
-// rows of stage s then need owned cells of stage <= s and ghost cells of stage < s only: a rank solves them in one sweep once the
-// ghost values of the stages before have arrived.  order: the owned cells stage-major, inside a stage level-major by the levels of
-// ffm_flow_levels on the owned sub-graph (ascending cell index inside a level) -- a non-zero owned column has a stage no larger
-// and a level smaller than its row's, so it stands before the row.  nLevels: the level count of the owned sub-graph.  Edges
-// between two ghost cells, and the edge that a ghost cell's (absent) row would need, are no dependencies of this rank.  A cycle among
-// the owned cells is refused; a cycle through several ranks is invisible here (ffm_flow_order_create_staged bounds the stages).
-extern "C" int ffm_flow_stages(int nOwned, int nGhost, int nFaces, const int *lowerAddr, const int *upperAddr, const double *upper,
-                               const double *lower, const int *ghostStage, int *stage, int *order, int *nLevels)
-{
-    if (nOwned < 0 || nGhost < 0 || nFaces < 0 || (nFaces && (!lowerAddr || !upperAddr || !upper || !lower)) || (nGhost && !ghostStage) ||
-        (nOwned && (!stage || !order)) || !nLevels) return FFM_ERR_ARG;
     const int N = nOwned, M = nOwned + nGhost, F = nFaces;
     for (int f = 0; f < F; f++)
         if (lowerAddr[f] < 0 || lowerAddr[f] >= M || upperAddr[f] < 0 || upperAddr[f] >= M) {
-            ffm_set_error("ffm_flow_stages: face %d joins cells %d and %d of %d (+ %d ghost cells)", f, lowerAddr[f], upperAddr[f], N, nGhost);
+            if (staged) ffm_set_error("%s: face %d joins cells %d and %d of %d (+ %d ghost cells)", who, f, lowerAddr[f], upperAddr[f], N, nGhost);
+            else ffm_set_error("%s: face %d joins cells %d and %d of %d", who, f, lowerAddr[f], upperAddr[f], N);
             return FFM_ERR_ARG;
         }
-    for (int g = 0; g < nGhost; g++) if (ghostStage[g] < 0) { ffm_set_error("ffm_flow_stages: ghost cell %d has stage %d", g, ghostStage[g]); return FFM_ERR_ARG; }
+    for (int g = 0; g < nGhost; g++) if (ghostStage[g] < 0) { ffm_set_error("%s: ghost cell %d has stage %d", who, g, ghostStage[g]); return FFM_ERR_ARG; }
     // the owned sub-graph (successors of every owned cell, CSR) and what the ghost cells impose
     std::vector<int> start(N + 1, 0), indeg(N, 0), stg(N, 0);
     auto each_edge = [&](auto &&owned, auto &&ghost) {          // edge src -> dst: row dst needs cell src
-        for (int f = 0; f < F; f++) for (int k = 0; k < 2; k++) {
-            if ((k ? upper[f] : lower[f]) == 0) continue;
-            const int src = k ? upperAddr[f] : lowerAddr[f], dst = k ? lowerAddr[f] : upperAddr[f];
-            if (dst >= N) continue;
-            if (src < N) owned(src, dst); else ghost(src - N, dst);
+        auto edge = [&](int src, int dst) { if (dst < N) { if (src < N) owned(src, dst); else ghost(src - N, dst); } };
+        for (int f = 0; f < F; f++) {
+            if (lower[f] != 0) edge(lowerAddr[f], upperAddr[f]);
+            if (upper[f] != 0) edge(upperAddr[f], lowerAddr[f]);
         }
     };
     each_edge([&](int s, int d) { start[s + 1]++; indeg[d]++; },
@@ -145,25 +88,53 @@ extern "C" int ffm_flow_stages(int nOwned, int nGhost, int nFaces, const int *lo
         for (int k = start[c]; k < start[c + 1]; k++) {
             const int r = succ[k];
             if (lev[r] < lev[c] + 1) lev[r] = lev[c] + 1;
-            if (stg[r] < stg[c]) stg[r] = stg[c];
+            if (nGhost && stg[r] < stg[c]) stg[r] = stg[c];          // (without ghost cells every stage stays 0)
             if (--indeg[r] == 0) queue.push_back(r);
         }
     }
     if ((int)queue.size() != N) {
-        ffm_set_error("ffm_flow_stages: the non-zero off-diagonal coefficients form a cycle through %d of %d owned cells: "
-                      "the matrix is not triangular under any cell order", N - (int)queue.size(), N);
+        ffm_set_error("%s: the non-zero off-diagonal coefficients form a cycle through %d of %d %scells: "
+                      "the matrix is not triangular under any cell order", who, N - (int)queue.size(), N, staged ? "owned " : "");
         return FFM_ERR_UNSUPPORTED;
     }
-    // stage-major, level-major inside a stage, ascending cell index inside a level: two stable counting sorts, by level, then by stage
-    std::vector<int> byLev(N), pos(nLev + 1, 0);
+    // two stable counting sorts, by level, then by stage (the identity where there is one stage: left out)
+    std::vector<int> pos(nLev + 1, 0);
     for (int c = 0; c < N; c++) pos[lev[c] + 1]++;
     for (int i = 0; i < nLev; i++) pos[i + 1] += pos[i];
-    for (int c = 0; c < N; c++) byLev[pos[lev[c]]++] = c;
-    pos.assign(nStg + 1, 0);
-    for (int c = 0; c < N; c++) pos[stg[c] + 1]++;
-    for (int i = 0; i < nStg; i++) pos[i + 1] += pos[i];
-    for (int i = 0; i < N; i++) { const int c = byLev[i]; order[pos[stg[c]]++] = c; }
-    for (int c = 0; c < N; c++) stage[c] = stg[c];
+    for (int c = 0; c < N; c++) order[pos[lev[c]]++] = c;
+    if (nStg > 1) {
+        const std::vector<int> byLev(order, order + N);
+        pos.assign(nStg + 1, 0);
+        for (int c = 0; c < N; c++) pos[stg[c] + 1]++;
+        for (int i = 0; i < nStg; i++) pos[i + 1] += pos[i];
+        for (int i = 0; i < N; i++) { const int c = byLev[i]; order[pos[stg[c]]++] = c; }
+    }
+    if (stage) for (int c = 0; c < N; c++) stage[c] = stg[c];
     *nLevels = nLev;
     return FFM_OK;
+}
+
+extern "C" int ffm_flow_levels(int nCells, int nFaces, const int *lowerAddr, const int *upperAddr, const double *upper, const double *lower,
+                               int *order, int *nLevels)
+{
+    if (nCells < 0 || nFaces < 0 || (nFaces && (!lowerAddr || !upperAddr || !upper || !lower)) || (nCells && !order) || !nLevels) return FFM_ERR_ARG;
+    return flow_kahn("ffm_flow_levels", false, nCells, 0, nFaces, lowerAddr, upperAddr, upper, lower, nullptr, nullptr, order, nLevels);
+}
+
+// ------------------------------------------------------------------------------- stages of a ray matrix on one rank's sub-domain ---
+// The decomposed form of the order above.  A rank holds rows for its nOwned cells; its nGhost ghost cells (indices nOwned ..) are
+// sources whose stage another rank found.  The stage of a cell is the largest number of rank crossings on any upstream path to it:
+// stage[c] = max over the cells u that row c needs of stage[u] (u owned) or ghostStage[u] + 1 (u a ghost cell), 0 without any.  All
+// rows of stage s then need owned cells of stage <= s and ghost cells of stage < s only: a rank solves them in one sweep once the
+// ghost values of the stages before have arrived.  order: the owned cells stage-major, inside a stage level-major by the levels of
+// ffm_flow_levels on the owned sub-graph (ascending cell index inside a level) -- a non-zero owned column has a stage no larger
+// and a level smaller than its row's, so it stands before the row.  nLevels: the level count of the owned sub-graph.  Edges
+// between two ghost cells, and the edge that a ghost cell's (absent) row would need, are no dependencies of this rank.  A cycle among
+// the owned cells is refused; a cycle through several ranks is invisible here (ffm_flow_order_create_staged bounds the stages).
+extern "C" int ffm_flow_stages(int nOwned, int nGhost, int nFaces, const int *lowerAddr, const int *upperAddr, const double *upper,
+                               const double *lower, const int *ghostStage, int *stage, int *order, int *nLevels)
+{
+    if (nOwned < 0 || nGhost < 0 || nFaces < 0 || (nFaces && (!lowerAddr || !upperAddr || !upper || !lower)) || (nGhost && !ghostStage) ||
+        (nOwned && (!stage || !order)) || !nLevels) return FFM_ERR_ARG;
+    return flow_kahn("ffm_flow_stages", true, nOwned, nGhost, nFaces, lowerAddr, upperAddr, upper, lower, ghostStage, stage, order, nLevels);
 }

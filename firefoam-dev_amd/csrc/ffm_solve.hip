@@ -833,59 +833,103 @@ extern "C" int ffm_solve_d(ffm_ldu *A, int solver, int precond, double tol, doub
     return FFM_OK;
 }
 
+// ------------------------------------------------------------------ exact one-sweep solves: what they share ---
+// A solve that is one substitution sweep (ffm_solve_triangular_rows_d, the flow-ordered solves) still reports OpenFOAM's
+// normalised residuals of the start value and of the result.  ranks: the sums are taken over all ranks (the Amul refreshes psi's
+// ghost entries), else over this rank's rows as they stand -- nothing then reaches another rank: no ghost refresh, no all-reduce,
+// and one host synchronisation fewer.  The single-rank path keeps the row kernel for the Amul with sumA (ffm_k_spmv_sumA may take
+// the tiled kernel, another summation order).  Vectors in the internal numbering.
+static int exact_solve_begin(ffm_ldu *A, bool ranks, const double *psi, const double *source, double **rA, ffm_perf *out)
+{
+    double *sumA, *Apsi;
+    FFM_TRY(ffm_ldu_work(A, 1, &sumA)); FFM_TRY(ffm_ldu_work(A, 2, &Apsi)); FFM_TRY(ffm_ldu_work(A, 3, rA));
+    FFM_TRY(scalar_op(A->ctx, OP_RESET));
+    FFM_TRY(ranks ? ffm_k_spmv_sumA(A, psi, Apsi, sumA) : ffm_k_spmv_sumA_rows(A, psi, Apsi, sumA));
+    return norm_and_initial(A, psi, source, Apsi, sumA, *rA, out, nullptr, nullptr, !ranks);
+}
+// v[0 .. n) -> their sum (isMax 0) or maximum (1) over the ranks; n <= 4
+static int allreduce_host_values(ffm_ctx *c, double *v, int n, int isMax)
+{
+    if (c->nRanks <= 1 && !c->comm) return FFM_OK;
+    FFM_TRY(ffm_h2d(c, c->scal_d + S_TMP0, v, sizeof(double) * n));
+    FFM_TRY(isMax ? ffm_allreduce_minmax(c, S_TMP0, 1, n) : ffm_allreduce_slots(c, S_TMP0, n));
+    return ffm_d2h(c, v, c->scal_d + S_TMP0, sizeof(double) * n);
+}
+// What the sweep left.  nIterations 1; converged says whether the substitution WAS the solve: sum |source - A psi| <= 1e-10
+// sum |source| (an exact substitution leaves rounding, ~1e-15; a matrix that is not triangular in the order of the sweep leaves
+// O(1)).  The test is on the unnormalised sums because OpenFOAM's normFactor is round-off wherever the solution is uniform over
+// the rows.  psiCaller: where psi goes back to in the caller's numbering, or null.  The abort word of the dataflow sweeps is
+// reported last, with ranks on every rank.
+static int exact_solve_record(ffm_ldu *A, bool ranks, const char *who, double *psi, const double *source, double *rA, double *psiCaller, ffm_perf *out)
+{
+    ffm_ctx *c = A->ctx; const long N = A->nOwned;
+    // ranks: the residual's Amul refreshes psi's ghost entries, which hold the neighbours' results on return.  (A matrix without a
+    // ghost exchange and interfaces -- the single-rank ordered solve -- gets the same launch from either routine.)
+    FFM_TRY(ranks ? ffm_k_residual(A, psi, source, rA) : ffm_k_residual_rows(A, psi, source, rA));
+    FFM_TRY(ffm_k_summag(c, rA, N, S_TMP0));
+    FFM_TRY(ffm_k_summag(c, source, N, S_TMP1));
+    if (ranks) FFM_TRY(ffm_allreduce_slots(c, S_TMP0, 2));
+    FFM_TRY(scalar_op(c, OP_RES));                                                  // (reads S_TMP0 only)
+    if (psiCaller) FFM_TRY(ffm_from_internal(A, psi, psiCaller));
+    FFM_TRY(ffm_read_scalars(c));
+    out->initialResidual = c->scal_h[S_RES0]; out->finalResidual = c->scal_h[S_RES];
+    out->nIterations = 1; out->singular = 0;
+    out->converged = (c->scal_h[S_TMP0] <= 1e-10 * c->scal_h[S_TMP1]) ? 1 : 0;      // (false for NaN too)
+    const int rcAbort = ffm_sweep_check_abort(A);
+    if (!ranks) return rcAbort;
+    double ab = rcAbort != FFM_OK ? 1.0 : 0.0;
+    FFM_TRY(allreduce_host_values(c, &ab, 1, 1));
+    if (rcAbort != FFM_OK) return rcAbort;
+    if (ab != 0.0) { ffm_set_error("%s: a dataflow sweep timed out on another rank", who); return FFM_ERR_HIP; }
+    return FFM_OK;
+}
+
 // The exact solve of a matrix that is triangular in the matrix's cell order, on this rank's rows alone: calcReciprocalD of a
 // triangular matrix is 1/diag, and one DILU application is then the forward (lower-triangular) or the backward (upper-triangular)
 // substitution in face order -- psi = A^-1 source, one sweep pair, no Krylov iteration.  Nothing here reaches another rank (no
 // ghost refresh, no sum over ranks): faces towards ghost cells must carry zero coefficients, their terms belong in `source`.
-// out: nIterations 1; initialResidual and finalResidual are OpenFOAM's normalised residuals of the start value and of the
-// result, with the sums taken over this rank's rows.  converged says whether the substitution WAS the solve:
-// sum |source - A psi| <= 1e-10 sum |source| (an exact substitution leaves rounding, ~1e-15; a matrix that is not triangular
-// in this order -- a wrong renaming, a ghost face left in -- leaves O(1)).  The test is on the unnormalised sums because
-// OpenFOAM's normFactor is round-off wherever the solution is uniform over the rows.  The matrix is the bound one
-// (ffm_ldu_bind_coeffs_native_d), vectors in the library's cell order.
+// out: as exact_solve_record leaves it, the sums taken over this rank's rows (converged 0: a wrong renaming, a ghost face left
+// in).  The matrix is the bound one (ffm_ldu_bind_coeffs_native_d), vectors in the library's cell order.
 extern "C" int ffm_solve_triangular_rows_d(ffm_ldu *A, double *psi_d, const double *source_d, ffm_perf *out)
 {
     if (!A || !psi_d || !source_d || !out) { ffm_set_error("ffm_solve_triangular_rows_d: null argument"); return FFM_ERR_ARG; }
     if (!A->identity || !A->ifaces.empty()) { ffm_set_error("ffm_solve_triangular_rows_d: needs the library's cell order and no coupled patches"); return FFM_ERR_UNSUPPORTED; }
     memset(out, 0, sizeof(*out));
     FFM_HIP(hipSetDevice(A->ctx->device));
-    ffm_ctx *c = A->ctx; const long N = A->nOwned;
-    double *sumA, *Apsi, *rA;
-    FFM_TRY(ffm_ldu_work(A, 1, &sumA)); FFM_TRY(ffm_ldu_work(A, 2, &Apsi)); FFM_TRY(ffm_ldu_work(A, 3, &rA));
-    FFM_TRY(scalar_op(c, OP_RESET));
-    FFM_TRY(ffm_k_spmv_sumA_rows(A, psi_d, Apsi, sumA));
-    FFM_TRY(norm_and_initial(A, psi_d, source_d, Apsi, sumA, rA, out, nullptr, nullptr, true));
+    double *rA;
+    FFM_TRY(exact_solve_begin(A, false, psi_d, source_d, &rA, out));
     FFM_TRY(ffm_precond_setup_i(A, FFM_DILU));
     FFM_TRY(ffm_precond_apply_i(A, FFM_DILU, false, source_d, psi_d));
-    FFM_TRY(ffm_k_residual_rows(A, psi_d, source_d, rA));
-    FFM_TRY(ffm_k_summag(c, rA, N, S_TMP0));
-    FFM_TRY(scalar_op(c, OP_RES));
-    FFM_TRY(ffm_k_summag(c, source_d, N, S_TMP1));
-    FFM_TRY(ffm_read_scalars(c));
-    out->initialResidual = c->scal_h[S_RES0]; out->finalResidual = c->scal_h[S_RES];
-    out->nIterations = 1; out->singular = 0;
-    out->converged = (c->scal_h[S_TMP0] <= 1e-10 * c->scal_h[S_TMP1]) ? 1 : 0;      // (false for NaN too)
-    FFM_TRY(ffm_sweep_check_abort(A));
-    return FFM_OK;
+    return exact_solve_record(A, false, "ffm_solve_triangular_rows_d", psi_d, source_d, rA, nullptr, out);
 }
 
 // ------------------------------------------------------------------ flow-ordered exact solve ---
 // A matrix with at most one non-zero off-diagonal coefficient per face and no cycle among them (an upwind ray equation,
 // fvm::div(Ji, Ii) + fvm::Sp(k omega, Ii), on any mesh with planar faces) is triangular under the level-major order of its own
-// dependency graph (ffm_flow_levels, ffm_rays.cpp).  ffm_flow_order keeps that order on the device: int[N], 4 N bytes, in the
-// matrix's internal cell numbering.  ffm_solve_ordered_d is one dataflow sweep in that order -- the machinery of k_flow_sweep:
-// chunks of 256 positions by ticket, published values, bounded waits -- in which a row waits for the cells of its non-zero
-// entries only, lower faces then upper faces in face order, one division: bitwise the serial forward substitution.
-// The order is never trusted: a pass over the rows first checks, against the coefficients the matrix holds now, that the column
-// of every non-zero entry stands earlier in the order than its row, and the sweep is launched only where no row fails -- a row
-// then waits only for positions of its own or an earlier chunk, whose workgroups are running or done.
+// dependency graph (ffm_flow_levels, ffm_rays.cpp).  On a decomposed mesh the cells' graph is still acyclic, the ranks' is not
+// (rank A feeds B across one cut face, B feeds A across another), so the order is staged by cells: stage = the largest number of
+// rank crossings on any upstream path (ffm_flow_stages), and the order is stage-major.  The rows of stage s need owned cells of
+// stage <= s and ghost cells of stage < s.  ffm_flow_order keeps the order on the device, int[N] in the matrix's internal cell
+// numbering, and the stages' position ranges on the host; a single-rank order is the case of no ghost cells and one stage [0, N):
+// it holds no stage arrays (4 N bytes of device memory), and neither making nor using it communicates.
+// The solve, per stage: one dataflow sweep over the positions of the stage -- the machinery of k_flow_sweep: chunks of 256
+// positions by ticket, published values, bounded waits -- in which a row waits for the owned cells of its non-zero entries only,
+// lower faces then upper faces in face order, one division: bitwise the serial forward substitution.  A ghost column is read from
+// psi's ghost entry, which the exchange behind the stage before filled; then all ranks refresh psi's ghost entries once and the
+// next stage follows: nStages - 1 exchanges per solve, none on a single rank.
+// The order is never trusted: a pass over the rows first checks, against the coefficients the matrix holds now, that the owned
+// column of every non-zero entry stands earlier in the order than its row, in no later stage, and that a ghost column's stage is
+// below the row's; the sweeps are launched only where no row fails on any rank -- a row then waits only for positions of its own
+// or an earlier chunk, whose workgroups are running or done.  With ranks, every decision a rank takes on what it alone sees (a
+// local cycle, a row the order does not fit, the abort word) is all-reduced first, so all ranks leave a call the same way.
 struct ffm_flow_order {
     ffm_ctx *ctx = nullptr;
-    int N = 0, nLevels = 0;
+    bool staged = false;           // made by ffm_flow_order_create_staged: the entry point decides, not the matrix
+    int N = 0, nGhost = 0, nLevels = 0;
+    int nStages = 1;               // over all ranks, the same on every rank
     int *order = nullptr;          // [N] device: position -> internal cell
-    // the staged form of a decomposed matrix (ffm_flow_order_create_staged; nStages == 0: a single-rank order)
-    int nGhost = 0, nStages = 0;   // nStages: over all ranks, the same on every rank
     std::vector<int> stageStart;   // [nStages + 1] host: stage s = the positions [stageStart[s], stageStart[s + 1]) of order
+    // null in a single-rank order: every cell in stage 0, no ghost cells
     int *stage = nullptr;          // [N] device: stage of every owned cell (internal numbering)
     int *ghostStage = nullptr;     // [nGhost] device: stage of every ghost cell on the rank that owns it
 };
@@ -902,303 +946,26 @@ struct OrderedArgs {
 __global__ void k_order_pos(long n, const int *__restrict__ order, int *__restrict__ pos)
 { GRID_STRIDE(p, n) pos[order[p]] = (int)p; }
 
-// rows with a non-zero entry whose column does not stand earlier in the order: block partial counts
+// non-zero entries whose owned column does not stand earlier in the order than the row or has a later stage, or whose ghost
+// column's stage is not below the row's: block partial counts.  stage == null (a branch the whole grid takes alike): every cell in
+// stage 0, and a ghost column fails
 template <int W>
 __global__ __launch_bounds__(256) void k_order_check(LduView v, const double *__restrict__ upper, const double *__restrict__ lower,
-                                                     const int *__restrict__ pos, double *__restrict__ partials)
+                                                     const int *__restrict__ pos, const int *__restrict__ stage,
+                                                     const int *__restrict__ ghostStage, double *__restrict__ partials)
 {
     __shared__ double sm[4];
     double bad = 0.0;
     GRID_STRIDE(i, (long)v.N) {
         const int c = (int)i;
         RowEnt<W> L, U; load_lower<W>(v, c, L); load_upper<W>(v, c, U);
-        const int pc = pos[c];
+        const int pc = pos[c], sc = stage ? stage[c] : 0;
 #pragma unroll
         for (int s = 0; s < W; s++) {
-            if (L.on[s] && lower[L.f[s]] != 0.0 && !(pos[L.nb[s]] < pc)) bad += 1.0;
-            if (U.on[s] && upper[U.f[s]] != 0.0 && !(pos[U.nb[s]] < pc)) bad += 1.0;
-        }
-    }
-    const double r = block_sum(bad, sm);
-    if (threadIdx.x == 0) partials[blockIdx.x] = r;
-}
-
-template <int W>
-__global__ __launch_bounds__(FLOW_T) void k_flow_ordered(OrderedArgs a)
-{
-    __shared__ unsigned shTicket;
-    if (threadIdx.x == 0) shTicket = atomicAdd(&a.ticket[0], 1u);
-    __syncthreads();
-    const int p = (int)shTicket * FLOW_T + threadIdx.x;
-    if (p >= a.N) return;
-    const int c = a.order[p];
-    unsigned spins = 0;
-    RowEnt<W> L, U; load_lower<W>(a.v, c, L); load_upper<W>(a.v, c, U);
-    double al[W], au[W], pl[W], pu[W];
-#pragma unroll
-    for (int s = 0; s < W; s++) {
-        al[s] = a.lower[L.f[s]]; au[s] = a.upper[U.f[s]];
-        L.on[s] = L.on[s] && al[s] != 0.0; U.on[s] = U.on[s] && au[s] != 0.0;      // a zero entry is no dependency: not waited for
-        pl[s] = 0.0; pu[s] = 0.0;
-    }
-    const double bc = a.source[c], dg = a.diag[c];
-    bool done = false; do { if (!done) {
-        bool ready = true;
-#pragma unroll
-        for (int s = 0; s < W; s++) {
-            if (L.on[s]) { pl[s] = s_ld(&a.mf[L.nb[s]]); ready = ready && !f_pending(pl[s]); }
-            if (U.on[s]) { pu[s] = s_ld(&a.mf[U.nb[s]]); ready = ready && !f_pending(pu[s]); }
-        }
-        if (ready) {
-            double val = bc;
-#pragma unroll
-            for (int s = 0; s < W; s++) if (L.on[s]) val -= al[s] * pl[s];
-#pragma unroll
-            for (int s = 0; s < W; s++) if (U.on[s]) val -= au[s] * pu[s];
-            val /= dg;
-            a.psi[c] = val;
-            f_st(&a.mf[c], val);
-            done = true;
-        } else done = f_give_up(spins, a.ticket, a.nap);
-    } } while (__ballot(!done) != 0ull);
-}
-
-static bool ordered_single_rank(const ffm_ldu *A)
-{ return A->nOwned == A->nCells && A->ifaces.empty() && A->ghNbrRank.empty(); }
-
-// the off-diagonals the matrix holds, once, as the faces of the internal numbering in the caller's face order of every row
-// (columns >= nOwned: ghost cells)
-static int download_faces(ffm_ldu *A, std::vector<int> &l, std::vector<int> &u, std::vector<double> &cu, std::vector<double> &cl)
-{
-    const int nS = A->nSlices, T = A->upTotal;
-    std::vector<int> upOff((size_t)nS + 1, 0), upNbr((size_t)T);
-    std::vector<double> up((size_t)T), lo((size_t)T);
-    FFM_TRY(ffm_d2h(A->ctx, upOff.data(), A->upOff, sizeof(int) * ((size_t)nS + 1)));
-    FFM_TRY(ffm_d2h(A->ctx, upNbr.data(), A->upNbr, sizeof(int) * (size_t)T));
-    FFM_TRY(ffm_d2h(A->ctx, up.data(), A->upper, sizeof(double) * (size_t)T));
-    if (A->lower != A->upper) FFM_TRY(ffm_d2h(A->ctx, lo.data(), A->lower, sizeof(double) * (size_t)T)); else lo = up;
-    l.reserve(A->nFaces); u.reserve(A->nFaces); cu.reserve(A->nFaces); cl.reserve(A->nFaces);
-    for (int sl = 0; sl < nS; sl++) {
-        const int base = upOff[sl], w = (upOff[sl + 1] - base) >> 6;
-        for (int lane = 0; lane < 64; lane++) for (int s = 0; s < w; s++) {
-            const int e = base + s * 64 + lane, n = upNbr[e];
-            if (n < 0) continue;
-            l.push_back(sl * 64 + lane); u.push_back(n); cu.push_back(up[e]); cl.push_back(lo[e]);
-        }
-    }
-    return FFM_OK;
-}
-
-extern "C" int ffm_flow_order_create(ffm_ldu *A, ffm_flow_order **out)
-{
-    if (!A || !out) { ffm_set_error("ffm_flow_order_create: null argument"); return FFM_ERR_ARG; }
-    *out = nullptr;
-    if (!ordered_single_rank(A)) {
-        ffm_set_error("ffm_flow_order_create: single rank only (the matrix has ghost cells, processor interfaces or a ghost exchange)");
-        return FFM_ERR_UNSUPPORTED;
-    }
-    FFM_HIP(hipSetDevice(A->ctx->device));
-    const int N = A->nOwned;
-    std::vector<int> l, u; std::vector<double> cu, cl;
-    FFM_TRY(download_faces(A, l, u, cu, cl));
-    std::vector<int> order((size_t)std::max(N, 1));
-    int nLev = 0;
-    FFM_TRY(ffm_flow_levels(N, (int)l.size(), l.data(), u.data(), cu.data(), cl.data(), order.data(), &nLev));
-    ffm_flow_order *o = new ffm_flow_order;
-    o->ctx = A->ctx; o->N = N; o->nLevels = nLev;
-    if (hipMalloc((void **)&o->order, sizeof(int) * (size_t)std::max(N, 1)) != hipSuccess) { delete o; ffm_set_error("ffm_flow_order_create: out of device memory"); return FFM_ERR_HIP; }
-    const int rc = ffm_h2d(A->ctx, o->order, order.data(), sizeof(int) * (size_t)N);
-    if (rc != FFM_OK) { hipFree(o->order); delete o; return rc; }
-    *out = o;
-    return FFM_OK;
-}
-extern "C" int ffm_flow_order_nlevels(const ffm_flow_order *o) { return o ? o->nLevels : FFM_ERR_ARG; }
-extern "C" int ffm_flow_order_destroy(ffm_flow_order *o)
-{
-    if (!o) return FFM_OK;
-    hipSetDevice(o->ctx->device);
-    hipStreamSynchronize(o->ctx->stream);
-    hipFree(o->order); hipFree(o->stage); hipFree(o->ghostStage);
-    delete o;
-    return FFM_OK;
-}
-
-extern "C" int ffm_solve_ordered_d(ffm_ldu *A, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out)
-{
-    if (!A || !o || !psi_d || !source_d || !out) { ffm_set_error("ffm_solve_ordered_d: null argument"); return FFM_ERR_ARG; }
-    if (!ordered_single_rank(A)) {
-        ffm_set_error("ffm_solve_ordered_d: single rank only (the matrix has ghost cells, processor interfaces or a ghost exchange)");
-        return FFM_ERR_UNSUPPORTED;
-    }
-    if (o->ctx != A->ctx || o->N != A->nOwned) { ffm_set_error("ffm_solve_ordered_d: the order belongs to another matrix (%d cells, matrix %d)", o->N, A->nOwned); return FFM_ERR_UNSUPPORTED; }
-    memset(out, 0, sizeof(*out));
-    FFM_HIP(hipSetDevice(A->ctx->device));
-    ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned;
-    // ---- 1. the order against the coefficients the matrix holds now; nothing else is launched before the count is back
-    double *posBuf;
-    FFM_TRY(ffm_ldu_work(A, 23, &posBuf));
-    int *pos = (int *)posBuf;
-    const int g = sgrid(N);
-    hipLaunchKernelGGL(k_order_pos, dim3(g), dim3(256), 0, s, N, o->order, pos);
-    FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_order_check<W>, dim3(g), dim3(256), 0, s, ffm_view(A), A->upper, A->lower, pos, c->partials_d));
-    FFM_HIP(hipGetLastError());
-    FFM_TRY(partial_sum_to(c, g, S_TMP0));
-    FFM_TRY(ffm_read_scalars(c));
-    if (!(c->scal_h[S_TMP0] == 0.0)) {
-        ffm_set_error("ffm_solve_ordered_d: %.0f non-zero entries do not precede their rows in this order (a stale order, the order of "
-                      "another matrix, or a matrix that is not triangular): nothing solved", c->scal_h[S_TMP0]);
-        return FFM_ERR_UNSUPPORTED;
-    }
-    // ---- 2. the sweep, on the internal numbering
-    const double *si = source_d; double *pi = psi_d;
-    if (!A->identity) {
-        FFM_TRY(ffm_to_internal(A, source_d, 1, &si));
-        const double *pin; FFM_TRY(ffm_to_internal(A, psi_d, 2, &pin)); pi = A->permIn[2];
-    }
-    double *sumA, *Apsi, *rA;
-    FFM_TRY(ffm_ldu_work(A, 1, &sumA)); FFM_TRY(ffm_ldu_work(A, 2, &Apsi)); FFM_TRY(ffm_ldu_work(A, 3, &rA));
-    FFM_TRY(scalar_op(c, OP_RESET));
-    FFM_TRY(ffm_k_spmv_sumA_rows(A, pi, Apsi, sumA));
-    FFM_TRY(norm_and_initial(A, pi, si, Apsi, sumA, rA, out, nullptr, nullptr, true));
-    OrderedArgs a{};
-    a.v = ffm_view(A); a.N = A->nOwned; a.nap = 1; a.order = o->order;
-    a.upper = A->upper; a.lower = A->lower; a.diag = A->diag; a.source = si; a.psi = pi; a.ticket = A->sweepTicket;
-    FFM_TRY(ffm_ldu_work(A, 20, &a.mf));
-    hipLaunchKernelGGL(k_flow_fill, dim3(g), dim3(256), 0, s, N, a.mf, (double *)nullptr, (double *)nullptr, a.ticket);
-    const int nChunk = (A->nOwned + FLOW_T - 1) / FLOW_T;
-    if (nChunk > 0) FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_flow_ordered<W>, dim3(nChunk), dim3(FLOW_T), 0, s, a));
-    FFM_HIP(hipGetLastError());
-    // ---- 3. what the solve left
-    FFM_TRY(ffm_k_residual_rows(A, pi, si, rA));
-    FFM_TRY(ffm_k_summag(c, rA, N, S_TMP0));
-    FFM_TRY(scalar_op(c, OP_RES));
-    FFM_TRY(ffm_k_summag(c, si, N, S_TMP1));
-    if (!A->identity) FFM_TRY(ffm_from_internal(A, pi, psi_d));
-    FFM_TRY(ffm_read_scalars(c));
-    out->initialResidual = c->scal_h[S_RES0]; out->finalResidual = c->scal_h[S_RES];
-    out->nIterations = 1; out->singular = 0;
-    out->converged = (c->scal_h[S_TMP0] <= 1e-10 * c->scal_h[S_TMP1]) ? 1 : 0;      // (false for NaN too)
-    FFM_TRY(ffm_sweep_check_abort(A));
-    return FFM_OK;
-}
-
-// ------------------------------------------------------------------ flow-ordered exact solve, decomposed ---
-// On a decomposed mesh the cells' dependency graph is still acyclic, the ranks' is not (rank A feeds B across one cut face, B
-// feeds A across another), so the order is staged by cells: stage = the largest number of rank crossings on any upstream path
-// (ffm_flow_stages, ffm_rays.cpp).  The rows of stage s need owned cells of stage <= s and ghost cells of stage < s:
-// every rank solves its stage-s rows in one dataflow sweep -- k_flow_ordered's machinery over the positions of the stage, a ghost
-// column read from psi's ghost entry, which the exchange behind the stage before filled -- then all ranks refresh psi's ghost
-// entries once, and stage s + 1 follows: nStages - 1 exchanges per solve.  Every decision a rank takes on what it alone sees (a
-// local cycle, a row the order does not fit, the abort word) is all-reduced first, so all ranks leave a call the same way.
-static bool ordered_decomposed(const ffm_ldu *A)
-{
-    // a ghost exchange, or a rank of several that has no neighbour (and then no ghost cell)
-    return A->ifaces.empty() && (!A->ghNbrRank.empty() || (A->ctx->nRanks > 1 && A->nCells == A->nOwned));
-}
-// v[0 .. n) -> their sum (isMax 0) or maximum (1) over the ranks; n <= 4
-static int allreduce_host_values(ffm_ctx *c, double *v, int n, int isMax)
-{
-    if (c->nRanks <= 1 && !c->comm) return FFM_OK;
-    FFM_TRY(ffm_h2d(c, c->scal_d + S_TMP0, v, sizeof(double) * n));
-    FFM_TRY(isMax ? ffm_allreduce_minmax(c, S_TMP0, 1, n) : ffm_allreduce_slots(c, S_TMP0, n));
-    return ffm_d2h(c, v, c->scal_d + S_TMP0, sizeof(double) * n);
-}
-__global__ void k_int_to_double(long n, const int *__restrict__ a, double *__restrict__ x)
-{ GRID_STRIDE(i, n) x[i] = (double)a[i]; }
-__global__ void k_double_to_int(long n, const double *__restrict__ x, int *__restrict__ a)
-{ GRID_STRIDE(i, n) a[i] = (int)x[i]; }
-
-extern "C" int ffm_flow_order_create_staged(ffm_ldu *A, ffm_flow_order **out)
-{
-    if (!A || !out) { ffm_set_error("ffm_flow_order_create_staged: null argument"); return FFM_ERR_ARG; }
-    *out = nullptr;
-    if (!ordered_decomposed(A)) {
-        ffm_set_error("ffm_flow_order_create_staged: needs a matrix with a ghost exchange (ffm_ldu_set_ghost_exchange) and no processor "
-                      "interfaces; ffm_flow_order_create is the single-rank form");
-        return FFM_ERR_UNSUPPORTED;
-    }
-    FFM_HIP(hipSetDevice(A->ctx->device));
-    ffm_ctx *c = A->ctx; hipStream_t s = c->stream;
-    const int N = A->nOwned, nG = A->nCells - A->nOwned;
-    std::vector<int> l, u; std::vector<double> cu, cl;
-    FFM_TRY(download_faces(A, l, u, cu, cl));
-    double *x;                                             // the stages as a cell field: what the ghost exchange moves
-    FFM_TRY(ffm_ldu_work(A, 23, &x));
-    ffm_flow_order *o = new ffm_flow_order;
-    o->ctx = c; o->N = N; o->nGhost = nG;
-    // from here on every rank takes every step: what fails locally is carried in `fail` to the all-reduce of the round
-    int fail = FFM_OK;
-    if (hipMalloc((void **)&o->order, sizeof(int) * (size_t)std::max(N, 1)) != hipSuccess || hipMalloc((void **)&o->stage, sizeof(int) * (size_t)std::max(N, 1)) != hipSuccess ||
-        hipMalloc((void **)&o->ghostStage, sizeof(int) * (size_t)std::max(nG, 1)) != hipSuccess) {
-        ffm_set_error("ffm_flow_order_create_staged: out of device memory"); fail = FFM_ERR_HIP;
-    }
-    double total = (double)nG;                             // a path with more rank crossings than there are ghost cells revisits one
-    int rc = allreduce_host_values(c, &total, 1, 0);
-    std::vector<int> order((size_t)std::max(N, 1)), stage((size_t)std::max(N, 1), 0), ghostStage((size_t)std::max(nG, 1), 0), got((size_t)std::max(nG, 1), 0);
-    int nLev = 0, nStages = 0;
-    bool anyFail = false, cycle = false;
-    while (rc == FFM_OK) {
-        if (fail == FFM_OK) fail = ffm_flow_stages(N, nG, (int)l.size(), l.data(), u.data(), cu.data(), cl.data(), ghostStage.data(), stage.data(), order.data(), &nLev);
-        int top = -1;
-        for (int i = 0; i < N; i++) top = std::max(top, stage[i]);
-        // the owned cells' stages to the neighbours' ghost cells: one ghost exchange of a double field (small integers: exact)
-        if (fail == FFM_OK) rc = ffm_h2d(c, o->stage, stage.data(), sizeof(int) * (size_t)N);
-        if (rc != FFM_OK) break;
-        if (fail == FFM_OK && N) hipLaunchKernelGGL(k_int_to_double, dim3(sgrid(N)), dim3(256), 0, s, (long)N, o->stage, x);
-        else if ((rc = ffm_dzero(c, x, sizeof(double) * (size_t)A->nCells)) != FFM_OK) break;
-        if ((rc = ffm_ghost_exchange(A, x)) != FFM_OK) break;
-        bool changed = false;
-        if (fail == FFM_OK && nG) {
-            hipLaunchKernelGGL(k_double_to_int, dim3(sgrid(nG)), dim3(256), 0, s, (long)nG, x + N, o->ghostStage);
-            if ((rc = ffm_d2h(c, got.data(), o->ghostStage, sizeof(int) * (size_t)nG)) != FFM_OK) break;
-            changed = got != ghostStage;
-            ghostStage = got;
-        }
-        double v[3] = {changed ? 1.0 : 0.0, fail != FFM_OK ? 1.0 : 0.0, (double)top};
-        if ((rc = allreduce_host_values(c, v, 3, 1)) != FFM_OK) break;
-        anyFail = v[1] != 0.0; cycle = v[2] > total; nStages = (int)v[2] + 1;
-        if (anyFail || cycle || v[0] == 0.0) break;
-    }
-    if (rc == FFM_OK && hipGetLastError() != hipSuccess) { ffm_set_error("ffm_flow_order_create_staged: a kernel launch failed"); rc = FFM_ERR_HIP; }
-    if (rc == FFM_OK && fail != FFM_OK) rc = fail;        // (ffm_flow_stages has set the message)
-    else if (rc == FFM_OK && anyFail) { ffm_set_error("ffm_flow_order_create_staged: refused on another rank (a cycle among its cells, or out of memory)"); rc = FFM_ERR_UNSUPPORTED; }
-    else if (rc == FFM_OK && cycle) {
-        ffm_set_error("ffm_flow_order_create_staged: a stage above the %.0f ghost cells of all ranks: the non-zero off-diagonal coefficients "
-                      "form a cycle through several ranks", total);
-        rc = FFM_ERR_UNSUPPORTED;
-    }
-    if (rc == FFM_OK) {
-        o->nLevels = nLev; o->nStages = nStages;
-        o->stageStart.assign((size_t)nStages + 1, 0);
-        for (int i = 0; i < N; i++) o->stageStart[stage[i] + 1]++;
-        for (int k = 0; k < nStages; k++) o->stageStart[k + 1] += o->stageStart[k];
-        rc = ffm_h2d(c, o->order, order.data(), sizeof(int) * (size_t)N);
-    }
-    if (rc != FFM_OK) { ffm_flow_order_destroy(o); return rc; }
-    *out = o;
-    return FFM_OK;
-}
-extern "C" int ffm_flow_order_nstages(const ffm_flow_order *o) { return o ? o->nStages : FFM_ERR_ARG; }
-
-// k_order_check for a staged order: non-zero entries whose owned column does not stand earlier than the row or has a later stage,
-// or whose ghost column's stage is not below the row's
-template <int W>
-__global__ __launch_bounds__(256) void k_order_check_staged(LduView v, const double *__restrict__ upper, const double *__restrict__ lower,
-                                                            const int *__restrict__ pos, const int *__restrict__ stage,
-                                                            const int *__restrict__ ghostStage, double *__restrict__ partials)
-{
-    __shared__ double sm[4];
-    double bad = 0.0;
-    GRID_STRIDE(i, (long)v.N) {
-        const int c = (int)i;
-        RowEnt<W> L, U; load_lower<W>(v, c, L); load_upper<W>(v, c, U);
-        const int pc = pos[c], sc = stage[c];
-#pragma unroll
-        for (int s = 0; s < W; s++) {
-            if (L.on[s] && lower[L.f[s]] != 0.0 && !(pos[L.nb[s]] < pc && stage[L.nb[s]] <= sc)) bad += 1.0;
+            if (L.on[s] && lower[L.f[s]] != 0.0 && !(pos[L.nb[s]] < pc && (!stage || stage[L.nb[s]] <= sc))) bad += 1.0;
             if (U.on[s] && upper[U.f[s]] != 0.0) {
                 const int n = U.nb[s];
-                if (n < v.N ? !(pos[n] < pc && stage[n] <= sc) : !(ghostStage[n - v.N] < sc)) bad += 1.0;
+                if (n < v.N ? !(pos[n] < pc && (!stage || stage[n] <= sc)) : !(stage && ghostStage[n - v.N] < sc)) bad += 1.0;
             }
         }
     }
@@ -1206,11 +973,12 @@ __global__ __launch_bounds__(256) void k_order_check_staged(LduView v, const dou
     if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
-// k_flow_ordered over the positions [p0, p1) of one stage: a row waits on the published array for its owned columns only (cells
-// of this launch's earlier positions, or of an earlier launch: published then); a ghost column is psi's ghost entry as the
-// exchange behind an earlier stage left it, a plain load -- a kernel boundary lies in between
-template <int W>
-__global__ __launch_bounds__(FLOW_T) void k_flow_ordered_stage(OrderedArgs a, int p0, int p1)
+// the sweep over the positions [p0, p1) of one stage: a row waits on the published array for its owned columns only (cells of this
+// launch's earlier positions, or of an earlier launch: published then); a ghost column is psi's ghost entry as the exchange behind
+// an earlier stage left it, a plain load -- a kernel boundary lies in between.  GHOSTS false, a matrix without ghost cells: every
+// column is owned, `own` folds into U.on
+template <int W, bool GHOSTS>
+__global__ __launch_bounds__(FLOW_T) void k_flow_ordered(OrderedArgs a, int p0, int p1)
 {
     __shared__ unsigned shTicket;
     if (threadIdx.x == 0) shTicket = atomicAdd(&a.ticket[0], 1u);
@@ -1226,7 +994,7 @@ __global__ __launch_bounds__(FLOW_T) void k_flow_ordered_stage(OrderedArgs a, in
     for (int s = 0; s < W; s++) {
         al[s] = a.lower[L.f[s]]; au[s] = a.upper[U.f[s]];
         L.on[s] = L.on[s] && al[s] != 0.0; U.on[s] = U.on[s] && au[s] != 0.0;      // a zero entry is no dependency: not waited for
-        own[s] = U.on[s] && U.nb[s] < a.N;
+        own[s] = U.on[s] && (!GHOSTS || U.nb[s] < a.N);
         pl[s] = 0.0; pu[s] = (U.on[s] && !own[s]) ? a.psi[U.nb[s]] : 0.0;
     }
     const double bc = a.source[c], dg = a.diag[c];
@@ -1251,19 +1019,149 @@ __global__ __launch_bounds__(FLOW_T) void k_flow_ordered_stage(OrderedArgs a, in
     } } while (__ballot(!done) != 0ull);
 }
 
-extern "C" int ffm_solve_ordered_staged_d(ffm_ldu *A, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out)
+static bool ordered_single_rank(const ffm_ldu *A)
+{ return A->nOwned == A->nCells && A->ifaces.empty() && A->ghNbrRank.empty(); }
+static bool ordered_decomposed(const ffm_ldu *A)
 {
-    if (!A || !o || !psi_d || !source_d || !out) { ffm_set_error("ffm_solve_ordered_staged_d: null argument"); return FFM_ERR_ARG; }
-    if (!ordered_decomposed(A)) {
-        ffm_set_error("ffm_solve_ordered_staged_d: needs a matrix with a ghost exchange (ffm_ldu_set_ghost_exchange) and no processor "
-                      "interfaces; ffm_solve_ordered_d is the single-rank form");
-        return FFM_ERR_UNSUPPORTED;
+    // a ghost exchange, or a rank of several that has no neighbour (and then no ghost cell)
+    return A->ifaces.empty() && (!A->ghNbrRank.empty() || (A->ctx->nRanks > 1 && A->nCells == A->nOwned));
+}
+// the refusal of a matrix that is not the entry point's kind (a matrix without ghost cells on a context of several ranks is both)
+static int ordered_refuse(const ffm_ldu *A, bool ranks, const char *who)
+{
+    if (ranks ? ordered_decomposed(A) : ordered_single_rank(A)) return FFM_OK;
+    if (ranks) ffm_set_error("%s: needs a matrix with a ghost exchange (ffm_ldu_set_ghost_exchange) and no processor interfaces; "
+                             "ffm_flow_order_create and ffm_solve_ordered_d are the single-rank form", who);
+    else ffm_set_error("%s: single rank only (the matrix has ghost cells, processor interfaces or a ghost exchange)", who);
+    return FFM_ERR_UNSUPPORTED;
+}
+
+// the off-diagonals the matrix holds, once, as the faces of the internal numbering in the caller's face order of every row
+// (columns >= nOwned: ghost cells)
+static int download_faces(ffm_ldu *A, std::vector<int> &l, std::vector<int> &u, std::vector<double> &cu, std::vector<double> &cl)
+{
+    const int nS = A->nSlices, T = A->upTotal;
+    std::vector<int> upOff((size_t)nS + 1, 0), upNbr((size_t)T);
+    std::vector<double> up((size_t)T), lo((size_t)T);
+    FFM_TRY(ffm_d2h(A->ctx, upOff.data(), A->upOff, sizeof(int) * ((size_t)nS + 1)));
+    FFM_TRY(ffm_d2h(A->ctx, upNbr.data(), A->upNbr, sizeof(int) * (size_t)T));
+    FFM_TRY(ffm_d2h(A->ctx, up.data(), A->upper, sizeof(double) * (size_t)T));
+    if (A->lower != A->upper) FFM_TRY(ffm_d2h(A->ctx, lo.data(), A->lower, sizeof(double) * (size_t)T)); else lo = up;
+    l.reserve(A->nFaces); u.reserve(A->nFaces); cu.reserve(A->nFaces); cl.reserve(A->nFaces);
+    for (int sl = 0; sl < nS; sl++) {
+        const int base = upOff[sl], w = (upOff[sl + 1] - base) >> 6;
+        for (int lane = 0; lane < 64; lane++) for (int s = 0; s < w; s++) {
+            const int e = base + s * 64 + lane, n = upNbr[e];
+            if (n < 0) continue;
+            l.push_back(sl * 64 + lane); u.push_back(n); cu.push_back(up[e]); cl.push_back(lo[e]);
+        }
     }
+    return FFM_OK;
+}
+
+__global__ void k_int_to_double(long n, const int *__restrict__ a, double *__restrict__ x)
+{ GRID_STRIDE(i, n) x[i] = (double)a[i]; }
+__global__ void k_double_to_int(long n, const double *__restrict__ x, int *__restrict__ a)
+{ GRID_STRIDE(i, n) a[i] = (int)x[i]; }
+
+static int flow_order_create(ffm_ldu *A, bool ranks, ffm_flow_order **out)
+{
+    const char *who = ranks ? "ffm_flow_order_create_staged" : "ffm_flow_order_create";
+    if (!A || !out) { ffm_set_error("%s: null argument", who); return FFM_ERR_ARG; }
+    *out = nullptr;
+    FFM_TRY(ordered_refuse(A, ranks, who));
+    FFM_HIP(hipSetDevice(A->ctx->device));
+    ffm_ctx *c = A->ctx; hipStream_t s = c->stream;
+    const int N = A->nOwned, nG = A->nCells - A->nOwned;
+    std::vector<int> l, u; std::vector<double> cu, cl;
+    FFM_TRY(download_faces(A, l, u, cu, cl));
+    double *x = nullptr;                                   // the stages as a cell field: what the ghost exchange moves
+    if (ranks) FFM_TRY(ffm_ldu_work(A, 23, &x));
+    ffm_flow_order *o = new ffm_flow_order;
+    o->ctx = c; o->staged = ranks; o->N = N; o->nGhost = nG;
+    // from here on every rank takes every step: what fails locally is carried in `fail` to the all-reduce of the round
+    int fail = FFM_OK, rc = FFM_OK;
+    if (hipMalloc((void **)&o->order, sizeof(int) * (size_t)std::max(N, 1)) != hipSuccess ||
+        (ranks && (hipMalloc((void **)&o->stage, sizeof(int) * (size_t)std::max(N, 1)) != hipSuccess ||
+                   hipMalloc((void **)&o->ghostStage, sizeof(int) * (size_t)std::max(nG, 1)) != hipSuccess))) {
+        ffm_set_error("%s: out of device memory", who); fail = FFM_ERR_HIP;
+    }
+    std::vector<int> order((size_t)std::max(N, 1)), stage((size_t)std::max(N, 1), 0);      // (a single rank: every stage 0)
+    bool anyFail = false, cycle = false;
+    double total = (double)nG;                             // a path with more rank crossings than there are ghost cells revisits one
+    if (!ranks) {
+        if (fail == FFM_OK) fail = ffm_flow_levels(N, (int)l.size(), l.data(), u.data(), cu.data(), cl.data(), order.data(), &o->nLevels);
+    } else {
+        // the fixpoint over the ranks: all ghost stages 0, then rounds of ffm_flow_stages, one ghost exchange of the stages and one
+        // all-reduce of "some ghost stage changed", until none does
+        rc = allreduce_host_values(c, &total, 1, 0);
+        std::vector<int> ghostStage((size_t)std::max(nG, 1), 0), got((size_t)std::max(nG, 1), 0);
+        while (rc == FFM_OK) {
+            if (fail == FFM_OK) fail = ffm_flow_stages(N, nG, (int)l.size(), l.data(), u.data(), cu.data(), cl.data(), ghostStage.data(), stage.data(), order.data(), &o->nLevels);
+            int top = -1;
+            for (int i = 0; i < N; i++) top = std::max(top, stage[i]);
+            // the owned cells' stages to the neighbours' ghost cells: one ghost exchange of a double field (small integers: exact)
+            if (fail == FFM_OK) rc = ffm_h2d(c, o->stage, stage.data(), sizeof(int) * (size_t)N);
+            if (rc != FFM_OK) break;
+            if (fail == FFM_OK && N) hipLaunchKernelGGL(k_int_to_double, dim3(sgrid(N)), dim3(256), 0, s, (long)N, o->stage, x);
+            else if ((rc = ffm_dzero(c, x, sizeof(double) * (size_t)A->nCells)) != FFM_OK) break;
+            if ((rc = ffm_ghost_exchange(A, x)) != FFM_OK) break;
+            bool changed = false;
+            if (fail == FFM_OK && nG) {
+                hipLaunchKernelGGL(k_double_to_int, dim3(sgrid(nG)), dim3(256), 0, s, (long)nG, x + N, o->ghostStage);
+                if ((rc = ffm_d2h(c, got.data(), o->ghostStage, sizeof(int) * (size_t)nG)) != FFM_OK) break;
+                changed = got != ghostStage;
+                ghostStage = got;
+            }
+            double v[3] = {changed ? 1.0 : 0.0, fail != FFM_OK ? 1.0 : 0.0, (double)top};
+            if ((rc = allreduce_host_values(c, v, 3, 1)) != FFM_OK) break;
+            anyFail = v[1] != 0.0; cycle = v[2] > total; o->nStages = (int)v[2] + 1;
+            if (anyFail || cycle || v[0] == 0.0) break;
+        }
+    }
+    if (rc == FFM_OK && hipGetLastError() != hipSuccess) { ffm_set_error("%s: a kernel launch failed", who); rc = FFM_ERR_HIP; }
+    if (rc == FFM_OK && fail != FFM_OK) rc = fail;        // (ffm_flow_levels, ffm_flow_stages or the allocation has set the message)
+    else if (rc == FFM_OK && anyFail) { ffm_set_error("%s: refused on another rank (a cycle among its cells, or out of memory)", who); rc = FFM_ERR_UNSUPPORTED; }
+    else if (rc == FFM_OK && cycle) {
+        ffm_set_error("%s: a stage above the %.0f ghost cells of all ranks: the non-zero off-diagonal coefficients form a cycle through several ranks", who, total);
+        rc = FFM_ERR_UNSUPPORTED;
+    }
+    if (rc == FFM_OK) {
+        o->stageStart.assign((size_t)o->nStages + 1, 0);
+        for (int i = 0; i < N; i++) o->stageStart[stage[i] + 1]++;
+        for (int k = 0; k < o->nStages; k++) o->stageStart[k + 1] += o->stageStart[k];
+        rc = ffm_h2d(c, o->order, order.data(), sizeof(int) * (size_t)N);
+    }
+    if (rc != FFM_OK) { ffm_flow_order_destroy(o); return rc; }
+    *out = o;
+    return FFM_OK;
+}
+extern "C" int ffm_flow_order_create(ffm_ldu *A, ffm_flow_order **out) { return flow_order_create(A, false, out); }
+extern "C" int ffm_flow_order_create_staged(ffm_ldu *A, ffm_flow_order **out) { return flow_order_create(A, true, out); }
+extern "C" int ffm_flow_order_nlevels(const ffm_flow_order *o) { return o ? o->nLevels : FFM_ERR_ARG; }
+extern "C" int ffm_flow_order_nstages(const ffm_flow_order *o) { return o ? (o->staged ? o->nStages : 0) : FFM_ERR_ARG; }
+extern "C" int ffm_flow_order_destroy(ffm_flow_order *o)
+{
+    if (!o) return FFM_OK;
+    hipSetDevice(o->ctx->device);
+    hipStreamSynchronize(o->ctx->stream);
+    hipFree(o->order); hipFree(o->stage); hipFree(o->ghostStage);
+    delete o;
+    return FFM_OK;
+}
+
+// ranks false: the single-rank entry.  It may be called on a rank of several and never communicates: no all-reduce, no exchange
+// (one stage), the norms of this rank's rows
+static int solve_ordered(ffm_ldu *A, const ffm_flow_order *o, bool ranks, double *psi_d, const double *source_d, ffm_perf *out)
+{
+    const char *who = ranks ? "ffm_solve_ordered_staged_d" : "ffm_solve_ordered_d";
+    if (!A || !o || !psi_d || !source_d || !out) { ffm_set_error("%s: null argument", who); return FFM_ERR_ARG; }
+    FFM_TRY(ordered_refuse(A, ranks, who));
     memset(out, 0, sizeof(*out));
     FFM_HIP(hipSetDevice(A->ctx->device));
     ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned;
     // ---- 1. the order against the coefficients the matrix holds now, over all ranks; nothing else is launched or exchanged before
-    const bool mine = o->ctx == A->ctx && o->N == A->nOwned && o->nGhost == A->nCells - A->nOwned && o->nStages > 0;
+    const bool mine = o->ctx == A->ctx && o->staged == ranks && o->N == A->nOwned && o->nGhost == A->nCells - A->nOwned;
     const int g = sgrid(N);
     double v[3] = {1.0, (double)o->nStages, -(double)o->nStages};
     if (mine) {
@@ -1271,21 +1169,21 @@ extern "C" int ffm_solve_ordered_staged_d(ffm_ldu *A, const ffm_flow_order *o, d
         FFM_TRY(ffm_ldu_work(A, 23, &posBuf));
         int *pos = (int *)posBuf;
         hipLaunchKernelGGL(k_order_pos, dim3(g), dim3(256), 0, s, N, o->order, pos);
-        FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_order_check_staged<W>, dim3(g), dim3(256), 0, s, ffm_view(A), A->upper, A->lower, pos, o->stage, o->ghostStage, c->partials_d));
+        FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_order_check<W>, dim3(g), dim3(256), 0, s, ffm_view(A), A->upper, A->lower, pos, o->stage, o->ghostStage, c->partials_d));
         FFM_HIP(hipGetLastError());
         FFM_TRY(partial_sum_to(c, g, S_TMP0));
         FFM_TRY(ffm_read_scalars(c));
         v[0] = c->scal_h[S_TMP0];
     }
     const double bad = v[0];
-    FFM_TRY(allreduce_host_values(c, v, 3, 1));
+    if (ranks) FFM_TRY(allreduce_host_values(c, v, 3, 1));
     if (!(v[0] == 0.0) || v[1] != -v[2]) {
-        if (!mine) ffm_set_error("ffm_solve_ordered_staged_d: the order belongs to another matrix (%d cells, %d ghost cells, %d stages; matrix %d, %d): nothing solved",
-                                 o->N, o->nGhost, o->nStages, A->nOwned, A->nCells - A->nOwned);
-        else if (!(bad == 0.0)) ffm_set_error("ffm_solve_ordered_staged_d: %.0f non-zero entries do not precede their rows in this order or reach a ghost cell of a "
-                                              "stage not below their row's (a stale order, the order of another matrix, or a matrix that is not triangular): nothing solved", bad);
-        else if (v[1] != -v[2]) ffm_set_error("ffm_solve_ordered_staged_d: the ranks' orders have %.0f to %.0f stages (orders of different matrices): nothing solved", -v[2], v[1]);
-        else ffm_set_error("ffm_solve_ordered_staged_d: the order was refused on another rank: nothing solved");
+        if (!mine) ffm_set_error("%s: the order belongs to another matrix (%d cells, %d ghost cells, %d stages, made by ffm_flow_order_create%s; matrix %d, %d): nothing solved",
+                                 who, o->N, o->nGhost, o->nStages, o->staged ? "_staged" : "", A->nOwned, A->nCells - A->nOwned);
+        else if (!(bad == 0.0)) ffm_set_error("%s: %.0f non-zero entries do not precede their rows in this order or reach a ghost cell of a stage not below their "
+                                              "row's (a stale order, the order of another matrix, or a matrix that is not triangular): nothing solved", who, bad);
+        else if (v[1] != -v[2]) ffm_set_error("%s: the ranks' orders have %.0f to %.0f stages (orders of different matrices): nothing solved", who, -v[2], v[1]);
+        else ffm_set_error("%s: the order was refused on another rank: nothing solved", who);
         return FFM_ERR_UNSUPPORTED;
     }
     // ---- 2. the stages, on the internal numbering
@@ -1294,11 +1192,8 @@ extern "C" int ffm_solve_ordered_staged_d(ffm_ldu *A, const ffm_flow_order *o, d
         FFM_TRY(ffm_to_internal(A, source_d, 1, &si));
         const double *pin; FFM_TRY(ffm_to_internal(A, psi_d, 2, &pin)); pi = A->permIn[2];
     }
-    double *sumA, *Apsi, *rA;
-    FFM_TRY(ffm_ldu_work(A, 1, &sumA)); FFM_TRY(ffm_ldu_work(A, 2, &Apsi)); FFM_TRY(ffm_ldu_work(A, 3, &rA));
-    FFM_TRY(scalar_op(c, OP_RESET));
-    FFM_TRY(ffm_k_spmv_sumA(A, pi, Apsi, sumA));
-    FFM_TRY(norm_and_initial(A, pi, si, Apsi, sumA, rA, out));
+    double *rA;
+    FFM_TRY(exact_solve_begin(A, ranks, pi, si, &rA, out));
     OrderedArgs a{};
     a.v = ffm_view(A); a.N = A->nOwned; a.nap = 1; a.order = o->order;
     a.upper = A->upper; a.lower = A->lower; a.diag = A->diag; a.source = si; a.psi = pi; a.ticket = A->sweepTicket;
@@ -1308,29 +1203,20 @@ extern "C" int ffm_solve_ordered_staged_d(ffm_ldu *A, const ffm_flow_order *o, d
         const int p0 = o->stageStart[st], p1 = o->stageStart[st + 1], nChunk = (p1 - p0 + FLOW_T - 1) / FLOW_T;
         if (nChunk > 0) {
             if (st > 0) FFM_TRY(ffm_dzero(c, a.ticket, sizeof(unsigned int)));          // the ticket counter; the abort word stays
-            FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL(k_flow_ordered_stage<W>, dim3(nChunk), dim3(FLOW_T), 0, s, a, p0, p1));
+            if (o->nGhost) FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_flow_ordered<W, true>), dim3(nChunk), dim3(FLOW_T), 0, s, a, p0, p1));
+            else FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_flow_ordered<W, false>), dim3(nChunk), dim3(FLOW_T), 0, s, a, p0, p1));
             FFM_HIP(hipGetLastError());
         }
         if (st + 1 < o->nStages) FFM_TRY(ffm_ghost_exchange(A, pi));                    // every rank, also one whose stage was empty
     }
-    // ---- 3. what the solve left (the residual's Amul refreshes psi's ghost entries: they hold the neighbours' results on return)
-    FFM_TRY(ffm_k_residual(A, pi, si, rA));
-    FFM_TRY(ffm_k_summag(c, rA, N, S_TMP0));
-    FFM_TRY(ffm_k_summag(c, si, N, S_TMP1));
-    FFM_TRY(ffm_allreduce_slots(c, S_TMP0, 2));
-    FFM_TRY(scalar_op(c, OP_RES));
-    if (!A->identity) FFM_TRY(ffm_from_internal(A, pi, psi_d));
-    FFM_TRY(ffm_read_scalars(c));
-    out->initialResidual = c->scal_h[S_RES0]; out->finalResidual = c->scal_h[S_RES];
-    out->nIterations = 1; out->singular = 0;
-    out->converged = (c->scal_h[S_TMP0] <= 1e-10 * c->scal_h[S_TMP1]) ? 1 : 0;      // (false for NaN too)
-    const int rcAbort = ffm_sweep_check_abort(A);
-    double ab = rcAbort != FFM_OK ? 1.0 : 0.0;
-    FFM_TRY(allreduce_host_values(c, &ab, 1, 1));
-    if (rcAbort != FFM_OK) return rcAbort;
-    if (ab != 0.0) { ffm_set_error("ffm_solve_ordered_staged_d: a dataflow sweep timed out on another rank"); return FFM_ERR_HIP; }
-    return FFM_OK;
+    // ---- 3. what the solve left
+    return exact_solve_record(A, ranks, who, pi, si, rA, A->identity ? nullptr : psi_d, out);
 }
+// `out` is zeroed before an order is refused (a null argument and a matrix of the other kind are refused before)
+extern "C" int ffm_solve_ordered_d(ffm_ldu *A, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out)
+{ return solve_ordered(A, o, false, psi_d, source_d, out); }
+extern "C" int ffm_solve_ordered_staged_d(ffm_ldu *A, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out)
+{ return solve_ordered(A, o, true, psi_d, source_d, out); }
 
 // ------------------------------------------------------------------ several systems with common off-diagonals ---
 // fvMatrix::solveSegregated of a vector equation and the species loop under a multivariateSelection scheme solve systems that differ in

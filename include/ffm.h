@@ -556,7 +556,10 @@ int ffm_flow_levels(int nCells, int nFaces, const int *lowerAddr, const int *upp
                     int *order /* [nCells] */, int *nLevels);
 /* The same order of the coefficients the matrix holds now (set or bound), kept on the device: int[nCells], 4 nCells bytes per
  * order.  Creating one downloads the off-diagonal coefficients once (set-up cost, like an agglomeration).  Single rank: a
- * matrix with ghost cells, processor interfaces or a ghost exchange is refused (FFM_ERR_UNSUPPORTED), as is a cyclic one.   */
+ * matrix with ghost cells, processor interfaces or a ghost exchange is refused (FFM_ERR_UNSUPPORTED), as is a cyclic one.
+ * This is the staged order below in the case of no ghost cells and one stage [0, nCells): one algorithm, and the single-rank
+ * entry points (this one, ffm_solve_ordered_d) are the ones that never communicate, also on a rank of several.  An order
+ * belongs to the entry point that made it: handed to the other kind's solve it is refused like another matrix's order.      */
 typedef struct ffm_flow_order ffm_flow_order;
 int ffm_flow_order_create(ffm_ldu *ldu, ffm_flow_order **out);
 int ffm_flow_order_nlevels(const ffm_flow_order *o);
@@ -568,7 +571,10 @@ int ffm_flow_order_destroy(ffm_flow_order *o);
  * returns FFM_ERR_UNSUPPORTED and psi_d is untouched.  out: nIterations 1, OpenFOAM's normalised residuals of the start value
  * and of the result; converged = 1 only where sum |source - A psi| <= 1e-10 sum |source| (the rule of
  * ffm_solve_triangular_rows_d).  Vectors in the caller's cell numbering: where the library renumbered the cells
- * (ffm_ldu_is_native_order() == 0) they go through the permutation the other solvers use.  Single rank only.              */
+ * (ffm_ldu_is_native_order() == 0) they go through the permutation the other solvers use.  Single rank only: the one-stage
+ * case of ffm_solve_ordered_staged_d, without its all-reduces and exchanges, the norms taken over this rank's rows.  An order of
+ * another matrix (another context or size, or one made by ffm_flow_order_create_staged) is refused with FFM_ERR_UNSUPPORTED
+ * before anything is launched; *out is zeroed before an order is refused, as in the staged call.                            */
 int ffm_solve_ordered_d(ffm_ldu *ldu, const ffm_flow_order *o, double *psi_d, const double *source_d, ffm_perf *out);
 
 /* ------------------------------------------------------- flow-ordered exact solve on a decomposed mesh, any partition */
@@ -607,7 +613,7 @@ int ffm_flow_order_nstages(const ffm_flow_order *o);
  * coefficients the matrix holds NOW (every non-zero owned column earlier in the order and of a stage <= the row's, every
  * non-zero ghost column of a stage < the row's) and the failure count is all-reduced with the stage counts: if any row on any
  * rank fails, or the ranks' orders differ in their stage count, ALL ranks return FFM_ERR_UNSUPPORTED with psi_d untouched,
- * before any sweep or exchange.  out: nIterations 1; OpenFOAM's normalised residuals of the start value and of the result and
+ * before any sweep or exchange (so does an order made by ffm_flow_order_create).  out: nIterations 1; OpenFOAM's normalised residuals of the start value and of the result and
  * converged (the rule of ffm_solve_ordered_d) with the sums over all ranks, the same on every rank.  A sweep that timed out on
  * any rank makes all ranks return FFM_ERR_HIP.  Vectors in the caller's numbering, owned + ghost entries; on return psi's ghost
  * entries hold the neighbour ranks' results.                                                                              */

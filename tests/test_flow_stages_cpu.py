@@ -4,7 +4,7 @@ with the ghost stages carried between the "ranks" in numpy until nothing changes
 takes over the communicator.  The stages equal the restatement on the merged mesh (tests/ray_stages.py: the longest path counting
 rank crossings), every rank's order is a permutation, stage-major, with every non-zero owned column before its row.  A ring
 through two ranks that neither sees locally exceeds the ghost-count bound within a few rounds; a cycle among a rank's own cells is
-refused by the call itself."""
+refused by the call itself.  Without ghost cells ffm_flow_stages is ffm_flow_levels: both are one Kahn pass."""
 import numpy as np
 import pytest
 
@@ -45,6 +45,20 @@ def test_stages_equal_the_merged_restatement(ffm, name, partitioner, world):
             assert np.all(np.diff(key) >= 0) and np.all(np.diff(order)[np.diff(key) == 0] > 0), (name, tag, s.rank)
         counts.append(int(want.max()) + 1)
     print("%s %s into %d: stages of the five directions %r" % (name, partitioner, world, counts))
+
+
+@pytest.mark.parametrize("name", MESHES + ["w8", "w32l30"])
+def test_without_ghost_cells_the_stages_are_the_levels(ffm, name):
+    m = R.mesh(name)
+    N = m.nCells
+    l, u = np.asarray(m.l, np.int64), np.asarray(m.u, np.int64)
+    for tag, d, omega in R.five_directions():
+        _, upper, lower = R.ray_matrix(m, d, omega)
+        want, nLevels = ffm.flow_levels(N, l, u, upper, lower)
+        stage, order, n = ffm.flow_stages(N, 0, l, u, upper, lower, np.zeros(0, np.int32))
+        assert not stage.any(), (name, tag)
+        assert np.array_equal(order, want), (name, tag)
+        assert n == nLevels, (name, tag)
 
 
 def test_a_ring_through_two_ranks_exceeds_the_ghost_count_bound(ffm):

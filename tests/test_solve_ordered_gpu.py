@@ -3,9 +3,14 @@
 arithmetic is fully specified -- on a box of two chunks of 256 positions in the library's numbering and in a random one, on
 polyhedral meshes of every row-width bucket above a hex's and on the steckler room; for four rays of different octants and
 (1,0,0).  Orders are reused and swapped on one matrix handle; an order that does not fit the matrix, a matrix that is not
-triangular and a decomposed matrix are refused before any sweep is launched."""
+triangular, a decomposed matrix and the order of a matrix of another size are refused before any sweep is launched.  The
+perf records -- the norms of the rank's rows alone, which the row kernels form -- are bit for bit those recorded from the commit
+before the single-rank solve became the one-stage case of the staged one (tests/golden/solve_ordered_perf.json, written by
+scripts/record_solve_ordered_perf.py); ffm_solve_triangular_rows_d shares the prologue and the epilogue and is pinned with it."""
 import ctypes as C
 import heapq
+import json
+import os
 
 import numpy as np
 import pytest
@@ -79,6 +84,43 @@ def case(ffm, O, name):
     return _cache[name]
 
 
+PERF_CASES = ["box", "box_random", "w32multi"]
+PERF_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "solve_ordered_perf.json")
+
+
+def perf_records(ffm, O, ctx):
+    """{key: [initialResidual.hex(), finalResidual.hex()]} of ffm_solve_ordered_d on the five rays of PERF_CASES from a finite
+    hashed start value, and of ffm_solve_triangular_rows_d on the all-positive ray of `box` (triangular in the library's order).
+    The ray matrices are asymmetric, so the tiled symmetric Amul is never theirs; `box` (336 cells) stands for the hex box"""
+    out = {}
+    for name in PERF_CASES:
+        k = case(ffm, O, name)
+        A = ffm.lduMatrix(ctx, k["N"], k["l"], k["u"])
+        for i, r in enumerate(k["rays"]):
+            A.set_coeffs(r["diag"], r["upper"], r["lower"])
+            order = A.flow_order()
+            psi = ctx.to_device(O.hash_u(90 + i, np.arange(k["N"])) - 0.25)
+            perf = A.solve_ordered(order, psi, ctx.to_device(r["source"]))
+            assert perf["nIterations"] == 1 and perf["converged"] == 1, perf
+            out["ordered/%s/%s" % (name, r["tag"])] = [perf["initialResidual"].hex(), perf["finalResidual"].hex()]
+            order.close()
+        A.close()
+    k = case(ffm, O, "box")
+    r = k["rays"][0]
+    assert not r["upper"].any()                                      # the all-positive ray: lower-triangular as numbered
+    A = ffm.lduMatrix(ctx, k["N"], k["l"], k["u"]).set_coeffs(r["diag"], r["upper"], r["lower"])
+    assert A.native_order
+    psi, src = ctx.to_device(O.hash_u(97, np.arange(k["N"])) - 0.25), ctx.to_device(r["source"])
+    fn, perf = ffm.lib().ffm_solve_triangular_rows_d, ffm.binding.Perf()
+    fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ffm.binding.Perf)], C.c_int
+    assert fn(A.h, C.c_void_p(psi.data_ptr()), C.c_void_p(src.data_ptr()), C.byref(perf)) == 0
+    assert perf.nIterations == 1 and perf.converged == 1
+    assert np.allclose(psi.cpu().numpy(), r["want"], rtol=1e-12, atol=0)      # (the DILU sweep multiplies by 1/diag: not bitwise)
+    out["triangular_rows/box/%s" % r["tag"]] = [perf.initialResidual.hex(), perf.finalResidual.hex()]
+    A.close()
+    return out
+
+
 def bits(t):
     return t.cpu().numpy().view(np.int64)
 
@@ -149,6 +191,30 @@ def test_the_order_of_the_opposite_ray_is_refused_and_psi_untouched(O, ffm, ctx,
     psi, perf = solve(ctx, A, order, r["source"])
     assert np.array_equal(bits(psi), r["want"].view(np.int64)) and perf["converged"] == 1
     order.close(); A.close()
+
+
+def test_perf_records_are_those_of_the_commit_before_the_unification(O, ffm, ctx):
+    want = json.load(open(PERF_GOLDEN))
+    got = perf_records(ffm, O, ctx)
+    for key in sorted(got):
+        print(key, got[key], "recorded", want["records"].get(key))
+    assert len(got) == 16 and got == want["records"]
+    assert all(float.fromhex(a) > 0 and float.fromhex(a) > float.fromhex(b) >= 0 for a, b in got.values())
+
+
+def test_the_order_of_a_matrix_of_another_size_is_refused_and_psi_untouched(O, ffm, ctx):
+    k, k2 = case(ffm, O, "box"), case(ffm, O, "w8")
+    assert k["N"] != k2["N"]
+    r, r2 = k["rays"][0], k2["rays"][0]
+    A = ffm.lduMatrix(ctx, k["N"], k["l"], k["u"]).set_coeffs(r["diag"], r["upper"], r["lower"])
+    B = ffm.lduMatrix(ctx, k2["N"], k2["l"], k2["u"]).set_coeffs(r2["diag"], r2["upper"], r2["lower"])
+    order = A.flow_order()
+    start = O.hash_u(8, np.arange(k2["N"]))
+    psi = ctx.to_device(start)
+    with pytest.raises(ffm.FfmError, match=r"\(-5\)"):
+        B.solve_ordered(order, psi, ctx.to_device(r2["source"]))
+    assert np.array_equal(bits(psi), start.view(np.int64))
+    order.close(); A.close(); B.close()
 
 
 def test_a_laplacian_has_no_flow_order(O, ffm, ctx):
