@@ -229,6 +229,8 @@ def lib():
         "ffm_fvc_rho_eqn": ([vp, C.c_double] + [dp] * 4, C.c_int),
         "ffm_fvc_div_phiK_terms": ([vp, C.c_int] + [C.c_double] * 4 + [dp] * 14, C.c_int),
         "ffm_fvdom_ray_assemble_d": ([vp, hp] + [C.c_double] * 3 + [dp] * 9, C.c_int),
+        "ffm_fvdom_wall_coeffs_d": ([vp, C.c_int, C.c_int, hp, hp, C.c_double] + [dp] * 8, C.c_int),
+        "ffm_fvdom_sum_rays_d": ([vp, C.c_int, dp, dp], C.c_int),
         "ffm_mesh_nboundary": ([vp], C.c_int),
         "ffm_mesh_nnative": ([vp], C.c_int),
         "ffm_faces_to_native": ([vp, hp, dp], C.c_int),
@@ -962,6 +964,13 @@ class Thermo:
         _check(lib().ffm_thermo_correct_d(self.h, he.numel(), self._Y(Y), P(he), P(p), P(T), P(psi), P(mu), P(alpha)), "ffm_thermo_correct_d")
         self.ctx.sync()             # the outputs are the caller's tensors: complete before torch's stream reads them
 
+    def properties(self, Y, T, psi=None, mu=None, alpha=None):
+        """psi, mu, alpha at the given temperature T (no iteration: the patch faces that fix T)"""
+        self.ctx._ready()
+        P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(lib().ffm_thermo_properties_d(self.h, T.numel(), self._Y(Y), P(T), P(psi), P(mu), P(alpha)), "ffm_thermo_properties_d")
+        self.ctx.sync()
+
     def he(self, Y, T, out):
         self.ctx._ready()
         _check(lib().ffm_thermo_he_d(self.h, T.numel(), self._Y(Y), C.c_void_p(T.data_ptr()), C.c_void_p(out.data_ptr())), "ffm_thermo_he_d")
@@ -1125,6 +1134,14 @@ class PyrolysisPanel:
     def set_reaction(self, A, Ta, Tcrit, n):
         """the Arrhenius solid reaction of constant/panelRegion/reactions (ffm_pyro_set_reaction)"""
         _check(lib().ffm_pyro_set_reaction(self.h, float(A), float(Ta), float(Tcrit), float(n)), "ffm_pyro_set_reaction")
+
+    def set_solids(self, virgin, charred):
+        """the solids of constant/panelRegion/thermo.solid, each (rho, Cp, kappa, Hf); the uniform start state is formed again from them
+        (ffm_pyro_set_solids), so this comes before the first step"""
+        v = np.ascontiguousarray(virgin, np.float64); c = np.ascontiguousarray(charred, np.float64)
+        if v.shape != (4,) or c.shape != (4,):
+            raise ValueError("a solid is (rho, Cp, kappa, Hf)")
+        _check(lib().ffm_pyro_set_solids(self.h, _hp(v), _hp(c)), "ffm_pyro_set_solids")
 
     def set_incident_radiation(self, Qr):
         """`QrIncident` of the fixedIncidentRadiation patch [W/m2]: a scalar, or one value per column (numpy array or torch CUDA tensor)"""

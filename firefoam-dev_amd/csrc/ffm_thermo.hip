@@ -55,7 +55,8 @@ __device__ __forceinline__ const double *coeffs(const Mix &m, double T) { return
 __device__ __forceinline__ double th_Cp(const Mix &m, double T) { const double *a = coeffs(m, T); return ((((a[4] * T + a[3]) * T + a[2]) * T + a[1]) * T + a[0]); }
 __device__ __forceinline__ double th_Ha(const double *a, double T) { return ((((a[4] / 5.0 * T + a[3] / 4.0) * T + a[2] / 3.0) * T + a[1] / 2.0) * T + a[0]) * T + a[5]; }
 __device__ __forceinline__ double th_Hs(const Mix &m, double T) { return th_Ha(coeffs(m, T), T) - th_Ha(m.low, TH_TSTD); }
-__device__ __forceinline__ double th_limit(const Mix &m, double T) { return fmin(fmax(T, m.Tlow), m.Thigh); }
+// janafThermo::limit: T unchanged unless T < Tlow || T > Thigh, so a NaN iterate stays NaN (fmin / fmax alone would turn it into Tlow)
+__device__ __forceinline__ double th_limit(const Mix &m, double T) { return (T < m.Tlow || T > m.Thigh) ? fmin(fmax(T, m.Tlow), m.Thigh) : T; }
 
 // hePsiThermo::calculate for n cells (or the faces of a patch: the same arithmetic on the patch-face mixture)
 __global__ void k_thermo_correct(long n, ThermoTable t, ThermoPtrs y, const double *__restrict__ he, const double *__restrict__ p,

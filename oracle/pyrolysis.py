@@ -61,8 +61,11 @@ class Panel:
     of the last correct() -- that is what fvc::laplacian(kappa(), T()) in solveEnergy and the coupled patch's kappa(*this) see."""
 
     def __init__(self, nCol, nLay=8, thickness=0.0127, area=1.0, T0=298.15, Yw0=1.0, model="reactingOneDim", alphaScheme="linear",
-                 kappaScheme="linear", back=None, radiation=None):
+                 kappaScheme="linear", back=None, radiation=None, wood=None, char=None, reaction=None):
         assert model in ("reactingOneDim", "reactingOneDim21")
+        # the solids of thermo.solid and the reaction of `reactions`: the module's (cases/pyrolysis1D) unless given
+        self.wood, self.char = WOOD if wood is None else wood, CHAR if char is None else char
+        self.reaction = dict(REACTION if reaction is None else reaction)
         self.model, self.alphaScheme, self.kappaScheme, self.back, self.radiation = model, alphaScheme, kappaScheme, back, radiation
         self.nCol, self.nLay = nCol, nLay
         self.dx = thickness / nLay
@@ -70,7 +73,7 @@ class Panel:
         self.V = self.A * self.dx
         self.Yw0 = Yw0
         self.Yw = np.full((nCol, nLay), Yw0)
-        self.rho = np.full((nCol, nLay), 1.0 / (Yw0 / WOOD.rho + (1 - Yw0) / CHAR.rho)) if Yw0 < 1 else np.full((nCol, nLay), WOOD.rho)
+        self.rho = np.full((nCol, nLay), 1.0 / (Yw0 / self.wood.rho + (1 - Yw0) / self.char.rho)) if Yw0 < 1 else np.full((nCol, nLay), self.wood.rho)
         self.T = np.full((nCol, nLay), float(T0))
         self.h = self.Cp() * (self.T - TSTD)
         self.alpha = self.kappa_vol() / self.Cp()             # alpha_ of the constructor's correct()
@@ -81,16 +84,16 @@ class Panel:
 
     def Cp(self, Yw=None):
         Yw = self.Yw if Yw is None else Yw
-        return Yw * WOOD.Cp + (1.0 - Yw) * CHAR.Cp
+        return Yw * self.wood.Cp + (1.0 - Yw) * self.char.Cp
 
     def Xw(self, Yw=None):
         """volume fraction of the virgin solid"""
         Yw = self.Yw if Yw is None else Yw
-        return (Yw / WOOD.rho) / (Yw / WOOD.rho + (1.0 - Yw) / CHAR.rho)
+        return (Yw / self.wood.rho) / (Yw / self.wood.rho + (1.0 - Yw) / self.char.rho)
 
     def kappa_vol(self, Yw=None):
         X = self.Xw(Yw)
-        return X * WOOD.kappa + (1.0 - X) * CHAR.kappa
+        return X * self.wood.kappa + (1.0 - X) * self.char.kappa
 
     def kappa(self):
         """solidThermo.kappa() = Cp()*alpha_ (see the class docstring)"""
@@ -109,16 +112,16 @@ class Panel:
     def _evolve(self, dt, flux, Tback):
         """reactingOneDim(21)::evolveRegion.  flux(kappa_patch) -> heat flux INTO the exposed face [W/m2], called where the
         reference evaluates the coupled patch of T: inside solveEnergy, after solveSpeciesMass, with the old temperatures."""
-        R = REACTION
+        R, wood, char = self.reaction, self.wood, self.char
         rdt = 1.0 / dt
         rho0, Yw0f, h0, T0 = self.rho.copy(), self.Yw.copy(), self.h.copy(), self.T.copy()
         alpha = self.alpha
         # ---- solidChemistry->calculate()
         kf = np.where(T0 < R["Tcrit"], 0.0, R["A"] * np.exp(-R["Ta"] / T0))
         omega = kf * np.power(rho0 * Yw0f / self.c0, R["n"]) * self.c0
-        sr = CHAR.rho / WOOD.rho
+        sr = char.rho / wood.rho
         RRw, RRc, RRg = -omega, sr * omega, (1.0 - sr) * omega
-        Qdot = -(WOOD.Hf * RRw + CHAR.Hf * RRc)
+        Qdot = -(wood.Hf * RRw + char.Hf * RRc)
         # ---- solveContinuity: fvm::ddt(rho) == -RRg
         self.rho = (rdt * rho0 * self.V - self.V * RRg) / (rdt * self.V)
         # ---- solveSpeciesMass: fvm::ddt(rho, Yw) == RRs(wood); char = 1 - Yt
@@ -136,8 +139,8 @@ class Panel:
         diag[:, :-1] += c_a; diag[:, 1:] += c_a
         src = rdt * rho0 * h0 * self.V + self.V * Qdot
         if self.model == "reactingOneDim21":
-            src = src + self.V * (RRw * T0 * WOOD.Cp)            # + RRs(0)*T*Cp0
-            src = src + self.V * (RRc * T0 * CHAR.Cp)            # + RRs(1)*T*Cp1
+            src = src + self.V * (RRw * T0 * wood.Cp)            # + RRs(0)*T*Cp0
+            src = src + self.V * (RRc * T0 * char.Cp)            # + RRs(1)*T*Cp1
         # + fvc::laplacian(alpha, h) - fvc::laplacian(kappa, T) on the LHS: source -= (lapA - lapK)
         fa = c_a * (h0[:, 1:] - h0[:, :-1]); fk = c_k * (T0[:, 1:] - T0[:, :-1])
         lapA = np.zeros((self.nCol, nL)); lapK = np.zeros((self.nCol, nL))
@@ -201,7 +204,7 @@ class Panel:
         """what the gas region's wall patch reads from the panel after its evolve(): refT (fluid branch of the coupled condition:
         the solid's cell temperature, valueFraction 1), U_b (flowRateInletVelocityPyrolysisCoupled, :127-248) and the wall emissivity
         of greyDiffusiveRadiation with `emissivityMode solidRadiation` (radiationCoupledBase.C:150-182)"""
-        hocPyr = (hocSolid * WOOD.rho - HOC_CHAR * CHAR.rho) / (WOOD.rho - CHAR.rho)
+        hocPyr = (hocSolid * self.wood.rho - HOC_CHAR * self.char.rho) / (self.wood.rho - self.char.rho)
         phi = self.massGas * hocPyr / qFuel
         U = (-phi / magSf) / rho_b
         emis = self.surface_radiation()[1] if self.radiation is not None else None
@@ -241,7 +244,7 @@ def couple(panel, Twall, Tgas_cell, kappaDelta_gas, qin, emissivity, absorptivit
     total = conv - absorptivity * qin + emissivity * SIGMA_SB * ((Twall * Twall) * (Twall * Twall))
     refGrad = -total / kap
     Tw = Ts + refGrad / (2.0 / panel.dx)
-    hocPyr = (hocSolid * WOOD.rho - HOC_CHAR * CHAR.rho) / (WOOD.rho - CHAR.rho)
+    hocPyr = (hocSolid * panel.wood.rho - HOC_CHAR * panel.char.rho) / (panel.wood.rho - panel.char.rho)
     phi = panel.massGas * hocPyr / qFuel
     U = (-phi / magSf) / rho_b
     return -total, Tw, Ts.copy(), nf * U[:, None]

@@ -46,6 +46,8 @@ def case_selections(case):
 
 class IncidentPanel(PY.Panel):
     def __init__(self, nCol, nLay=8, QrIncident=None, qr0=None, Tcrit=None, **kw):
+        if Tcrit is not None:
+            kw["reaction"] = dict(kw.get("reaction") or PY.REACTION, Tcrit=Tcrit)
         super().__init__(nCol, nLay, **kw)
         self.QrIncident = None if QrIncident is None else np.broadcast_to(np.asarray(QrIncident, float), (nCol,)).copy()
         self.qr0 = None if qr0 is None else np.broadcast_to(np.asarray(qr0, float), (nCol,)).copy()
@@ -65,16 +67,10 @@ class IncidentPanel(PY.Panel):
         return qr, q0
 
     def _evolve(self, dt, flux, Tback):
-        saved = PY.REACTION
-        if self.Tcrit is not None:
-            PY.REACTION = dict(saved, Tcrit=self.Tcrit)
-        try:
-            if self.qr0 is None:
-                return super()._evolve(dt, flux, Tback)
-            qr, q0 = self.qr_field()                               # before solveSpeciesMass
-            res = super()._evolve(dt, flux, Tback)
-        finally:
-            PY.REACTION = saved
+        if self.qr0 is None:
+            return super()._evolve(dt, flux, Tback)
+        qr, q0 = self.qr_field()                               # before solveSpeciesMass
+        res = super()._evolve(dt, flux, Tback)
         qf = np.empty((self.nCol, self.nLay + 1))
         qf[:, 0] = q0
         qf[:, 1:-1] = 0.5 * (qr[:, :-1] + qr[:, 1:])
