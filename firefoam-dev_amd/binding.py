@@ -115,6 +115,7 @@ def lib():
         "ffm_precond_setup": ([vp, C.c_int, dp], C.c_int),
         "ffm_precond_apply": ([vp, C.c_int, C.c_int, dp, dp], C.c_int),
         "ffm_precond_setup_multi": ([vp, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)], C.c_int),
+        "ffm_ldu_tile_reach": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
         "ffm_gs_smooth": ([vp, C.c_int, C.c_int, dp, dp], C.c_int),
         "ffm_solve_d": ([vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, dp, dp,
                          C.POINTER(Perf)], C.c_int),
@@ -279,6 +280,7 @@ def lib():
         "ffm_plume_nfaces": ([vp], C.c_int),
         "ffm_plume_get_field": ([vp, C.c_char_p, hp], C.c_int),
         "ffm_plume_nsolves": ([vp], C.c_int),
+        "ffm_plume_joint_steps": ([vp], C.c_int),
         "ffm_plume_get_solve": ([vp, C.c_int, C.c_char_p, C.POINTER(Perf)], C.c_int),
         "ffm_plume_get_raw": ([vp, C.c_char_p, hp, C.c_long], C.c_long),
         "ffm_plume_ldu": ([vp], vp),
@@ -739,6 +741,12 @@ class lduMatrix:
         self.ctx.sync()
         return out
 
+    def tile_reach(self):
+        """(reach, limit, limit5) of the tile plan (ffm_ldu_tile_reach): five lock-step systems need reach <= limit5"""
+        r, a, b = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().ffm_ldu_tile_reach(self.h, C.byref(r), C.byref(a), C.byref(b)), "ffm_ldu_tile_reach")
+        return r.value, a.value, b.value
+
     def precondition(self, preconditioner, rA, transpose=False):
         self.ctx._ready()
         w = self.ctx.empty(self.nCells)
@@ -919,6 +927,10 @@ class Plume:
             _check(lib().ffm_plume_get_solve(self.h, i, nm, C.byref(pf)), "ffm_plume_get_solve")
             res.append((nm.value.decode(), pf.as_dict()))
         return res
+
+    def joint_steps(self):
+        """steps so far that assembled and solved h with the species (ffm_plume_joint_steps)"""
+        return lib().ffm_plume_joint_steps(self.h)
 
     def ldu_handle(self):
         return lib().ffm_plume_ldu(self.h)

@@ -15,7 +15,8 @@
 // tests/test_fused_gpu.py checks each of them bitwise against the chain of per-operator entry points.
 #include "ffm_mesh.hpp"
 
-constexpr int FUSE_MAX = 4;
+constexpr int FUSE_MAX = 5;          // fields of one pass: the four species and h under the common weights (k_scalar_eqns<W,5,true,true>)
+constexpr int FUSE_MAX_OWN = 4;      // ... where every field brings its own gradients / limiter
 #define CHECK_M(m) if (!(m)) { ffm_set_error("null mesh"); return FFM_ERR_ARG; }
 
 struct GradMulti {
@@ -549,7 +550,7 @@ extern "C" int ffm_fvc_grad_multi(ffm_mesh *m, int nf, const double *const *vf, 
                                   double *const *gy, double *const *gz)
 {
     CHECK_M(m);
-    if (nf < 1 || nf > FUSE_MAX || !vf || !vb || !gx || !gy || !gz) return FFM_ERR_ARG;
+    if (nf < 1 || nf > FUSE_MAX_OWN || !vf || !vb || !gx || !gy || !gz) return FFM_ERR_ARG;
     GradMulti a;
     for (int i = 0; i < FUSE_MAX; i++) { const int k = i < nf ? i : 0; a.vf[i] = vf[k]; a.vb[i] = vb[k]; a.gx[i] = gx[k]; a.gy[i] = gy[k]; a.gz[i] = gz[k]; }
     for (int i = 0; i < nf; i++) if (!vf[i] || (m->B && !vb[i]) || !gx[i] || !gy[i] || !gz[i]) return FFM_ERR_ARG;
@@ -571,7 +572,7 @@ extern "C" int ffm_fvm_scalar_transport_multi(ffm_mesh *m, int nf, int scheme, d
                                               double *const *lower, double *const *source)
 {
     CHECK_M(m);
-    if (nf < 1 || nf > FUSE_MAX || (scheme != 2 && scheme != 3) || !rho || !rho0 || !phi_f || !gamma_f || (m->B && (!phi_b || !gamma_b)))
+    if (nf < 1 || nf > FUSE_MAX_OWN || (scheme != 2 && scheme != 3) || !rho || !rho0 || !phi_f || !gamma_f || (m->B && (!phi_b || !gamma_b)))
         return FFM_ERR_ARG;
     if (!vf || !gx || !gy || !gz || !vf0 || !f || !ref || !refGrad || !diag || !upper || !lower || !source) return FFM_ERR_ARG;
     ScalarEqns a;
@@ -652,7 +653,13 @@ extern "C" int ffm_fvm_scalar_transport_multi_ws(ffm_mesh *m, int nf, const doub
     for (int i = 0; i < nf; i++) { if (upper[i] && lower[i]) { if (a.nOffDiag != i) return FFM_ERR_ARG; a.nOffDiag = i + 1; } else if ((upper[i] == nullptr) != (lower[i] == nullptr)) return FFM_ERR_ARG; }
 #define SEW(NF) do { if (suFactor) FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_scalar_eqns<W, NF, true, true>), mview(m), a)); \
                      else FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_scalar_eqns<W, NF, true, false>), mview(m), a)); } while (0)
-    switch (nf) { case 1: SEW(1); break; case 2: SEW(2); break; case 3: SEW(3); break; default: SEW(4); break; }
+    switch (nf) {
+    case 1: SEW(1); break; case 2: SEW(2); break; case 3: SEW(3); break; case 4: SEW(4); break;
+    default:        // five fields: the species and h of the plume step, scaled sources only
+        if (!suFactor) return FFM_ERR_UNSUPPORTED;
+        FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_scalar_eqns<W, 5, true, true>), mview(m), a));
+        break;
+    }
 #undef SEW
     FFM_HIP(hipGetLastError());
     return FFM_OK;

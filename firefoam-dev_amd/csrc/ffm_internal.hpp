@@ -264,8 +264,9 @@ int ffm_tile_amul_pcg(ffm_ldu *A, const double *w, const double *pin, double *po
 int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot);
 int ffm_tile_precond(ffm_ldu *A, int precond, bool transpose, const double *r, double *w);
 // several systems with the matrix's off-diagonal coefficients in one sweep (ffm_tile.hip: k_tile_m)
-#define FFM_TILE_MAXSYS 4
+#define FFM_TILE_MAXSYS 5
 bool ffm_tile_multi_usable(const ffm_ldu *A);
+bool ffm_tile_multi_fits(const ffm_ldu *A, int n);      // n systems fit the LDS rings of one sweep (five: the short ring)
 int ffm_tile_precond_multi(ffm_ldu *A, int precond, int n, const double *const *rD, const double *const *r, double *const *w);
 int ffm_tile_calc_rD_multi(ffm_ldu *A, int n, const double *const *diag, double *const *D);
 int ffm_k_spmv_multi(ffm_ldu *A, int n, const double *const *diag, const double *const *x, double *const *y, double *const *sumA);

@@ -183,7 +183,7 @@ extern "C" int ffm_ldu_set_global_cells(ffm_ldu *A, long g) { if (!A || g < A->n
 
 int ffm_ldu_work(ffm_ldu *A, int idx, double **out)
 {
-    if (idx < 0 || idx > 63) return FFM_ERR_ARG;          // 32 ..: the lanes of ffm_solve_multi_d
+    if (idx < 0 || idx > 31 + 9 * (FFM_TILE_MAXSYS - 1)) return FFM_ERR_ARG;          // 32 ..: the lanes of ffm_solve_multi_d
     if ((int)A->work.size() <= idx) A->work.resize(idx + 1, nullptr);
     if (!A->work[idx]) FFM_HIP(hipMalloc((void **)&A->work[idx], sizeof(double) * (size_t)std::max(A->nCells, 1)));
     *out = A->work[idx];
@@ -481,13 +481,13 @@ static void rows_multi_launch(ffm_ldu *A, const double *const *diag, const doubl
     FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_rows_m<MODE, NF, W>), dim3(rows_grid(A)), dim3(256), 0, A->ctx->stream, ffm_view(A),
                                                (const double *)A->upper, (const double *)A->lower, m));
 }
-// n = 2 .. 4 systems; sumA != NULL: also sumA[i] = the row sums of system i (lduMatrix::sumA).  Matrices without coupled patches.
+// n = 2 .. FFM_TILE_MAXSYS systems; sumA != NULL: also sumA[i] = the row sums of system i (lduMatrix::sumA).  Matrices without coupled patches.
 int ffm_k_spmv_multi(ffm_ldu *A, int n, const double *const *diag, const double *const *x, double *const *y, double *const *sumA)
 {
-    if (n < 2 || n > 4 || !A->ifaces.empty()) return FFM_ERR_ARG;
+    if (n < 2 || n > FFM_TILE_MAXSYS || !A->ifaces.empty()) return FFM_ERR_ARG;
     if (!A->ghNbrRank.empty()) for (int i = 0; i < n; i++) FFM_TRY(ffm_ghost_exchange(A, const_cast<double *>(x[i])));
-    if (sumA) { if (n == 2) rows_multi_launch<3, 2>(A, diag, x, y, sumA); else if (n == 3) rows_multi_launch<3, 3>(A, diag, x, y, sumA); else rows_multi_launch<3, 4>(A, diag, x, y, sumA); }
-    else { if (n == 2) rows_multi_launch<0, 2>(A, diag, x, y, sumA); else if (n == 3) rows_multi_launch<0, 3>(A, diag, x, y, sumA); else rows_multi_launch<0, 4>(A, diag, x, y, sumA); }
+    if (sumA) { if (n == 2) rows_multi_launch<3, 2>(A, diag, x, y, sumA); else if (n == 3) rows_multi_launch<3, 3>(A, diag, x, y, sumA); else if (n == 4) rows_multi_launch<3, 4>(A, diag, x, y, sumA); else rows_multi_launch<3, 5>(A, diag, x, y, sumA); }
+    else { if (n == 2) rows_multi_launch<0, 2>(A, diag, x, y, sumA); else if (n == 3) rows_multi_launch<0, 3>(A, diag, x, y, sumA); else if (n == 4) rows_multi_launch<0, 4>(A, diag, x, y, sumA); else rows_multi_launch<0, 5>(A, diag, x, y, sumA); }
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }

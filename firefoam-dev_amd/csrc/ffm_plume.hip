@@ -244,6 +244,7 @@ extern "C" int ffm_plume_create_block(ffm_ctx *ctx, int gx, int gy, int gz, cons
     P->wFuel = P->wN[8]; P->Qdot = P->wN[9]; P->Yt = P->wN[10]; P->alphaEff_f = P->wF[0]; P->alphaEff_b = P->wB[4];      // (the slot table: ffm_plume.hpp)
     const bool fused = P->fused = getenv("FFM_PLUME_UNFUSED") == nullptr;
     P->mvSelection = getenv("FFM_PLUME_INDEPENDENT_LIMITERS") == nullptr;
+    { const char *e = getenv("FFM_PLUME_SEPARATE_H"); P->separateH = e && atoi(e) != 0; }
     if (P->mvSelection) { P->wMv = dalloc(P, nNat); if (fused) for (int j = 0; j < 2; j++) for (int d = 0; d < 3; d++) P->mvG[j][d] = NN(); }
     for (int j = 0; j < 4; j++) {
         for (int d = 0; d < 3; d++) P->gM[j][d] = fused ? NN() : nullptr;
@@ -403,6 +404,8 @@ extern "C" long ffm_plume_get_raw(ffm_plume *P, const char *name, double *out, l
     return FFM_ERR_ARG;
 }
 
+// steps so far that assembled and solved h with the species (tests)
+extern "C" int ffm_plume_joint_steps(const ffm_plume *P) { return P ? P->jointSteps : FFM_ERR_ARG; }
 extern "C" int ffm_plume_nsolves(const ffm_plume *P) { return P ? (int)P->log.size() : FFM_ERR_ARG; }
 extern "C" int ffm_plume_get_solve(const ffm_plume *P, int i, char *name16, ffm_perf *perf)
 {

@@ -52,7 +52,7 @@ struct ffm_plume {
     // lives from one stage into a later one has a member of its own (next line).  `->`: must survive calls into other stages / the library.
     // (ops): the per-operator form only (FFM_PLUME_UNFUSED); (ops, blocks): that form and the fused one on a decomposed box -- the fused
     // single-block step forms the value where it is used and leaves the slot alone.
-    //   wN[0]    hydrostatic_init, rho_eqn_ops: div | e_eqn: ddtK -> | p_corrector: rAU -> (read for the last time before pc_flux_U's rho_eqn)
+    //   wN[0]    hydrostatic_init, rho_eqn_ops: div | e_eqn (or species_eqns with h): ddtK -> | p_corrector: rAU -> (read for the last time before pc_flux_U's rho_eqn)
     //   wN[1-3]  u_source_ops, scalar_transport, mv_weights_ops, e_K_terms: a gradient | p_corrector: rhorAU, HbyA[0-1] ->
     //   wN[4]    u_source_ops: divc | e_eqn: divK -> (scalar_transport reads it before it writes its source sum here) | p_corrector: HbyA[2] ->
     //   wN[5-7]  u_eqn (ops), pc_flux_U (ops, blocks): reconstruct(...) -> | e_eqn: [5] -dpdt -> | pc_phig_flux_ops: rho*HbyA
@@ -82,6 +82,8 @@ struct ffm_plume {
     bool mvSelection = true;
     double *wMv = nullptr, *mvG[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     bool fused = true;                     // FFM_PLUME_UNFUSED: one kernel per operator (tests compare the two paths)
+    bool separateH = false;                // FFM_PLUME_SEPARATE_H: h assembled and solved after the species, never as their fifth system
+    int jointSteps = 0;                    // steps in which h was the fifth system of the species' pass and solve (ffm_plume_joint_steps)
     // UEqn kept for pEqn (A, H)
     double *Udiag, *Uupper, *Ulower, *Usrc[3], *Uic[3], *Ubc[3];
     std::vector<SolveLog> log;

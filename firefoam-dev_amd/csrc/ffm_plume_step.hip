@@ -272,9 +272,16 @@ static int species_eqns_ops(ffm_plume *P)
     return FFM_OK;
 }
 
-// The four transported species share phi, rho and dEff: boundary values, gradients and matrices of all four in one pass each, then
-// the solves in the reference's order (nothing a later equation reads changes in an earlier solve)
-static int species_eqns(ffm_plume *P, bool *offDiagBound)
+// (defined with e_eqn below)
+struct KTerms { double *ddtK, *divK, *ndpdt; };
+static int e_K_terms(ffm_plume *P, const KTerms &kt);
+static int e_radiation_source(ffm_plume *P, const double **shSu, const double **shSp);
+
+// withH (the common limiter, PBiCGStab + DILU, one block, no radiation->correct() in this step): h is the fifth field of the assembly
+// pass and the fifth lane of the lock-step solve.  Nothing the enthalpy matrix reads is written by the species solves -- Qdot is
+// standin_combustion's, the K terms come from U, wMv is formed before, T, hs and G are old values -- so its explicit terms are formed
+// first; the solve log keeps the reference's order, every lane the numbers of a solve of its own.
+static int species_eqns(ffm_plume *P, bool *offDiagBound, bool withH)
 {
     *offDiagBound = false;
     if (!P->fused) return species_eqns_ops(P);
@@ -285,7 +292,29 @@ static int species_eqns(ffm_plume *P, bool *offDiagBound)
     for (int i = 0, j = 0; i < NSP; i++) if (i != INERT) {
         sp[j] = i; vf0[j] = P->Y0[i]; fq[j] = P->fS; rq[j] = P->refY[i]; gq[j] = P->zeroB; suq[j] = wFuel; nuq[j] = NU[i]; j++;
     }
-    if (P->mvSelection) {
+    if (withH) {
+        const KTerms kt = {P->wN[0], P->wN[4], P->wN[5]};
+        FFM_TRY(e_K_terms(P, kt));
+        const double *shSu, *shSp;
+        FFM_TRY(e_radiation_source(P, &shSu, &shSp));
+        constexpr int nq = ns + 1;
+        const double *vf0q[nq], *fq5[nq], *rq5[nq], *gq5[nq], *suq5[nq], *su2q[nq], *spq[nq], *expl[3 * nq]; double fac[nq];
+        double *dd[nq], *ss[nq], *uu[nq] = {P->spU[0], nullptr, nullptr, nullptr, nullptr}, *ll[nq] = {P->spL[0], nullptr, nullptr, nullptr, nullptr};
+        const char *nmq[nq]; double *pq[nq];
+        for (int j = 0; j < ns; j++) {
+            vf0q[j] = vf0[j]; fq5[j] = fq[j]; rq5[j] = rq[j]; gq5[j] = gq[j]; suq5[j] = suq[j]; fac[j] = nuq[j]; su2q[j] = spq[j] = nullptr;
+            for (int e = 0; e < 3; e++) expl[3 * j + e] = nullptr;
+            dd[j] = P->spD[j]; ss[j] = P->spS[j]; nmq[j] = SPN[sp[j]]; pq[j] = P->Y[sp[j]];
+        }
+        vf0q[ns] = P->hs0; fq5[ns] = P->fH; rq5[ns] = P->refH; gq5[ns] = P->zeroB; suq5[ns] = P->Qdot; fac[ns] = 1.0; su2q[ns] = shSu; spq[ns] = shSp;
+        expl[3 * ns] = kt.ddtK; expl[3 * ns + 1] = kt.divK; expl[3 * ns + 2] = kt.ndpdt;
+        dd[ns] = P->dWork; ss[ns] = P->sWork; nmq[ns] = "h"; pq[ns] = P->hs;
+        FFM_TRY(ffm_fvm_scalar_transport_multi_ws(m, nq, P->wMv, rdt, P->rho, P->rho0, P->phi, P->phib, af, afb, vf0q, fq5, rq5, gq5, suq5, fac, su2q,
+                                                  spq, expl, dd, uu, ll, ss));
+        FFM_TRY(solve_named_multi(P, nq, nmq, 1e-8, dd, P->spU[0], P->spL[0], pq, ss));
+        for (int j = 0; j < nq; j++) FFM_TRY(HX(P, pq[j]));
+        P->jointSteps++;
+    } else if (P->mvSelection) {
         // with the common weights and one diffusivity the four species have the SAME off-diagonal coefficients (only diag and source
         // differ, through the patch conditions and the sources): written once, gathered into the sweeps' layout once; the assembly
         // pass forms nu_i*wFuel itself
@@ -328,7 +357,6 @@ static int species_eqns(ffm_plume *P, bool *offDiagBound)
 }
 
 // ---- EEqn: the explicit LHS terms fvc::ddt(rho,K) + fvc::div(phi,K) - dpdt (solver/YEEqn.H:89-101)
-struct KTerms { double *ddtK, *divK, *ndpdt; };
 static int e_K_terms_ops(ffm_plume *P, const double *Kb, const double *kgx, const double *kgy, const double *kgz, const KTerms &kt)
 {
     ffm_mesh *m = P->mesh; const double rdt = P->rdt;
@@ -359,28 +387,36 @@ static int e_K_terms(ffm_plume *P, const KTerms &kt)
                     : e_K_terms_ops(P, Kb, kgx, kgy, kgz, kt);
 }
 
+// + radiation->Sh(thermo, he) = Ru - fvm::Sp(4 Rp T^3/Cpv, he) - Rp T^3 (T - 4 he/Cpv), Rp = 4 a sigma, Ru = a G - E
+// (radiationModel.C:229-244, fvDOM.C Rp / Ru), E of the current Qdot; both null where radiation is not coupled
+static int e_radiation_source(ffm_plume *P, const double **shSu, const double **shSp)
+{
+    *shSu = *shSp = nullptr;
+    if (!(P->radCoupled && P->radHaveG)) return FFM_OK;
+    double frac = 0.0;
+    FFM_TRY(plume_rad_fraction(P, &frac));
+    const double Rp = 4.0 * P->radA * SIGMA_SB, KA = P->radA;
+    double *su2 = P->radShSu, *sp2 = P->radShSp; const double *G = P->G, *T = P->T, *hh = P->hs, *Qd = P->Qdot;
+    forN(P, P->N, [=] __device__(long c) {
+        const double t = T[c], T3 = t * t * t;
+        const double Ru = KA * G[c] - frac * Qd[c];
+        sp2[c] = 4.0 * Rp * T3 / CP;
+        su2[c] = Ru - Rp * T3 * (t - 4.0 * hh[c] / CP);
+    });
+    *shSu = su2; *shSp = sp2;
+    return FFM_OK;
+}
+
+// The four transported species share phi, rho and dEff: boundary values, gradients and matrices of all four in one pass each, then
+// the solves in the reference's order (nothing a later equation reads changes in an earlier solve)
 static int e_eqn(ffm_plume *P, bool shareH)
 {
-    ffm_mesh *m = P->mesh; const int N = P->N; const double rdt = P->rdt;
+    ffm_mesh *m = P->mesh; const double rdt = P->rdt;
     const KTerms kt = {P->wN[0], P->wN[4], P->wN[5]};
     FFM_TRY(e_K_terms(P, kt));
     const double *expl[3] = {kt.ddtK, kt.divK, kt.ndpdt};
-    // + radiation->Sh(thermo, he) = Ru - fvm::Sp(4 Rp T^3/Cpv, he) - Rp T^3 (T - 4 he/Cpv), Rp = 4 a sigma, Ru = a G - E
-    // (radiationModel.C:229-244, fvDOM.C Rp / Ru), E of the current Qdot
-    const double *shSu = nullptr, *shSp = nullptr;
-    if (P->radCoupled && P->radHaveG) {
-        double frac = 0.0;
-        FFM_TRY(plume_rad_fraction(P, &frac));
-        const double Rp = 4.0 * P->radA * SIGMA_SB, KA = P->radA;
-        double *su2 = P->radShSu, *sp2 = P->radShSp; const double *G = P->G, *T = P->T, *hh = P->hs, *Qd = P->Qdot;
-        forN(P, N, [=] __device__(long c) {
-            const double t = T[c], T3 = t * t * t;
-            const double Ru = KA * G[c] - frac * Qd[c];
-            sp2[c] = 4.0 * Rp * T3 / CP;
-            su2[c] = Ru - Rp * T3 * (t - 4.0 * hh[c] / CP);
-        });
-        shSu = su2; shSp = sp2;
-    }
+    const double *shSu, *shSp;
+    FFM_TRY(e_radiation_source(P, &shSu, &shSp));
     if (!P->fused) return scalar_transport(P, "h", 2, P->hs, P->hs0, P->fH, P->refH, P->alphaEff_f, P->alphaEff_b, P->Qdot, expl, 1e-8, shSu, shSp, P->wMv);
     const double *af = P->alphaEff_f, *afb = P->alphaEff_b;
     const double *vf[1] = {P->hs}, *vb[1] = {P->spB[0]}, *vf0[1] = {P->hs0}, *fq[1] = {P->fH}, *rq[1] = {P->refH}, *gq[1] = {P->zeroB}, *suq[1] = {P->Qdot};
@@ -604,9 +640,11 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     standin_combustion(P);
     FFM_TRY(mv_weights(P));
     bool spOffDiagBound;
-    FFM_TRY(species_eqns(P, &spOffDiagBound));
-    if (P->radFreq > 0 && P->stepNo % P->radFreq == 0) { FFM_TRY(radiation_correct(P)); spOffDiagBound = false; }     // radiation->correct(), solver/YEEqn.H:80: its ray solves bind other coefficients
-    FFM_TRY(e_eqn(P, spOffDiagBound));
+    const bool radNow = P->radFreq > 0 && P->stepNo % P->radFreq == 0;
+    const bool jointYh = P->fused && P->mvSelection && !P->stecklerSolvers && P->oneBlock && !radNow && !P->separateH;
+    FFM_TRY(species_eqns(P, &spOffDiagBound, jointYh));
+    if (radNow) { FFM_TRY(radiation_correct(P)); spOffDiagBound = false; }     // radiation->correct(), solver/YEEqn.H:80: its ray solves bind other coefficients
+    if (!jointYh) FFM_TRY(e_eqn(P, spOffDiagBound));
     standin_thermo(P);
     FFM_TRY(p_corrector(P, false));
     FFM_TRY(p_corrector(P, true));

@@ -1346,8 +1346,9 @@ extern "C" int ffm_solve_multi_d(ffm_ldu *A, int nSys, int solver, int precond, 
     for (int i = 0; i < nSys; i++) if (!diag_d[i] || !psi_d[i] || !source_d[i]) { ffm_set_error("ffm_solve_multi_d: null array"); return FFM_ERR_ARG; }
     FFM_HIP(hipSetDevice(A->ctx->device));
     Controls k{tol, relTol, minIter, maxIter, 1};
+    // (five systems need the short LDS ring: a plan whose ring neighbours lie too far apart for it solves them one after the other)
     const bool batched = nSys >= 2 && nSys <= FFM_TILE_MAXSYS && solver == FFM_PBICGSTAB && (precond == FFM_DILU || precond == FFM_DIC) &&
-                         A->identity && A->sweepMode == 2 && ffm_tile_multi_usable(A) && A->ifaces.empty();
+                         A->identity && A->sweepMode == 2 && ffm_tile_multi_fits(A, nSys) && A->ifaces.empty();
     if (!batched) {          // one after the other (any solver, any matrix)
         for (int i = 0; i < nSys; i++) {
             FFM_TRY(ffm_ldu_bind_coeffs_native_d(A, diag_d[i], upper_d, lower_d, i > 0));
@@ -1411,6 +1412,7 @@ extern "C" int ffm_precond_setup_multi(ffm_ldu *A, int precond, int nSys, const 
     if (!A || !diag_d || !rD_out_d || nSys < 2 || nSys > FFM_TILE_MAXSYS) { ffm_set_error("ffm_precond_setup_multi: bad argument"); return FFM_ERR_ARG; }
     if (precond != FFM_DIC && precond != FFM_DILU) { ffm_set_error("ffm_precond_setup_multi: DIC or DILU"); return FFM_ERR_UNSUPPORTED; }
     if (!(A->identity && A->sweepMode == 2 && ffm_tile_multi_usable(A))) { ffm_set_error("ffm_precond_setup_multi needs a tiled matrix in the library's cell order"); return FFM_ERR_UNSUPPORTED; }
+    if (!ffm_tile_multi_fits(A, nSys)) { ffm_set_error("ffm_precond_setup_multi: %d systems do not fit the LDS rings of this matrix's tile plan", nSys); return FFM_ERR_UNSUPPORTED; }
     if (precond == FFM_DIC && !A->symmetric) { ffm_set_error("DIC needs a symmetric matrix"); return FFM_ERR_UNSUPPORTED; }
     for (int i = 0; i < nSys; i++) if (!diag_d[i] || !rD_out_d[i]) { ffm_set_error("ffm_precond_setup_multi: null array"); return FFM_ERR_ARG; }
     FFM_HIP(hipSetDevice(A->ctx->device));

@@ -53,6 +53,7 @@ struct TileDir {            // one sweep direction (device arrays)
     int *src = nullptr;         // [3*nOwn] native coefficient index of each neighbour slot (-1: none)
     double *coefU = nullptr, *coefL = nullptr;        // [3*nOwn] gathered upper / lower coefficients (lazily allocated)
     unsigned long epochU = ~0ul, epochL = ~0ul;
+    int reach = 0;              // largest cell distance of a neighbour served by the ring (host; <= T_RINGD)
     double *mail = nullptr;     // [nPub + 1] (inside ffm_tile_plan::mailAll)
 };
 
@@ -130,8 +131,9 @@ static int build_dir(ffm_ldu *A, bool fwd, const std::vector<int> &lvl, const st
     std::vector<int> nbr((size_t)W * nOwn, -1), src((size_t)W * nOwn, -1);
     std::vector<unsigned char> exposed(nOwn, 0);
     auto isExt = [&](int c, int nb) { return grpOfCell[nb] != grpOfCell[c] || std::abs(c - nb) > T_RINGD; };
-    std::atomic<int> tooMany(0);
+    std::atomic<int> tooMany(0), reach(0);
     ffm_parallel_for(nOwn, [&](long c0_, long c1_) {
+        int far = 0;
         for (long c = c0_; c < c1_; c++) {
             const int sl = (int)(c >> 6), lane = (int)(c & 63), wdt = (off[sl + 1] - off[sl]) / 64;
             int k = 0;
@@ -144,10 +146,14 @@ static int build_dir(ffm_ldu *A, bool fwd, const std::vector<int> &lvl, const st
                 nbr[(size_t)W * c + k] = nb;
                 src[(size_t)W * c + k] = fwd ? (A->h_upOff[(e >> 4) >> 6] + (e & 15) * 64 + ((e >> 4) & 63)) : q;
                 if (isExt((int)c, nb)) exposed[nb] = 1;          // (several threads may store the same 1)
+                else far = std::max(far, std::abs((int)c - nb));
                 k++;
             }
         }
+        int seen = reach.load();
+        while (far > seen && !reach.compare_exchange_weak(seen, far)) {}
     });
+    D.reach = reach;
     if (tooMany) { ok = false; return FFM_OK; }
     // entries: runs of one level, at most T_ENT cells and T_XMAX external references; forward ascending, backward descending
     std::vector<unsigned short> code((size_t)4 * nOwn, (unsigned short)T_NONE);
@@ -725,14 +731,20 @@ constexpr int TM_PF = 4;            // read-ahead of the multi-system sweeps (NF
 static_assert(T_PM < TM_PF, "read-ahead distances");
 template <int NF> struct TileMulti { const double *dg[NF]; const double *r[NF]; double *w[NF]; double *mail[NF]; };
 
-template <int MODE, int NF>
+// R: the ring length.  The plan's codes are LDS slots of a T_RING ring; a shorter ring (five rings of T_RING doubles do not fit the
+// LDS) takes an in-ring code modulo R and an external code rebased from T_RING to R, and serves plans whose ring neighbours lie
+// within R - 2*T_ENT cells (TileDir::reach, ffm_tile_multi_fits).
+constexpr int TM_RING5 = 2048;
+template <int MODE, int NF, int R = T_RING>
 __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const double *__restrict__ ca, const double *__restrict__ cb, TileMulti<NF> m)
 {
+    static_assert(R <= T_RING && (R & (R - 1)) == 0 && R > 2 * T_ENT, "ring length");
+    constexpr int LDS = R + 2 * T_XMAX + 1;
     static_assert(MODE == TM_FWD || MODE == TM_BWD || MODE == TM_RD, "DILU / DIC application and calcReciprocalD");
     constexpr bool ASC = MODE != TM_BWD;
     constexpr bool TWO = MODE == TM_RD;
     constexpr int W = T_W, PF = TM_PF;
-    __shared__ double ring[NF][T_LDS];
+    __shared__ double ring[NF][LDS];
     __shared__ int4 shRec[4];
     __shared__ int shG;
     __shared__ int shAbort;
@@ -762,7 +774,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
             _Pragma("unroll") for (int i_ = 0; i_ < NF; i_++) {                                           \
                 double v_ = qxv[k][i_];                                                                   \
                 if (__builtin_expect(t_pending(v_), 0)) v_ = t_wait_value(&m.mail[i_][qxi[k]], t.ticket, &shAbort); \
-                ring[i_][T_RING + (((e) & 1) * T_XMAX) + lane] = v_;                                      \
+                ring[i_][R + (((e) & 1) * T_XMAX) + lane] = v_;                                           \
             }                                                                                             \
         }                                                                                                 \
     }
@@ -826,7 +838,9 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
                 const unsigned cd[4] = {pq[k].x & 0xFFFFu, pq[k].x >> 16, pq[k].y & 0xFFFFu, pq[k].y >> 16};
                 unsigned sl[W];
 #pragma unroll
-                for (int s = 0; s < W; s++) sl[s] = min(cd[s], (unsigned)(T_LDS - 1));
+                for (int s = 0; s < W; s++)
+                    sl[s] = (R == T_RING) ? min(cd[s], (unsigned)(LDS - 1))
+                                          : (cd[s] < (unsigned)T_RING ? (cd[s] & (unsigned)(R - 1)) : min(cd[s] - (unsigned)(T_RING - R), (unsigned)(LDS - 1)));
                 double val[NF];
 #pragma unroll
                 for (int i = 0; i < NF; i++) {
@@ -851,7 +865,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
 #pragma unroll
                     for (int i = 0; i < NF; i++) {
                         *(double *)((char *)m.w[i] + c * 8u) = (MODE == TM_RD) ? 1.0 / val[i] : val[i];
-                        ring[i][(c - gs) & (unsigned)(T_RING - 1)] = val[i];
+                        ring[i][(c - gs) & (unsigned)(R - 1)] = val[i];
                         if (cd[3] != T_NONE) t_st(&m.mail[i][ppb[k] + cd[3]], val[i]);
                     }
                 }
@@ -865,28 +879,42 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
 
 
 bool ffm_tile_multi_usable(const ffm_ldu *A) { return ffm_tile_usable(A); }
+// n systems in one sweep: up to four on the plan's own ring, five on the short one where the plan's ring neighbours are near enough
+bool ffm_tile_multi_fits(const ffm_ldu *A, int n)
+{
+    if (n < 2 || n > FFM_TILE_MAXSYS || !ffm_tile_multi_usable(A)) return false;
+    return n <= 4 || std::max(A->tile->f.reach, A->tile->b.reach) <= TM_RING5 - 2 * T_ENT;
+}
+extern "C" int ffm_ldu_tile_reach(const ffm_ldu *A, int *reach, int *limit, int *limit5)
+{
+    if (!A || !reach || !limit || !limit5) return FFM_ERR_ARG;
+    if (!ffm_tile_usable(A)) { ffm_set_error("ffm_ldu_tile_reach: the matrix has no tile plan"); return FFM_ERR_UNSUPPORTED; }
+    *reach = std::max(A->tile->f.reach, A->tile->b.reach); *limit = T_RINGD; *limit5 = TM_RING5 - 2 * T_ENT;
+    return FFM_OK;
+}
 static int tile_multi_mail(ffm_ldu *A)
 {
     ffm_tile_plan *T = A->tile;
     if (!T->mailMulti) FFM_HIP(hipMalloc((void **)&T->mailMulti, sizeof(double) * (size_t)FFM_TILE_MAXSYS * (size_t)T->nMail));
     return FFM_OK;
 }
-template <int MODE, int NF>
+template <int MODE, int NF, int R = T_RING>
 static void tile_multi_launch(ffm_ldu *A, const TileDir &d, const double *ca, const double *cb, const double *const *dg, const double *const *r, double *const *w)
 {
     ffm_tile_plan *T = A->tile;
     TileMulti<NF> m;
     for (int i = 0; i < NF; i++) { m.dg[i] = dg[i]; m.r[i] = r ? r[i] : nullptr; m.w[i] = w[i]; m.mail[i] = T->mailMulti + (size_t)i * T->nMail + (d.mail - T->mailAll); }
-    hipLaunchKernelGGL((k_tile_m<MODE, NF>), dim3(T->G), dim3(T_THREADS + 64), 0, A->ctx->stream, tview(A, d), ca, cb, m);
+    hipLaunchKernelGGL((k_tile_m<MODE, NF, R>), dim3(T->G), dim3(T_THREADS + 64), 0, A->ctx->stream, tview(A, d), ca, cb, m);
 }
 #define TILE_MULTI(MODE, n, ...) switch (n) { case 2: tile_multi_launch<MODE, 2>(__VA_ARGS__); break; case 3: tile_multi_launch<MODE, 3>(__VA_ARGS__); break; \
-                                             default: tile_multi_launch<MODE, 4>(__VA_ARGS__); break; }
+                                             case 4: tile_multi_launch<MODE, 4>(__VA_ARGS__); break; \
+                                             default: tile_multi_launch<MODE, 5, TM_RING5>(__VA_ARGS__); break; }
 // DILU / DIC application (not transposed) of n = 2 .. FFM_TILE_MAXSYS systems with the matrix's off-diagonal coefficients and their
 // own reciprocal diagonals: w[i] = precondition(r[i]).
 int ffm_tile_precond_multi(ffm_ldu *A, int precond, int n, const double *const *rD, const double *const *r, double *const *w)
 {
     ffm_tile_plan *T = A->tile;
-    if (n < 2 || n > FFM_TILE_MAXSYS || !ffm_tile_multi_usable(A)) return FFM_ERR_ARG;
+    if (!ffm_tile_multi_fits(A, n)) return FFM_ERR_ARG;
     const double *cf, *cb;
     FFM_TRY(tile_coef(A, T->f, precond == FFM_DIC, &cf));
     FFM_TRY(tile_coef(A, T->b, true, &cb));
@@ -901,7 +929,7 @@ int ffm_tile_precond_multi(ffm_ldu *A, int precond, int n, const double *const *
 int ffm_tile_calc_rD_multi(ffm_ldu *A, int n, const double *const *diag, double *const *D)
 {
     ffm_tile_plan *T = A->tile;
-    if (n < 2 || n > FFM_TILE_MAXSYS || !ffm_tile_multi_usable(A)) return FFM_ERR_ARG;
+    if (!ffm_tile_multi_fits(A, n)) return FFM_ERR_ARG;
     const double *cu, *cl;
     FFM_TRY(tile_coef(A, T->f, true, &cu));
     if (A->lower == A->upper) cl = cu; else FFM_TRY(tile_coef(A, T->f, false, &cl));

@@ -224,9 +224,13 @@ int ffm_residual(ffm_ldu *ldu, const double *x_d, const double *b_d, double *r_d
 int ffm_precond_setup(ffm_ldu *ldu, int precond, double *rD_out_d /*nullable*/);
 int ffm_precond_apply(ffm_ldu *ldu, int precond, int transpose,
                       const double *r_d, double *w_d);
-/* calcReciprocalD (DIC / DILU) of nSys = 2..4 systems that share the bound off-diagonal coefficients and differ in the diagonal,
+/* calcReciprocalD (DIC / DILU) of nSys = 2..5 systems that share the bound off-diagonal coefficients and differ in the diagonal,
  * in the ONE sweep ffm_solve_multi_d uses for them (tiled matrix in the library's cell order; anything else is refused).           */
 int ffm_precond_setup_multi(ffm_ldu *ldu, int precond, int nSys, const double *const *diag_d, double *const *rD_out_d);
+/* The tile plan's largest cell distance between a cell and a neighbour served from the sweeps' LDS ring, the limit of the plan's own
+ * ring (up to four lock-step systems) and the limit of the short ring that five systems need: with reach > limit5,
+ * ffm_solve_multi_d solves five systems one after the other and ffm_precond_setup_multi refuses five.  Tiled matrices only.   */
+int ffm_ldu_tile_reach(const ffm_ldu *ldu, int *reach, int *limit, int *limit5);
 int ffm_gs_smooth(ffm_ldu *ldu, int symmetric_sweep, int nSweeps, double *psi_d,
                   const double *b_d);
 
@@ -244,8 +248,9 @@ int ffm_solve(ffm_ldu *ldu, int solver, int precond, double tolerance,
  * under a multivariateSelection scheme with one diffusivity (solver/YEEqn.H:43-60).  Every system gets the solve a call of
  * ffm_ldu_bind_coeffs_native_d(diag_d[i], upper_d, lower_d) + ffm_solve_d would give it -- the same operations in the same order,
  * its own iteration count and residuals in out[i] -- but for PBiCGStab with DILU / DIC on a tiled matrix in the library's cell order
- * the systems (at most 4 at a time) advance in lock step and the preconditioner sweeps and calcReciprocalD of those still iterating
- * are one sweep each (coefficients and addressing read once).  Any other selection: one solve after the other.
+ * the systems (at most 5 at a time; 5 only where ffm_ldu_tile_reach reports reach <= limit5) advance in lock step and the preconditioner
+ * sweeps and calcReciprocalD of those still iterating are one sweep each (coefficients and addressing read once).  Any other selection:
+ * one solve after the other.
  * diag_d[i] [cells], upper_d / lower_d [native faces; lower_d NULL or == upper_d: symmetric], psi_d[i] in/out, source_d[i].
  * The matrix is left bound to the caller's arrays as by ffm_ldu_bind_coeffs_native_d.                                         */
 int ffm_solve_multi_d(ffm_ldu *ldu, int nSys, int solver, int precond, double tolerance, double relTol, int minIter, int maxIter,
@@ -478,7 +483,8 @@ int ffm_fvm_scalar_transport_multi(ffm_mesh *m, int nf, int scheme, double k, do
 /* the same pass with the face weights given (a multivariateSelection scheme's common weights: ffm_fv_multivariate_weights) instead of
  * one limiter per field -- what mvConvection->fvmDiv(phi, Yi) of solver/YEEqn.H:44 assembles.  With common weights and one gamma every
  * field has the SAME off-diagonal coefficients: upper[i] = lower[i] = NULL for the fields i >= n0 (n0 = 0 .. nf) leaves them unwritten,
- * the caller solves those systems with the arrays of an earlier field (ffm_ldu_bind_coeffs_native_d with offDiagUnchanged). */
+ * the caller solves those systems with the arrays of an earlier field (ffm_ldu_bind_coeffs_native_d with offDiagUnchanged).
+ * nf <= 4; ffm_fvm_scalar_transport_multi_ws with suFactor given also takes nf = 5 (the four species and h). */
 int ffm_fvm_scalar_transport_multi_w(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
                                      const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
                                      const double *const *vf0, const double *const *f, const double *const *ref,
@@ -675,6 +681,8 @@ int ffm_plume_ncells(const ffm_plume *p);
 int ffm_plume_nfaces(const ffm_plume *p);
 int ffm_plume_get_field(ffm_plume *p, const char *name, double *out);
 int ffm_plume_nsolves(const ffm_plume *p);
+/* steps so far in which h was assembled and solved as the fifth system of the species (FFM_PLUME_SEPARATE_H=1: never)            */
+int ffm_plume_joint_steps(const ffm_plume *p);
 int ffm_plume_get_solve(const ffm_plume *p, int i, char *name16, ffm_perf *perf);
 /* the case's raw state for a driver that runs the same case through another path (bench.py: the reference's equation files over the Foam
  * layer): cell fields [N] in the library's cell order, face fields [F] in the renumbered LDU face order, boundary arrays [B] in (patch, face)
