@@ -241,7 +241,6 @@ void ffm_comm_finalize_i(ffm_ctx *ctx);
 int ffm_precond_setup_i(ffm_ldu *A, int precond);
 int ffm_precond_apply_i(ffm_ldu *A, int precond, bool transpose, const double *r, double *w);
 int ffm_tile_build(ffm_ldu *A, const std::vector<int> &lev, const std::vector<int> &bl, const std::vector<int> &grpCell);
-int ffm_tile_calc_rD(ffm_ldu *A);
 int ffm_sweep_check_abort(ffm_ldu *A);                   // abort word of the tiled and the dataflow sweeps (ffm_solve.hip)
 int ffm_tile_gs_ghost_terms(ffm_ldu *A, const double *psi, double *bP);
 int ffm_ghost_exchange(ffm_ldu *A, double *x);
@@ -262,13 +261,11 @@ bool ffm_tile_amul_asym_usable(const ffm_ldu *A);
 int ffm_tile_amul_asym(ffm_ldu *A, const double *x, double *y);
 int ffm_tile_amul_pcg(ffm_ldu *A, const double *w, const double *pin, double *pout, double *psi, double *y, int dotSlot);
 int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot);
-int ffm_tile_precond(ffm_ldu *A, int precond, bool transpose, const double *r, double *w);
-// several systems with the matrix's off-diagonal coefficients in one sweep (ffm_tile.hip: k_tile_m)
+// n = 1 .. FFM_TILE_MAXSYS systems with the matrix's off-diagonal coefficients in one sweep (ffm_tile.hip: k_tile); n = 1: the matrix's own
 #define FFM_TILE_MAXSYS 5
-bool ffm_tile_multi_usable(const ffm_ldu *A);
 bool ffm_tile_multi_fits(const ffm_ldu *A, int n);      // n systems fit the LDS rings of one sweep (five: the short ring)
-int ffm_tile_precond_multi(ffm_ldu *A, int precond, int n, const double *const *rD, const double *const *r, double *const *w);
-int ffm_tile_calc_rD_multi(ffm_ldu *A, int n, const double *const *diag, double *const *D);
+int ffm_tile_precond(ffm_ldu *A, int precond, bool transpose, int n, const double *const *rD, const double *const *r, double *const *w);
+int ffm_tile_calc_rD(ffm_ldu *A, int n, const double *const *diag, double *const *D);
 int ffm_k_spmv_multi(ffm_ldu *A, int n, const double *const *diag, const double *const *x, double *const *y, double *const *sumA);
 // ffm_solve_d on internal (native-order) vectors, no caller-order staging (ffm_solve.hip; GAMG's coarsest level)
 extern "C" int ffm_solve_internal_i(ffm_ldu *A, int solver, int precond, double tol, double relTol, int minIter, int maxIter, int nSweeps,

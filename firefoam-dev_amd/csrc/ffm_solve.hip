@@ -23,6 +23,9 @@
 // Scalars (alpha, beta, residual norms) stay on the device; the host reads the
 // residual back once per iteration (twice for PBiCGStab) to take the
 // convergence decision, as SolverPerformance::checkConvergence does.
+//
+// PBiCGStab is written once, over lanes (pbicgstab_lanes): a lane is one system's solver state, a plain solve is the
+// single lane that is the matrix's own state, and ffm_solve_multi_d runs up to FFM_TILE_MAXSYS lanes in lock step.
 #include "ffm_internal.hpp"
 #include "ffm_device.hpp"
 #include <algorithm>
@@ -478,7 +481,8 @@ int ffm_sweep_check_abort(ffm_ldu *A)
 static int calc_rD(ffm_ldu *A)
 {
     if (A->sweepMode == 2) {
-        return ffm_tile_calc_rD(A);          // (stores 1/D)
+        const double *dg = A->diag;
+        return ffm_tile_calc_rD(A, 1, &dg, &A->rD);          // (stores 1/D)
     }
     FlowArgs a; FFM_TRY(flow_args(A, SM_RD, a));
     FLOW_LAUNCH(SM_RD, a);
@@ -512,7 +516,7 @@ int ffm_precond_apply_i(ffm_ldu *A, int precond, bool transpose, const double *r
     const long N = A->nOwned;
     if (precond == FFM_NONE) { hipLaunchKernelGGL(k_copy, dim3(sgrid(N)), dim3(256), 0, s, N, w, r); FFM_HIP(hipGetLastError()); return FFM_OK; }
     if (precond == FFM_DIAGONALP) { hipLaunchKernelGGL(k_mul, dim3(sgrid(N)), dim3(256), 0, s, N, w, A->rD, r); FFM_HIP(hipGetLastError()); return FFM_OK; }
-    if (A->sweepMode == 2) return ffm_tile_precond(A, precond, transpose, r, w);
+    if (A->sweepMode == 2) { const double *rD = A->rD; return ffm_tile_precond(A, precond, transpose, 1, &rD, &r, &w); }
     // DIC: fwd upper / bwd upper.  DILU: fwd lower / bwd upper.  DILU^T: fwd upper / bwd lower.
     FlowArgs a; FFM_TRY(flow_args(A, SM_PRECOND, a));
     a.cf = (precond == FFM_DIC) ? A->upper : (transpose ? A->upper : A->lower);
@@ -664,54 +668,151 @@ static int pcg(ffm_ldu *A, int precond, const Controls &k, double *psi, const do
     return FFM_OK;
 }
 
-// PBiCGStab::solve
-static int pbicgstab(ffm_ldu *A, int precond, const Controls &k, double *psi, const double *source, ffm_perf *perf)
+// PBiCGStab::solve, of one system or of several in lock step.  fvMatrix::solveSegregated of a vector equation and the species loop
+// under a multivariateSelection scheme solve systems that differ in the diagonal and the right-hand side only.  Every such system is
+// a lane with its own solver state (scalars, work vectors, reciprocal diagonal); each lane goes through the operations of a solve
+// of its own in the same order -- its numbers and its iteration count are those of a solve of its own -- but the preconditioner
+// sweeps, the Amuls and calcReciprocalD of the lanes still iterating are ONE launch each (ffm_tile.hip: k_tile<.., NF>, ffm_ldu.hip:
+// k_rows_m), and the host reads all residuals back with one synchronisation per half iteration.  A lane that is left alone takes
+// the one-system calls; a single lane that is the matrix's own state (own_lane) is the plain solve: any matrix, any preconditioner.
+namespace {
+struct Lane {
+    const double *diag, *source; double *psi; ffm_perf *perf;
+    double *scal_d, *scal_h;
+    int work;                   // its work vectors are ffm_ldu_work(work + 1 .. work + 8)
+    double *rD, *pA, *yA, *rA, *AyA, *sA, *zA, *tA, *rA0;
+    bool active;
+};
+struct LaneGuard {          // the context's scalar block and the matrix's diagonal / reciprocal diagonal are switched per lane
+    ffm_ldu *A; bool several; double *scal_d, *scal_h, *diag, *rD;
+    LaneGuard(ffm_ldu *a, bool sev) : A(a), several(sev), scal_d(a->ctx->scal_d), scal_h(a->ctx->scal_h), diag(a->diag), rD(a->rD) {}
+    void use(const Lane &l) { A->ctx->scal_d = l.scal_d; A->ctx->scal_h = l.scal_h; A->diag = const_cast<double *>(l.diag); A->rD = l.rD; }
+    ~LaneGuard()            // several lanes leave some lane's reciprocal diagonal behind: the matrix's own is stale
+    { A->ctx->scal_d = scal_d; A->ctx->scal_h = scal_h; A->diag = diag; A->rD = rD; if (several) { A->rDKind = -1; A->rDEpoch = ~0ul; } }
+};
+}
+// the matrix's own state as a lane: LaneGuard::use changes nothing for it
+static Lane own_lane(ffm_ldu *A, double *psi, const double *source, ffm_perf *perf)
+{
+    Lane l{};
+    l.diag = A->diag; l.source = source; l.psi = psi; l.perf = perf; l.scal_d = A->ctx->scal_d; l.scal_h = A->ctx->scal_h; l.work = 0; l.rD = A->rD;
+    return l;
+}
+static int read_lane_scalars(ffm_ctx *c, Lane *L, int n)
+{
+    bool any = false;
+    for (int i = 0; i < n; i++) if (L[i].active) {
+        FFM_HIP(hipMemcpyAsync(L[i].scal_h, L[i].scal_d, sizeof(double) * NSCAL, hipMemcpyDeviceToHost, c->stream));
+        any = true;
+    }
+    if (any) FFM_HIP(hipStreamSynchronize(c->stream));
+    return FFM_OK;
+}
+static int precond_lanes(ffm_ldu *A, int precond, Lane *L, int n, double *Lane::*in, double *Lane::*out, LaneGuard &G)
+{
+    const double *rD[FFM_TILE_MAXSYS], *r[FFM_TILE_MAXSYS]; double *w[FFM_TILE_MAXSYS]; int m = 0, only = -1;
+    for (int i = 0; i < n; i++) if (L[i].active) { rD[m] = L[i].rD; r[m] = L[i].*in; w[m] = L[i].*out; m++; only = i; }
+    if (m >= 2) return ffm_tile_precond(A, precond, false, m, rD, r, w);
+    if (m == 1) { G.use(L[only]); return ffm_precond_apply_i(A, precond, false, L[only].*in, L[only].*out); }
+    return FFM_OK;
+}
+// out = A in for the lanes still iterating: one pass over the coefficients for all of them (ffm_ldu.hip: k_rows_m)
+static int amul_lanes(ffm_ldu *A, Lane *L, int n, double *Lane::*in, double *Lane::*out, LaneGuard &G)
+{
+    const double *dg[FFM_TILE_MAXSYS], *x[FFM_TILE_MAXSYS]; double *y[FFM_TILE_MAXSYS]; int m = 0, only = -1;
+    for (int i = 0; i < n; i++) if (L[i].active) { dg[m] = L[i].diag; x[m] = L[i].*in; y[m] = L[i].*out; m++; only = i; }
+    if (m >= 2) return ffm_k_spmv_multi(A, m, dg, x, y, nullptr);
+    if (m == 1) { G.use(L[only]); return ffm_k_spmv(A, L[only].*in, L[only].*out, false); }
+    return FFM_OK;
+}
+static int pbicgstab_lanes(ffm_ldu *A, int precond, const Controls &k, int n, Lane *L)
 {
     ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned; const int g = sgrid(N);
-    double *yA, *rA, *pA, *AyA, *sA, *zA, *tA, *rA0;
-    FFM_TRY(ffm_ldu_work(A, 1, &pA)); FFM_TRY(ffm_ldu_work(A, 2, &yA)); FFM_TRY(ffm_ldu_work(A, 3, &rA)); FFM_TRY(ffm_ldu_work(A, 8, &rA0));
-    FFM_TRY(scalar_op(c, OP_RESET));
-    FFM_TRY(ffm_k_spmv_sumA(A, psi, yA, pA));
-    FFM_TRY(norm_and_initial(A, psi, source, yA, pA, rA, perf, rA0, pA));
-    if (k.minIter > 0 || !check_convergence(perf, k)) {
-        FFM_TRY(ffm_ldu_work(A, 4, &AyA)); FFM_TRY(ffm_ldu_work(A, 5, &sA)); FFM_TRY(ffm_ldu_work(A, 6, &zA));
-        FFM_TRY(ffm_ldu_work(A, 7, &tA));
-        FFM_TRY(ffm_precond_setup_i(A, precond));
-        do {
-            if (perf->nIterations == 0) FFM_TRY(scalar_op(c, OP_BS_RHO, 0.0, 0, S_TMP2));        // rA0.rA and pA = rA came with the prologue
-            else {
-                FFM_TRY(ffm_k_dot(c, rA0, rA, N, S_TMP0));
-                FFM_TRY(finish_dot(c, OP_BS_RHO, 1, 0.0, perf->nIterations));
-                hipLaunchKernelGGL(k_bs_p, dim3(g), dim3(256), 0, s, N, pA, rA, AyA, c->scal_d);
-            }
-            FFM_TRY(ffm_precond_apply_i(A, precond, false, pA, yA));
-            FFM_TRY(ffm_k_spmv(A, yA, AyA, false));
-            FFM_TRY(ffm_k_dot(c, rA0, AyA, N, S_TMP0));
+    LaneGuard G(A, n > 1);
+    for (int i = 0; i < n; i++) {
+        Lane &l = L[i]; G.use(l);
+        FFM_TRY(ffm_ldu_work(A, l.work + 1, &l.pA)); FFM_TRY(ffm_ldu_work(A, l.work + 2, &l.yA)); FFM_TRY(ffm_ldu_work(A, l.work + 3, &l.rA));
+        FFM_TRY(ffm_ldu_work(A, l.work + 8, &l.rA0));
+        FFM_TRY(scalar_op(c, OP_RESET));
+    }
+    if (n == 1) FFM_TRY(ffm_k_spmv_sumA(A, L[0].psi, L[0].yA, L[0].pA));
+    else {      // yA = A psi and sumA of every system in one pass
+        const double *dg[FFM_TILE_MAXSYS], *x[FFM_TILE_MAXSYS]; double *y[FFM_TILE_MAXSYS], *sm[FFM_TILE_MAXSYS];
+        for (int i = 0; i < n; i++) { dg[i] = L[i].diag; x[i] = L[i].psi; y[i] = L[i].yA; sm[i] = L[i].pA; }
+        FFM_TRY(ffm_k_spmv_multi(A, n, dg, x, y, sm));
+    }
+    for (int i = 0; i < n; i++) {
+        Lane &l = L[i]; G.use(l);
+        FFM_TRY(norm_and_initial(A, l.psi, l.source, l.yA, l.pA, l.rA, l.perf, l.rA0, l.pA));          // (reads this lane's scalars back)
+        l.active = k.minIter > 0 || !check_convergence(l.perf, k);
+        if (!l.active) continue;
+        FFM_TRY(ffm_ldu_work(A, l.work + 4, &l.AyA)); FFM_TRY(ffm_ldu_work(A, l.work + 5, &l.sA)); FFM_TRY(ffm_ldu_work(A, l.work + 6, &l.zA));
+        FFM_TRY(ffm_ldu_work(A, l.work + 7, &l.tA));
+    }
+    {   // calcReciprocalD of the systems that iterate.  Several lanes: every lane's rD is then current and the single-lane calls below
+        // must not redo it, whatever the matrix's cache says of its own; the one lane of the matrix's own state keeps the cache check
+        const double *dg[FFM_TILE_MAXSYS]; double *D[FFM_TILE_MAXSYS]; int m = 0, only = -1;
+        for (int i = 0; i < n; i++) if (L[i].active) { dg[m] = L[i].diag; D[m] = L[i].rD; m++; only = i; }
+        if (m >= 2) FFM_TRY(ffm_tile_calc_rD(A, m, dg, D));          // (stores 1/D)
+        else if (m == 1) { G.use(L[only]); if (n > 1) A->rDKind = -1; FFM_TRY(ffm_precond_setup_i(A, precond)); }
+        if (n > 1) { A->rDKind = precond; A->rDEpoch = A->coeffEpoch; }
+    }
+    for (;;) {
+        bool any = false;
+        for (int i = 0; i < n; i++) if (L[i].active) {
+            Lane &l = L[i]; G.use(l); any = true;
+            if (l.perf->nIterations == 0) { FFM_TRY(scalar_op(c, OP_BS_RHO, 0.0, 0, S_TMP2)); continue; }       // rA0.rA and pA = rA came with the prologue
+            FFM_TRY(ffm_k_dot(c, l.rA0, l.rA, N, S_TMP0));
+            FFM_TRY(finish_dot(c, OP_BS_RHO, 1, 0.0, l.perf->nIterations));
+            hipLaunchKernelGGL(k_bs_p, dim3(g), dim3(256), 0, s, N, l.pA, l.rA, l.AyA, c->scal_d);
+        }
+        if (!any) break;
+        FFM_TRY(precond_lanes(A, precond, L, n, &Lane::pA, &Lane::yA, G));
+        FFM_TRY(amul_lanes(A, L, n, &Lane::yA, &Lane::AyA, G));
+        for (int i = 0; i < n; i++) if (L[i].active) {
+            Lane &l = L[i]; G.use(l);
+            FFM_TRY(ffm_k_dot(c, l.rA0, l.AyA, N, S_TMP0));
             FFM_TRY(finish_dot(c, OP_BS_ALPHA));
-            hipLaunchKernelGGL(k_bs_s, dim3(g), dim3(256), 0, s, N, sA, rA, AyA, c->scal_d, c->partials_d);
+            hipLaunchKernelGGL(k_bs_s, dim3(g), dim3(256), 0, s, N, l.sA, l.rA, l.AyA, c->scal_d, c->partials_d);
             FFM_TRY(partial_sum_to(c, g, S_TMP0));
             FFM_TRY(finish_dot(c, OP_RES));
-            FFM_TRY(ffm_read_scalars(c));
-            if (c->scal_h[S_SING] != 0.0) { perf->singular = 1; break; }
-            perf->finalResidual = c->scal_h[S_RES];
-            if (check_convergence(perf, k)) {
-                hipLaunchKernelGGL(k_axpy_alpha, dim3(g), dim3(256), 0, s, N, psi, yA, c->scal_d);
-                perf->nIterations++;
-                return FFM_OK;
+        }
+        FFM_TRY(read_lane_scalars(c, L, n));
+        for (int i = 0; i < n; i++) if (L[i].active) {
+            Lane &l = L[i]; G.use(l);
+            if (l.scal_h[S_SING] != 0.0) { l.perf->singular = 1; l.active = false; continue; }
+            l.perf->finalResidual = l.scal_h[S_RES];
+            if (check_convergence(l.perf, k)) {
+                hipLaunchKernelGGL(k_axpy_alpha, dim3(g), dim3(256), 0, s, N, l.psi, l.yA, c->scal_d);
+                l.perf->nIterations++;
+                l.active = false;
             }
-            FFM_TRY(ffm_precond_apply_i(A, precond, false, sA, zA));
-            FFM_TRY(ffm_k_spmv(A, zA, tA, false));
-            hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, s, N, tA, sA, c->partials_d);
+        }
+        FFM_TRY(precond_lanes(A, precond, L, n, &Lane::sA, &Lane::zA, G));
+        FFM_TRY(amul_lanes(A, L, n, &Lane::zA, &Lane::tA, G));
+        for (int i = 0; i < n; i++) if (L[i].active) {
+            Lane &l = L[i]; G.use(l);
+            hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, s, N, l.tA, l.sA, c->partials_d);
             FFM_TRY(partial_sum_to(c, g, S_TMP0, 2));
             FFM_TRY(finish_dot(c, OP_BS_OMEGA, 2));
-            hipLaunchKernelGGL(k_bs_xr, dim3(g), dim3(256), 0, s, N, psi, rA, yA, zA, sA, tA, c->scal_d, c->partials_d);
+            hipLaunchKernelGGL(k_bs_xr, dim3(g), dim3(256), 0, s, N, l.psi, l.rA, l.yA, l.zA, l.sA, l.tA, c->scal_d, c->partials_d);
             FFM_TRY(partial_sum_to(c, g, S_TMP0));
             FFM_TRY(finish_dot(c, OP_RES));
-            FFM_TRY(ffm_read_scalars(c));
-            perf->finalResidual = c->scal_h[S_RES];
-        } while ((++perf->nIterations < k.maxIter && !check_convergence(perf, k)) || perf->nIterations < k.minIter);
+        }
+        FFM_TRY(read_lane_scalars(c, L, n));
+        for (int i = 0; i < n; i++) if (L[i].active) {
+            Lane &l = L[i];
+            l.perf->finalResidual = l.scal_h[S_RES];
+            l.active = (++l.perf->nIterations < k.maxIter && !check_convergence(l.perf, k)) || l.perf->nIterations < k.minIter;
+        }
     }
+    FFM_HIP(hipGetLastError());
     return FFM_OK;
+}
+static int pbicgstab(ffm_ldu *A, int precond, const Controls &k, double *psi, const double *source, ffm_perf *perf)
+{
+    Lane l = own_lane(A, psi, source, perf);
+    return pbicgstab_lanes(A, precond, k, 1, &l);
 }
 
 // PBiCG::solve
@@ -1219,125 +1320,8 @@ extern "C" int ffm_solve_ordered_staged_d(ffm_ldu *A, const ffm_flow_order *o, d
 { return solve_ordered(A, o, true, psi_d, source_d, out); }
 
 // ------------------------------------------------------------------ several systems with common off-diagonals ---
-// fvMatrix::solveSegregated of a vector equation and the species loop under a multivariateSelection scheme solve systems that differ in
-// the diagonal and the right-hand side only.  PBiCGStab + DILU (or DIC) of nSys <= FFM_TILE_MAXSYS such systems run in lock step: every
-// system keeps its own solver state (scalars, work vectors, reciprocal diagonal) and goes through exactly the operations of pbicgstab()
-// above in the same order -- its numbers and its iteration count are those of a solve of its own -- but the preconditioner sweeps and
-// calcReciprocalD of the systems still iterating are ONE tiled sweep each (ffm_tile.hip: k_tile_m), and the host reads all residuals
-// back with one synchronisation per half iteration.
-namespace {
-struct Lane {
-    const double *diag, *source; double *psi; ffm_perf *perf;
-    double *scal_d, *scal_h;
-    double *rD, *pA, *yA, *rA, *AyA, *sA, *zA, *tA, *rA0;
-    bool active;
-};
-struct LaneGuard {          // the context's scalar block and the matrix's diagonal / reciprocal diagonal are switched per lane
-    ffm_ldu *A; double *scal_d, *scal_h, *diag, *rD; int rDKind; unsigned long rDEpoch;
-    explicit LaneGuard(ffm_ldu *a) : A(a), scal_d(a->ctx->scal_d), scal_h(a->ctx->scal_h), diag(a->diag), rD(a->rD), rDKind(a->rDKind), rDEpoch(a->rDEpoch) {}
-    void use(const Lane &l) { A->ctx->scal_d = l.scal_d; A->ctx->scal_h = l.scal_h; A->diag = const_cast<double *>(l.diag); A->rD = l.rD; }
-    ~LaneGuard() { A->ctx->scal_d = scal_d; A->ctx->scal_h = scal_h; A->diag = diag; A->rD = rD; A->rDKind = -1; A->rDEpoch = ~0ul; }
-};
-}
-static int read_lane_scalars(ffm_ctx *c, Lane *L, int n)
-{
-    for (int i = 0; i < n; i++) if (L[i].active)
-        FFM_HIP(hipMemcpyAsync(L[i].scal_h, L[i].scal_d, sizeof(double) * NSCAL, hipMemcpyDeviceToHost, c->stream));
-    FFM_HIP(hipStreamSynchronize(c->stream));
-    return FFM_OK;
-}
-static int precond_lanes(ffm_ldu *A, int precond, Lane *L, int n, double *Lane::*in, double *Lane::*out, LaneGuard &G)
-{
-    const double *rD[FFM_TILE_MAXSYS], *r[FFM_TILE_MAXSYS]; double *w[FFM_TILE_MAXSYS]; int m = 0, only = -1;
-    for (int i = 0; i < n; i++) if (L[i].active) { rD[m] = L[i].rD; r[m] = L[i].*in; w[m] = L[i].*out; m++; only = i; }
-    if (m >= 2) return ffm_tile_precond_multi(A, precond, m, rD, r, w);
-    if (m == 1) { G.use(L[only]); return ffm_precond_apply_i(A, precond, false, L[only].*in, L[only].*out); }
-    return FFM_OK;
-}
-// out = A in for the lanes still iterating: one pass over the coefficients for all of them (ffm_ldu.hip: k_rows_m)
-static int amul_lanes(ffm_ldu *A, Lane *L, int n, double *Lane::*in, double *Lane::*out, LaneGuard &G)
-{
-    const double *dg[FFM_TILE_MAXSYS], *x[FFM_TILE_MAXSYS]; double *y[FFM_TILE_MAXSYS]; int m = 0, only = -1;
-    for (int i = 0; i < n; i++) if (L[i].active) { dg[m] = L[i].diag; x[m] = L[i].*in; y[m] = L[i].*out; m++; only = i; }
-    if (m >= 2) return ffm_k_spmv_multi(A, m, dg, x, y, nullptr);
-    if (m == 1) { G.use(L[only]); return ffm_k_spmv(A, L[only].*in, L[only].*out, false); }
-    return FFM_OK;
-}
-static int pbicgstab_multi(ffm_ldu *A, int precond, const Controls &k, int n, Lane *L)
-{
-    ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned; const int g = sgrid(N);
-    LaneGuard G(A);
-    {   // wA = A psi and sumA of every system in one pass
-        const double *dg[FFM_TILE_MAXSYS], *x[FFM_TILE_MAXSYS]; double *y[FFM_TILE_MAXSYS], *sm[FFM_TILE_MAXSYS];
-        for (int i = 0; i < n; i++) { dg[i] = L[i].diag; x[i] = L[i].psi; y[i] = L[i].yA; sm[i] = L[i].pA; }
-        FFM_TRY(ffm_k_spmv_multi(A, n, dg, x, y, sm));
-    }
-    for (int i = 0; i < n; i++) {
-        Lane &l = L[i]; G.use(l);
-        FFM_TRY(scalar_op(c, OP_RESET));
-        FFM_TRY(norm_and_initial(A, l.psi, l.source, l.yA, l.pA, l.rA, l.perf, l.rA0, l.pA));          // (reads this lane's scalars back)
-        l.active = k.minIter > 0 || !check_convergence(l.perf, k);
-    }
-    {   // calcReciprocalD of the systems that iterate
-        const double *dg[FFM_TILE_MAXSYS]; double *D[FFM_TILE_MAXSYS]; int m = 0, only = -1;
-        for (int i = 0; i < n; i++) if (L[i].active) { dg[m] = L[i].diag; D[m] = L[i].rD; m++; only = i; }
-        if (m >= 2) FFM_TRY(ffm_tile_calc_rD_multi(A, m, dg, D));          // (stores 1/D)
-        else if (m == 1) { G.use(L[only]); A->rDKind = -1; FFM_TRY(ffm_precond_setup_i(A, precond)); }
-        A->rDKind = precond; A->rDEpoch = A->coeffEpoch;         // every lane's rD is current: the single-lane calls below must not redo it
-    }
-    for (;;) {
-        bool any = false;
-        for (int i = 0; i < n; i++) if (L[i].active) {
-            Lane &l = L[i]; G.use(l); any = true;
-            if (l.perf->nIterations == 0) { FFM_TRY(scalar_op(c, OP_BS_RHO, 0.0, 0, S_TMP2)); continue; }
-            FFM_TRY(ffm_k_dot(c, l.rA0, l.rA, N, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_BS_RHO, 1, 0.0, l.perf->nIterations));
-            hipLaunchKernelGGL(k_bs_p, dim3(g), dim3(256), 0, s, N, l.pA, l.rA, l.AyA, c->scal_d);
-        }
-        if (!any) break;
-        FFM_TRY(precond_lanes(A, precond, L, n, &Lane::pA, &Lane::yA, G));
-        FFM_TRY(amul_lanes(A, L, n, &Lane::yA, &Lane::AyA, G));
-        for (int i = 0; i < n; i++) if (L[i].active) {
-            Lane &l = L[i]; G.use(l);
-            FFM_TRY(ffm_k_dot(c, l.rA0, l.AyA, N, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_BS_ALPHA));
-            hipLaunchKernelGGL(k_bs_s, dim3(g), dim3(256), 0, s, N, l.sA, l.rA, l.AyA, c->scal_d, c->partials_d);
-            FFM_TRY(partial_sum_to(c, g, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_RES));
-        }
-        FFM_TRY(read_lane_scalars(c, L, n));
-        for (int i = 0; i < n; i++) if (L[i].active) {
-            Lane &l = L[i]; G.use(l);
-            if (l.scal_h[S_SING] != 0.0) { l.perf->singular = 1; l.active = false; continue; }
-            l.perf->finalResidual = l.scal_h[S_RES];
-            if (check_convergence(l.perf, k)) {
-                hipLaunchKernelGGL(k_axpy_alpha, dim3(g), dim3(256), 0, s, N, l.psi, l.yA, c->scal_d);
-                l.perf->nIterations++;
-                l.active = false;
-            }
-        }
-        FFM_TRY(precond_lanes(A, precond, L, n, &Lane::sA, &Lane::zA, G));
-        FFM_TRY(amul_lanes(A, L, n, &Lane::zA, &Lane::tA, G));
-        for (int i = 0; i < n; i++) if (L[i].active) {
-            Lane &l = L[i]; G.use(l);
-            hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, s, N, l.tA, l.sA, c->partials_d);
-            FFM_TRY(partial_sum_to(c, g, S_TMP0, 2));
-            FFM_TRY(finish_dot(c, OP_BS_OMEGA, 2));
-            hipLaunchKernelGGL(k_bs_xr, dim3(g), dim3(256), 0, s, N, l.psi, l.rA, l.yA, l.zA, l.sA, l.tA, c->scal_d, c->partials_d);
-            FFM_TRY(partial_sum_to(c, g, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_RES));
-        }
-        FFM_TRY(read_lane_scalars(c, L, n));
-        for (int i = 0; i < n; i++) if (L[i].active) {
-            Lane &l = L[i];
-            l.perf->finalResidual = l.scal_h[S_RES];
-            l.active = (++l.perf->nIterations < k.maxIter && !check_convergence(l.perf, k)) || l.perf->nIterations < k.minIter;
-        }
-    }
-    FFM_HIP(hipGetLastError());
-    return FFM_OK;
-}
-
+// PBiCGStab + DILU (or DIC) of nSys <= FFM_TILE_MAXSYS systems as the lanes of one pbicgstab_lanes (above); one system is the matrix's
+// own lane.  Everything else goes one system after the other through ffm_solve_d.
 extern "C" int ffm_solve_multi_d(ffm_ldu *A, int nSys, int solver, int precond, double tol, double relTol, int minIter, int maxIter,
                                  const double *const *diag_d, const double *upper_d, const double *lower_d, double *const *psi_d,
                                  const double *const *source_d, ffm_perf *out)
@@ -1346,10 +1330,11 @@ extern "C" int ffm_solve_multi_d(ffm_ldu *A, int nSys, int solver, int precond, 
     for (int i = 0; i < nSys; i++) if (!diag_d[i] || !psi_d[i] || !source_d[i]) { ffm_set_error("ffm_solve_multi_d: null array"); return FFM_ERR_ARG; }
     FFM_HIP(hipSetDevice(A->ctx->device));
     Controls k{tol, relTol, minIter, maxIter, 1};
-    // (five systems need the short LDS ring: a plan whose ring neighbours lie too far apart for it solves them one after the other)
-    const bool batched = nSys >= 2 && nSys <= FFM_TILE_MAXSYS && solver == FFM_PBICGSTAB && (precond == FFM_DILU || precond == FFM_DIC) &&
-                         A->identity && A->sweepMode == 2 && ffm_tile_multi_fits(A, nSys) && A->ifaces.empty();
-    if (!batched) {          // one after the other (any solver, any matrix)
+    // several lanes need the tiled sweeps of several systems (five systems the short LDS ring: a plan whose ring neighbours lie too far
+    // apart for it solves them one after the other); one lane needs the vectors in the library's cell order only
+    const bool lanes = nSys <= FFM_TILE_MAXSYS && solver == FFM_PBICGSTAB && (precond == FFM_DILU || precond == FFM_DIC) && A->identity &&
+                       (nSys == 1 || (A->sweepMode == 2 && ffm_tile_multi_fits(A, nSys) && A->ifaces.empty()));
+    if (!lanes) {          // one after the other (any solver, any matrix)
         for (int i = 0; i < nSys; i++) {
             FFM_TRY(ffm_ldu_bind_coeffs_native_d(A, diag_d[i], upper_d, lower_d, i > 0));
             FFM_TRY(ffm_solve_d(A, solver, precond, tol, relTol, minIter, maxIter, 1, psi_d[i], source_d[i], &out[i]));
@@ -1359,7 +1344,7 @@ extern "C" int ffm_solve_multi_d(ffm_ldu *A, int nSys, int solver, int precond, 
     FFM_TRY(ffm_ldu_bind_coeffs_native_d(A, diag_d[0], upper_d, lower_d, 0));
     if (precond == FFM_DIC && !A->symmetric) { ffm_set_error("DIC needs a symmetric matrix"); return FFM_ERR_UNSUPPORTED; }
     ffm_ctx *c = A->ctx;
-    if (!c->multiScal_d) {
+    if (nSys > 1 && !c->multiScal_d) {
         FFM_HIP(hipMalloc((void **)&c->multiScal_d, sizeof(double) * NSCAL * FFM_TILE_MAXSYS));
         FFM_HIP(hipHostMalloc((void **)&c->multiScal_h, sizeof(double) * NSCAL * FFM_TILE_MAXSYS, hipHostMallocDefault));
         FFM_HIP(hipMemsetAsync(c->multiScal_d, 0, sizeof(double) * NSCAL * FFM_TILE_MAXSYS, c->stream));
@@ -1368,13 +1353,11 @@ extern "C" int ffm_solve_multi_d(ffm_ldu *A, int nSys, int solver, int precond, 
     for (int i = 0; i < nSys; i++) {
         Lane &l = L[i];
         memset(&out[i], 0, sizeof(ffm_perf));
-        l.diag = diag_d[i]; l.source = source_d[i]; l.psi = psi_d[i]; l.perf = &out[i]; l.active = false;
-        l.scal_d = c->multiScal_d + (size_t)i * NSCAL; l.scal_h = c->multiScal_h + (size_t)i * NSCAL;
-        double **w[9] = {&l.rD, &l.pA, &l.yA, &l.rA, &l.AyA, &l.sA, &l.zA, &l.tA, &l.rA0};
-        if (i == 0) { l.rD = A->rD; for (int j = 1; j <= 8; j++) FFM_TRY(ffm_ldu_work(A, j, w[j])); }
-        else for (int j = 0; j < 9; j++) FFM_TRY(ffm_ldu_work(A, 32 + 9 * (i - 1) + j, w[j]));
+        l = own_lane(A, psi_d[i], source_d[i], &out[i]);            // lane 0 keeps the matrix's rD and the solvers' work vectors 1-8
+        if (nSys > 1) { l.diag = diag_d[i]; l.scal_d = c->multiScal_d + (size_t)i * NSCAL; l.scal_h = c->multiScal_h + (size_t)i * NSCAL; }
+        if (i > 0) { l.work = 32 + 9 * (i - 1); FFM_TRY(ffm_ldu_work(A, l.work, &l.rD)); }
     }
-    FFM_TRY(pbicgstab_multi(A, precond, k, nSys, L));
+    FFM_TRY(pbicgstab_lanes(A, precond, k, nSys, L));
     FFM_HIP(hipStreamSynchronize(c->stream));
     FFM_TRY(ffm_sweep_check_abort(A));
     return FFM_OK;
@@ -1411,12 +1394,12 @@ extern "C" int ffm_precond_setup_multi(ffm_ldu *A, int precond, int nSys, const 
 {
     if (!A || !diag_d || !rD_out_d || nSys < 2 || nSys > FFM_TILE_MAXSYS) { ffm_set_error("ffm_precond_setup_multi: bad argument"); return FFM_ERR_ARG; }
     if (precond != FFM_DIC && precond != FFM_DILU) { ffm_set_error("ffm_precond_setup_multi: DIC or DILU"); return FFM_ERR_UNSUPPORTED; }
-    if (!(A->identity && A->sweepMode == 2 && ffm_tile_multi_usable(A))) { ffm_set_error("ffm_precond_setup_multi needs a tiled matrix in the library's cell order"); return FFM_ERR_UNSUPPORTED; }
+    if (!(A->identity && A->sweepMode == 2 && ffm_tile_usable(A))) { ffm_set_error("ffm_precond_setup_multi needs a tiled matrix in the library's cell order"); return FFM_ERR_UNSUPPORTED; }
     if (!ffm_tile_multi_fits(A, nSys)) { ffm_set_error("ffm_precond_setup_multi: %d systems do not fit the LDS rings of this matrix's tile plan", nSys); return FFM_ERR_UNSUPPORTED; }
     if (precond == FFM_DIC && !A->symmetric) { ffm_set_error("DIC needs a symmetric matrix"); return FFM_ERR_UNSUPPORTED; }
     for (int i = 0; i < nSys; i++) if (!diag_d[i] || !rD_out_d[i]) { ffm_set_error("ffm_precond_setup_multi: null array"); return FFM_ERR_ARG; }
     FFM_HIP(hipSetDevice(A->ctx->device));
-    FFM_TRY(ffm_tile_calc_rD_multi(A, nSys, diag_d, rD_out_d));
+    FFM_TRY(ffm_tile_calc_rD(A, nSys, diag_d, rD_out_d));
     FFM_HIP(hipStreamSynchronize(A->ctx->stream));
     FFM_TRY(ffm_sweep_check_abort(A));
     return FFM_OK;

@@ -1,4 +1,5 @@
-// ffm_tile.hip -- tiled wavefront sweeps for DIC / DILU: calcReciprocalD, forward and backward substitution.
+// ffm_tile.hip -- tiled wavefront sweeps for DIC / DILU (calcReciprocalD, forward and backward substitution): one kernel template,
+// k_tile<MODE, NF, R, FUSE>, for one system or NF systems with common off-diagonal coefficients; Gauss-Seidel row sweeps: k_tile_gs.
 //
 // Same operators, bitwise, as the level-scheduled kernels of ffm_solve.hip (OpenFOAM-dev DICPreconditioner /
 // DILUPreconditioner::calcReciprocalD and ::precondition, reference selection cases/steckler/system/fvSolution:21-46).
@@ -32,7 +33,7 @@ constexpr int T_RING = 4096;        // doubles (power of two)
 constexpr int T_ENT = 256;          // max cells per entry = workgroup size
 constexpr int T_THREADS = 256;
 constexpr int T_W = FFM_TILE_W;     // neighbour slots per cell and direction (ffm_host.hpp: ffm_tile_feasible tests it on the host)
-constexpr int T_PF = 8;             // entries fetched ahead of the one being computed
+constexpr int T_PF = 8;             // entries fetched ahead of the one being computed, at most (tile_pf)
 constexpr int T_PM = 3;             // mailbox values are loaded this many entries ahead (2 <= T_PM < T_PF)
 constexpr int T_XMAX = 64;          // max external references per entry (one lane of the mail wave each; power of two)
 constexpr int T_RINGD = T_RING - 2 * T_ENT;     // largest cell distance served by the ring
@@ -63,7 +64,7 @@ struct ffm_tile_plan {
     TileDir f, b;
     double *mailAll = nullptr;
     long nMail = 0;
-    double *mailMulti = nullptr;    // [FFM_TILE_MAXSYS][nMail]: the mailboxes of the multi-system sweeps (k_tile_m), allocated on first use
+    double *mailMulti = nullptr;    // [FFM_TILE_MAXSYS][nMail]: the mailboxes of the sweeps of several systems, allocated on first use
     // ---- tiled Amul (symmetric matrices): same groups and entries as the forward sweep
     bool amulUsable = false;
     bool gsTables = false;          // the upper-neighbour and tail tables below exist (Gauss-Seidel sweeps, Amul tail)
@@ -366,8 +367,7 @@ struct TileView {
     const int *grpCell, *grpEnt, *extSrc;
     const int4 *rec;
     const uint2 *code;
-    double *mail;
-    unsigned int *ticket;       // [0] ticket counter, [1] abort word
+    unsigned int *ticket;      // [0] ticket counter, [1] abort word
 };
 
 __device__ __forceinline__ double t_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -397,37 +397,52 @@ __device__ __noinline__ double t_wait_value(const double *addr, unsigned int *ti
     return v;
 }
 
+// One kernel sweeps NF systems that share the off-diagonal coefficients (NF = 1: the matrix's own system).  The segregated solves of
+// a vector equation (fvMatrix::solveSegregated: the components of U differ in the boundary diagonal and the source only) and the
+// species equations under a multivariateSelection scheme (solver/YEEqn.H:43-60: one set of face weights, one diffusivity) are such
+// systems: neighbour codes and coefficients are read once, every system has its own ring in LDS, its own mailboxes and its own
+// diagonal / right-hand side / result; a level costs one barrier for all of them and their dependency chains interleave.
+// Per system i:
 // TM_FWD: w[c] = rD[c]*r[c] - sum_k rD[c]*a[c][k]*w[l_k]           (k ascending: the reference's face order)
 // TM_BWD: w[c] -= sum_k rD[c]*a[c][k]*w[u_k]                       (k descending)
 // TM_RD : D[c] = diag[c] - sum_k a[c][k]*b[c][k]/D[l_k]            (k ascending); D stays in the ring and the mailboxes, w[c] = 1/D[c]
-// TM_GSF: Gauss-Seidel forward row sweep: v = bPrime[c] - sum_k lower[c][k]*psi[l_k] (new values); aux[c] = v (kept for the
-//         reverse sweep of symGaussSeidel); v -= b[c][k] for k = 0..2 (b = upper*psi_old of the upper neighbours, computed
-//         by k_tile_gs_products; +0.0 where there is none); psi[c] = v/diag[c]
-// TM_GSB: reverse row sweep: v = aux[c] - sum_k upper[c][k]*psi[u_k] (new values, k ascending); psi[c] = v/diag[c]
+// (dg = rD for TM_FWD / TM_BWD, the diagonal for TM_RD)
 // The per-level path is issue-bound (one wave per SIMD runs the whole entry), so
 //   * waves 0-3 ("compute") are kept free of divergent branches: idle lanes work on a dummy cell, only stores are predicated;
 //   * wave 4 ("mail") does nothing but bring the external values of the next entry into LDS: entry record -> mailbox slot
 //     list -> mailbox values, each stage read ahead, re-loading a value while it still reads the sentinel.  Its few loads
 //     have a vmcnt stream of their own, so waiting for a mailbox value never waits for the compute waves' read-ahead.
 // Every wave executes the same number of workgroup barriers: one after the prologue, one per entry of the padded loop.
-// FUSE (PCG, DIC): the vector updates on either side of the preconditioner ride on the sweeps' own streams --
+// FUSE (PCG, DIC; one system): the vector updates on either side of the preconditioner ride on the sweeps' own streams --
 //   TM_FWD: aux = the residual, updated in place first: rA -= alpha*q (q = A pA: r when given, else w on entry; PCG.C "rA[cell] -= alpha*wA[cell]"),
 //           partials[group] = sum |rA| (the residual norm of the iteration that just ended);
 //   TM_BWD: partials[group] = sum wA*rA of the finished preconditioned residual (PCG.C wArA = gSumProd(wA, rA)).
 // The per-cell arithmetic is that of k_pcg_xr / the unfused sweep; only the order of the two sums differs (as in any reduction).
-template <int MODE, bool FUSE = false>
-__global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const double *__restrict__ ca, const double *__restrict__ cb,
-                                                         const double *__restrict__ dg, const double *__restrict__ r, double *w, double *aux,
-                                                         const double *__restrict__ scal = nullptr, double *__restrict__ partials = nullptr)
+// R: the ring length.  The plan's codes are LDS slots of a T_RING ring; a shorter ring (five rings of T_RING doubles do not fit the
+// LDS) takes an in-ring code modulo R and an external code rebased from T_RING to R, and serves plans whose ring neighbours lie
+// within R - 2*T_ENT cells (TileDir::reach, ffm_tile_multi_fits).
+constexpr int TM_PF = 4;            // read-ahead of the sweeps of several systems (NF systems' operands per slot)
+constexpr int TM_RING5 = 2048;
+// entries fetched ahead of the one being computed (register budget: one system 8, 6 with a second coefficient triple)
+constexpr int tile_pf(int NF, int MODE) { return NF > 1 ? TM_PF : (MODE == TM_RD || MODE == TM_GSF) ? 6 : T_PF; }
+static_assert(T_PM < TM_PF && tile_pf(1, TM_RD) <= T_PF && TM_PF <= T_PF, "read-ahead distances");
+template <int NF> struct TileSys { const double *dg[NF]; const double *r[NF]; double *w[NF]; double *mail[NF]; };
+
+template <int MODE, int NF, int R = T_RING, bool FUSE = false>
+__global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const double *__restrict__ ca, const double *__restrict__ cb, TileSys<NF> m,
+                                                         double *aux = nullptr, const double *__restrict__ scal = nullptr, double *__restrict__ partials = nullptr)
 {
+    static_assert(R <= T_RING && (R & (R - 1)) == 0 && R > 2 * T_ENT, "ring length");
     static_assert(!FUSE || MODE == TM_FWD || MODE == TM_BWD, "fused vector updates: DIC/DILU application only");
+    static_assert(MODE == TM_FWD || MODE == TM_BWD || MODE == TM_RD, "DILU / DIC application and calcReciprocalD (Gauss-Seidel: k_tile_gs)");
+    static_assert(NF == 1 || !FUSE, "fused vector updates: one system");
+    constexpr int LDS = R + 2 * T_XMAX + 1;
+    constexpr bool ASC = MODE != TM_BWD;
+    constexpr bool TWO = MODE == TM_RD;                         // a second triple of per-cell doubles (cb)
+    constexpr bool VEC = MODE != TM_RD;                         // a per-system vector operand (pv)
+    constexpr int W = T_W, PF = tile_pf(NF, MODE);
+    __shared__ double ring[NF][LDS];    // per system: ring of this group's values, the two halo buffers, the dummy slot
     __shared__ double shSum[4];
-    constexpr bool ASC = MODE != TM_BWD && MODE != TM_GSB;
-    constexpr bool TWO = MODE == TM_RD || MODE == TM_GSF;       // a second triple of per-cell doubles (cb)
-    constexpr int W = T_W;
-    constexpr int T_PF = TWO ? 6 : ::T_PF;                      // (register budget) read-ahead of this mode
-    __shared__ double ring[T_LDS];                    // ring of this group's values, the two halo buffers, the dummy slot
-    double *const halo = ring + T_RING;
     __shared__ int4 shRec[4];           // entry records handed from the mail wave to the compute waves
     __shared__ int shG;
     __shared__ int shAbort;
@@ -446,326 +461,9 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const doubl
     if (tid >= (unsigned)T_THREADS) {
         // ------------------------------------------------------------------ mail wave
         const unsigned lane = tid - (unsigned)T_THREADS;
-        int4 qrec[T_PF];                // record of entry e + 2*T_PF .. (slot = (e - e0) % T_PF)
-        unsigned qne[T_PF], qxi[T_PF];  // externals and this lane's mailbox slot of entry e + T_PF ..
-        double qxv[T_PF];               // mailbox value of entry e + T_PM ..
-#define Q_REC(k, e) { qrec[k] = t.rec[min((e), e1)]; }
-#define Q_IDX(k, e) { const int4 R_ = qrec[k]; qne[k] = ((e) < e1) ? ((unsigned)R_.y >> 16) : 0u; qxi[k] = (unsigned)t.extSrc[(unsigned)R_.w + (lane < qne[k] ? lane : 0u)]; }
-#define Q_MAIL(k) { qxv[k] = t_ld(&t.mail[lane < qne[k] ? qxi[k] : 0u]); }
-#define Q_PUT(k, e) {                                                                                    \
-        if (lane < qne[k]) {                                                                              \
-            double v_ = qxv[k];                                                                           \
-            if (__builtin_expect(t_pending(v_), 0)) v_ = t_wait_value(&t.mail[qxi[k]], t.ticket, &shAbort); \
-            halo[(((e) & 1) * T_XMAX) + lane] = v_;                                                       \
-        }                                                                                                 \
-    }
-#pragma unroll
-        for (int k = 0; k < T_PF; k++) Q_REC(k, e0 + k);
-#pragma unroll
-        for (int k = 0; k < T_PF; k++) { Q_IDX(k, e0 + k); Q_REC(k, e0 + T_PF + k); }
-#pragma unroll
-        for (int k = 0; k < T_PM; k++) Q_MAIL(k);
-        Q_PUT(0, e0);
-        if (lane == 0) shRec[(e0 + T_PF) & 3] = qrec[0];
-        t_barrier();
-        for (int e = e0; e < e1; e += T_PF) {
-#pragma unroll
-            for (int k = 0; k < T_PF; k++) {
-                const int ee = e + k;
-                Q_PUT((k + 1) % T_PF, ee + 1);          // externals of the next entry
-                if (lane == 0) shRec[(ee + 1 + T_PF) & 3] = qrec[(k + 1) % T_PF];     // record the compute waves fetch from next
-                Q_IDX(k, ee + T_PF);
-                Q_REC(k, ee + 2 * T_PF);
-                Q_MAIL((k + T_PM) % T_PF);
-                t_barrier();
-            }
-        }
-#undef Q_REC
-#undef Q_IDX
-#undef Q_MAIL
-#undef Q_PUT
-        return;             // (the fused sums are reduced by the compute waves alone)
-    }
-
-    // ---------------------------------------------------------------------- compute waves
-    // read-ahead registers: slot k serves the entries e with (e - e0) % T_PF == k
-    unsigned pc[T_PF], ppb[T_PF];
-    bool pok[T_PF];
-    uint2 pq[T_PF];
-    double pa[T_PF][W], pb[T_PF][TWO ? W : 1], pd[T_PF], pv[T_PF], pv2[FUSE ? T_PF : 1];
-    double fsum = 0.0;
-    const double fAlpha = (FUSE && MODE == TM_FWD) ? scal[S_ALPHA] : 0.0;
-    const bool fSing = (FUSE && MODE == TM_FWD) ? (scal[S_SING] != 0.0) : false;
-#define T_FETCH(k, e, R_) {                                                                             \
-        const unsigned cnt_ = ((e) < e1) ? ((unsigned)R_.y & 0xFFFFu) : 0u;                              \
-        const bool ok_ = tid < cnt_;                                                                     \
-        const unsigned cc_ = ok_ ? (ASC ? (unsigned)R_.x + tid : (unsigned)R_.x + cnt_ - 1u - tid) : gs; \
-        const unsigned o8_ = cc_ * 8u, o24_ = cc_ * 24u;        /* 32-bit byte offsets: arrays < 4 GiB (host check) */  \
-        pq[k] = *(const uint2 *)((const char *)t.code + o8_);                                            \
-        { const T3 v_ = *(const T3 *)((const char *)ca + o24_); pa[k][0] = v_.a; pa[k][1] = v_.b; pa[k][2] = v_.c; }     \
-        if (TWO) { const T3 v_ = *(const T3 *)((const char *)cb + o24_); pb[k][0] = v_.a; pb[k][TWO ? 1 : 0] = v_.b; pb[k][TWO ? 2 : 0] = v_.c; } \
-        pd[k] = *(const double *)((const char *)dg + o8_);                                               \
-        pv[k] = (FUSE && MODE == TM_FWD) ? *(const double *)((const char *)aux + o8_) : (MODE == TM_FWD || MODE == TM_GSF || MODE == TM_GSB) ? *(const double *)((const char *)r + o8_) : (MODE == TM_BWD ? *(const double *)((const char *)w + o8_) : 0.0); \
-        if (FUSE) pv2[FUSE ? k : 0] = (MODE == TM_FWD) ? *(const double *)((const char *)(r ? r : (const double *)w) + o8_) : *(const double *)((const char *)r + o8_); \
-        pc[k] = cc_; pok[k] = ok_; ppb[k] = (unsigned)R_.z;                                              \
-    }
-#pragma unroll
-    for (int k = 0; k < T_PF; k++) { const int4 R0 = t.rec[min(e0 + k, e1)]; T_FETCH(k, e0 + k, R0); }
-    t_barrier();
-    for (int e = e0; e < e1; e += T_PF) {
-#pragma unroll
-        for (int k = 0; k < T_PF; k++) {
-            const int ee = e + k;                           // entries past e1 are padding of the unrolled loop: barriers only
-            const int4 Rn = shRec[(ee + T_PF) & 3];         // record of the entry to fetch below (from the mail wave)
-            // ---- entry ee from slot k (idle lanes work on the dummy cell gs; nothing of theirs is stored)
-            {
-                const unsigned c = pc[k];
-                const unsigned cd[4] = {pq[k].x & 0xFFFFu, pq[k].x >> 16, pq[k].y & 0xFFFFu, pq[k].y >> 16};
-                double x[W];
-#pragma unroll
-                for (int s = 0; s < W; s++) x[s] = ring[min(cd[s], (unsigned)(T_LDS - 1))];     // the plan stores the LDS slot itself
-                const double d = pd[k];
-                double val;
-                if (MODE == TM_FWD) {
-                    double ri = pv[k];
-                    if (FUSE) {
-                        if (!fSing) { ri -= fAlpha * pv2[FUSE ? k : 0]; if (pok[k]) *(double *)((char *)aux + c * 8u) = ri; }
-                        fsum += pok[k] ? fabs(ri) : 0.0;
-                    }
-                    val = d * ri;
-#pragma unroll
-                    for (int s = 0; s < W; s++) { const double nv = val - d * pa[k][s] * x[s]; val = (cd[s] != T_NONE) ? nv : val; }
-                } else if (MODE == TM_BWD) {
-                    val = pv[k];
-#pragma unroll
-                    for (int s = W - 1; s >= 0; s--) { const double nv = val - d * pa[k][s] * x[s]; val = (cd[s] != T_NONE) ? nv : val; }
-                } else if (MODE == TM_RD) {
-                    val = d;
-#pragma unroll
-                    for (int s = 0; s < W; s++) { const double nv = val - pa[k][s] * pb[k][TWO ? s : 0] / x[s]; val = (cd[s] != T_NONE) ? nv : val; }
-                } else if (MODE == TM_GSF) {
-                    val = pv[k];
-#pragma unroll
-                    for (int s = 0; s < W; s++) { const double nv = val - pa[k][s] * x[s]; val = (cd[s] != T_NONE) ? nv : val; }
-                    if (pok[k]) *(double *)((char *)aux + c * 8u) = val;
-#pragma unroll
-                    for (int s = 0; s < W; s++) val -= pb[k][TWO ? s : 0];
-                    val = val / d;
-                } else {
-                    val = pv[k];
-#pragma unroll
-                    for (int s = 0; s < W; s++) { const double nv = val - pa[k][s] * x[s]; val = (cd[s] != T_NONE) ? nv : val; }
-                    val = val / d;
-                }
-                if (pok[k]) { *(double *)((char *)w + c * 8u) = (MODE == TM_RD) ? 1.0 / val : val; ring[(c - gs) & (unsigned)(T_RING - 1)] = val; }
-                if (FUSE && MODE == TM_BWD) fsum += pok[k] ? val * pv2[FUSE ? k : 0] : 0.0;
-                if (pok[k] && cd[3] != T_NONE) t_st(&t.mail[ppb[k] + cd[3]], val);
-            }
-            // ---- refill slot k with entry ee + T_PF
-            T_FETCH(k, ee + T_PF, Rn);
-            t_barrier();                                    // one barrier per level: ring and halo are visible to the next entry
-        }
-    }
-#undef T_FETCH
-    if (FUSE) {             // the four compute waves (the mail wave has left): wave sums through LDS, lane 0 adds them in wave order
-        double v = fsum;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if ((tid & 63u) == 0u) shSum[tid >> 6] = v;
-        t_barrier();
-        if (tid == 0) partials[g] = ((shSum[0] + shSum[1]) + shSum[2]) + shSum[3];
-    }
-}
-
-// out[i] = native[src[i]] (0 where a cell has fewer than T_W neighbours): coefficients in the kernel's cell-major layout
-__global__ void k_tile_gather(long n, const int *__restrict__ src, const double *__restrict__ native, double *__restrict__ out)
-{
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int q = src[i];
-        out[i] = (q >= 0) ? native[q] : 0.0;
-    }
-}
-// mailbox fill before a sweep (pair); it also zeroes the group ticket counter, so that the 32-bit counter never wraps and every
-// launch hands its groups out as ticket % G with ticket < 2 G (forward sweep 0..G-1, backward sweep G..2G-1)
-__global__ void k_tile_fill(long n, unsigned long long *p, unsigned long long v, unsigned int *ticket)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0) ticket[0] = 0u;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
-}
-
-static TileView tview(const ffm_ldu *A, const TileDir &d)
-{
-    TileView t; t.G = A->tile->G; t.grpCell = A->grpCell; t.grpEnt = d.grpEnt; t.extSrc = d.extSrc; t.rec = d.rec;
-    t.code = (const uint2 *)d.code; t.mail = d.mail; t.ticket = A->sweepTicket;
-    return t;
-}
-
-// gathered coefficients of one direction, refreshed when the matrix coefficients changed
-static int tile_coef(ffm_ldu *A, TileDir &d, bool upper, const double **out)
-{
-    const long n = (long)T_W * A->nOwned;
-    double *&buf = upper ? d.coefU : d.coefL;
-    unsigned long &ep = upper ? d.epochU : d.epochL;
-    if (!buf) { FFM_HIP(hipMalloc((void **)&buf, sizeof(double) * std::max<long>(n, 1))); ep = ~0ul; }
-    if (ep != A->offDiagEpoch) {
-        const int g = std::max(1, std::min(ffm_grid(n, 256), 8 * RED_BLOCKS));
-        hipLaunchKernelGGL(k_tile_gather, dim3(g), dim3(256), 0, A->ctx->stream, n, d.src, upper ? A->upper : A->lower, buf);
-        ep = A->offDiagEpoch;
-    }
-    *out = buf;
-    return FFM_OK;
-}
-
-static void tile_fill(ffm_ldu *A, double *p, long n)
-{
-    const int g = std::max(1, std::min(ffm_grid(n, 256), 8 * RED_BLOCKS));
-    hipLaunchKernelGGL(k_tile_fill, dim3(g), dim3(256), 0, A->ctx->stream, n, (unsigned long long *)p, T_SENT, A->sweepTicket);
-}
-
-int ffm_tile_precond(ffm_ldu *A, int precond, bool transpose, const double *r, double *w)
-{
-    ffm_tile_plan *T = A->tile;
-    hipStream_t s = A->ctx->stream;
-    // forward coefficient: DIC upper; DILU lower; DILU^T upper.  backward: DIC upper; DILU upper; DILU^T lower.
-    const bool fwdUpper = (precond == FFM_DIC) || transpose;
-    const bool bwdUpper = (precond == FFM_DIC) || !transpose;
-    const double *cf, *cb;
-    FFM_TRY(tile_coef(A, T->f, fwdUpper, &cf));
-    FFM_TRY(tile_coef(A, T->b, bwdUpper, &cb));
-    tile_fill(A, T->mailAll, T->nMail);
-    hipLaunchKernelGGL(k_tile<TM_FWD>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
-    hipLaunchKernelGGL(k_tile<TM_BWD>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr, (const double *)A->rD, r, w, (double *)nullptr);
-    FFM_HIP(hipGetLastError());
-    return FFM_OK;
-}
-
-__global__ void k_tile_sum_partials(int n, const double *__restrict__ partials, double *__restrict__ scal, int slot);
-// PCG with DIC on a tile plan: the two halves of the preconditioner application with the neighbouring vector
-// updates fused in (k_tile<.., FUSE>).  Forward: rA -= scal[S_ALPHA]*wA, scal[slot] = sum |rA| (local), wA = forward sweep of rA.
-// Backward: finishes wA, scal[slot] = sum wA*rA (local).
-bool ffm_tile_pcg_fusable(const ffm_ldu *A)
-{
-    const char *e = getenv("FFM_PCG_UNFUSED");
-    const bool off = e && atoi(e) != 0;
-    return !off && ffm_tile_usable(A) && A->tile->G <= 4 * RED_BLOCKS;
-}
-int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double *qA)
-{
-    ffm_tile_plan *T = A->tile;
-    hipStream_t s = A->ctx->stream;
-    const double *cf, *cb;
-    FFM_TRY(tile_coef(A, T->f, true, &cf));
-    FFM_TRY(tile_coef(A, T->b, true, &cb));
-    tile_fill(A, T->mailAll, T->nMail);
-    hipLaunchKernelGGL((k_tile<TM_FWD, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cf, (const double *)nullptr,
-                       (const double *)A->rD, qA, wA, rA, (const double *)A->ctx->scal_d, A->ctx->partials_d);
-    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
-    FFM_HIP(hipGetLastError());
-    return FFM_OK;
-}
-int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot)
-{
-    ffm_tile_plan *T = A->tile;
-    hipStream_t s = A->ctx->stream;
-    const double *cb;
-    FFM_TRY(tile_coef(A, T->b, true, &cb));
-    hipLaunchKernelGGL((k_tile<TM_BWD, true>), dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cb, (const double *)nullptr,
-                       (const double *)A->rD, rA, wA, (double *)nullptr, (const double *)A->ctx->scal_d, A->ctx->partials_d);
-    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
-    FFM_HIP(hipGetLastError());
-    return FFM_OK;
-}
-
-// upper*psi_old of the (owned) upper neighbours of every cell, slot by slot; +0.0 where a cell has fewer than three
-__global__ void k_tile_gs_products(long n3, const int *__restrict__ nbrCell, const double *__restrict__ coef, const double *__restrict__ psi,
-                                   double *__restrict__ out)
-{
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n3; i += (long)gridDim.x * blockDim.x) {
-        const int nb = nbrCell[i];
-        out[i] = (nb >= 0) ? coef[i] * psi[nb] : 0.0;
-    }
-}
-
-// One GaussSeidelSmoother / symGaussSeidelSmoother sweep (forward rows, then reverse rows when sym): psi in place, bP = bPrime
-// (source with the lagged interface terms), bSave = scratch [nCells].  prod = scratch [3*nCells].
-int ffm_tile_gs(ffm_ldu *A, bool sym, double *psi, const double *bP, double *bSave, double *prod)
-{
-    ffm_tile_plan *T = A->tile;
-    hipStream_t s = A->ctx->stream;
-    const double *cl, *cu;
-    FFM_TRY(tile_coef(A, T->f, A->lower == A->upper, &cl));        // lower coefficients, lower-neighbour layout
-    FFM_TRY(tile_coef(A, T->b, true, &cu));                         // upper coefficients, upper-neighbour layout
-    const long n3 = (long)T_W * A->nOwned;
-    hipLaunchKernelGGL(k_tile_gs_products, dim3(std::max(1, std::min(ffm_grid(n3, 256), 8 * RED_BLOCKS))), dim3(256), 0, s, n3,
-                       (const int *)T->upNbrCell, cu, (const double *)psi, prod);
-    tile_fill(A, T->mailAll, T->nMail);
-    hipLaunchKernelGGL(k_tile<TM_GSF>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), cl, (const double *)prod, (const double *)A->diag, bP, psi, bSave);
-    if (sym)
-        hipLaunchKernelGGL(k_tile<TM_GSB>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), cu, (const double *)nullptr, (const double *)A->diag,
-                           (const double *)bSave, psi, (double *)nullptr);
-    FFM_HIP(hipGetLastError());
-    return FFM_OK;
-}
-
-// rD = 1/D, D = diag - sum upper*lower/D[l] in face order
-int ffm_tile_calc_rD(ffm_ldu *A)
-{
-    ffm_tile_plan *T = A->tile;
-    const double *cu, *cl;
-    FFM_TRY(tile_coef(A, T->f, true, &cu));
-    if (A->lower == A->upper) cl = cu; else FFM_TRY(tile_coef(A, T->f, false, &cl));
-    tile_fill(A, T->f.mail, (long)T->f.nPub + 1);
-    hipLaunchKernelGGL(k_tile<TM_RD>, dim3(T->G), dim3(T_THREADS + 64), 0, A->ctx->stream, tview(A, T->f), cu, cl, (const double *)A->diag,
-                       (const double *)nullptr, A->rD, (double *)nullptr);
-    FFM_HIP(hipGetLastError());
-    return FFM_OK;
-}
-
-// ------------------------------------------------------------------ several systems in one sweep ---
-// The segregated solves of a vector equation (fvMatrix::solveSegregated: the components of U differ in the boundary diagonal and the
-// source only) and the species equations under a multivariateSelection scheme (solver/YEEqn.H:43-60: one set of face weights, one
-// diffusivity) have the SAME off-diagonal coefficients.  k_tile_m sweeps NF such systems at once: neighbour codes and coefficients are
-// read once, every system has its own ring in LDS, its own mailboxes and its own rD / right-hand side / result; a level costs one
-// barrier for all of them and their dependency chains interleave.  Per system the arithmetic is k_tile's, operation for operation.
-constexpr int TM_PF = 4;            // read-ahead of the multi-system sweeps (NF systems' operands per slot)
-static_assert(T_PM < TM_PF, "read-ahead distances");
-template <int NF> struct TileMulti { const double *dg[NF]; const double *r[NF]; double *w[NF]; double *mail[NF]; };
-
-// R: the ring length.  The plan's codes are LDS slots of a T_RING ring; a shorter ring (five rings of T_RING doubles do not fit the
-// LDS) takes an in-ring code modulo R and an external code rebased from T_RING to R, and serves plans whose ring neighbours lie
-// within R - 2*T_ENT cells (TileDir::reach, ffm_tile_multi_fits).
-constexpr int TM_RING5 = 2048;
-template <int MODE, int NF, int R = T_RING>
-__global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const double *__restrict__ ca, const double *__restrict__ cb, TileMulti<NF> m)
-{
-    static_assert(R <= T_RING && (R & (R - 1)) == 0 && R > 2 * T_ENT, "ring length");
-    constexpr int LDS = R + 2 * T_XMAX + 1;
-    static_assert(MODE == TM_FWD || MODE == TM_BWD || MODE == TM_RD, "DILU / DIC application and calcReciprocalD");
-    constexpr bool ASC = MODE != TM_BWD;
-    constexpr bool TWO = MODE == TM_RD;
-    constexpr int W = T_W, PF = TM_PF;
-    __shared__ double ring[NF][LDS];
-    __shared__ int4 shRec[4];
-    __shared__ int shG;
-    __shared__ int shAbort;
-    const unsigned tid = threadIdx.x;
-    if (tid == 0) {
-        const unsigned tk = atomicAdd(&t.ticket[0], 1u);
-        const int k = (int)(tk % (unsigned)t.G);
-        shG = ASC ? k : t.G - 1 - k; shAbort = 0;
-    }
-    __syncthreads();
-    const int g = __builtin_amdgcn_readfirstlane(shG);
-    const unsigned gs = (unsigned)__builtin_amdgcn_readfirstlane(t.grpCell[g]);
-    const int e0 = __builtin_amdgcn_readfirstlane(t.grpEnt[g]), e1 = __builtin_amdgcn_readfirstlane(t.grpEnt[g + 1]);
-    if (e0 >= e1) return;
-
-    if (tid >= (unsigned)T_THREADS) {
-        // ------------------------------------------------------------------ mail wave (as in k_tile, NF values per external)
-        const unsigned lane = tid - (unsigned)T_THREADS;
-        int4 qrec[PF];
-        unsigned qne[PF], qxi[PF];
-        double qxv[PF][NF];
+        int4 qrec[PF];                  // record of entry e + 2*PF .. (slot = (e - e0) % PF)
+        unsigned qne[PF], qxi[PF];      // externals and this lane's mailbox slot of entry e + PF ..
+        double qxv[PF][NF];             // mailbox values of entry e + T_PM ..
 #define Q_REC(k, e) { qrec[k] = t.rec[min((e), e1)]; }
 #define Q_IDX(k, e) { const int4 R_ = qrec[k]; qne[k] = ((e) < e1) ? ((unsigned)R_.y >> 16) : 0u; qxi[k] = (unsigned)t.extSrc[(unsigned)R_.w + (lane < qne[k] ? lane : 0u)]; }
 #define Q_MAIL(k) { _Pragma("unroll") for (int i_ = 0; i_ < NF; i_++) qxv[k][i_] = t_ld(&m.mail[i_][lane < qne[k] ? qxi[k] : 0u]); }
@@ -791,8 +489,189 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
 #pragma unroll
             for (int k = 0; k < PF; k++) {
                 const int ee = e + k;
-                Q_PUT((k + 1) % PF, ee + 1);
-                if (lane == 0) shRec[(ee + 1 + PF) & 3] = qrec[(k + 1) % PF];
+                Q_PUT((k + 1) % PF, ee + 1);            // externals of the next entry
+                if (lane == 0) shRec[(ee + 1 + PF) & 3] = qrec[(k + 1) % PF];         // record the compute waves fetch from next
+                Q_IDX(k, ee + PF);
+                Q_REC(k, ee + 2 * PF);
+                Q_MAIL((k + T_PM) % PF);
+                t_barrier();
+            }
+        }
+#undef Q_REC
+#undef Q_IDX
+#undef Q_MAIL
+#undef Q_PUT
+        return;             // (the fused sums are reduced by the compute waves alone)
+    }
+
+    // ---------------------------------------------------------------------- compute waves
+    // read-ahead registers: slot k serves the entries e with (e - e0) % PF == k
+    unsigned pc[PF], ppb[PF];
+    bool pok[PF];
+    uint2 pq[PF];
+    double pa[PF][W], pb[PF][TWO ? W : 1], pd[PF][NF], pv[PF][VEC ? NF : 1], pv2[FUSE ? PF : 1];
+    double fsum = 0.0;
+    const double fAlpha = (FUSE && MODE == TM_FWD) ? scal[S_ALPHA] : 0.0;
+    const bool fSing = (FUSE && MODE == TM_FWD) ? (scal[S_SING] != 0.0) : false;
+#define T_FETCH(k, e, R_) {                                                                             \
+        const unsigned cnt_ = ((e) < e1) ? ((unsigned)R_.y & 0xFFFFu) : 0u;                              \
+        const bool ok_ = tid < cnt_;                                                                     \
+        const unsigned cc_ = ok_ ? (ASC ? (unsigned)R_.x + tid : (unsigned)R_.x + cnt_ - 1u - tid) : gs; \
+        const unsigned o8_ = cc_ * 8u, o24_ = cc_ * 24u;        /* 32-bit byte offsets: arrays < 4 GiB (host check) */  \
+        pq[k] = *(const uint2 *)((const char *)t.code + o8_);                                            \
+        { const T3 v_ = *(const T3 *)((const char *)ca + o24_); pa[k][0] = v_.a; pa[k][1] = v_.b; pa[k][2] = v_.c; }     \
+        if (TWO) { const T3 v_ = *(const T3 *)((const char *)cb + o24_); pb[k][0] = v_.a; pb[k][TWO ? 1 : 0] = v_.b; pb[k][TWO ? 2 : 0] = v_.c; } \
+        _Pragma("unroll") for (int i_ = 0; i_ < NF; i_++) {                                              \
+            pd[k][i_] = *(const double *)((const char *)m.dg[i_] + o8_);                                 \
+            if (VEC) pv[k][VEC ? i_ : 0] = *(const double *)((const char *)((FUSE && MODE == TM_FWD) ? (const double *)aux : MODE == TM_BWD ? (const double *)m.w[i_] : m.r[i_]) + o8_); \
+        }                                                                                                \
+        if (FUSE) pv2[FUSE ? k : 0] = *(const double *)((const char *)((MODE == TM_FWD && !m.r[0]) ? (const double *)m.w[0] : m.r[0]) + o8_); \
+        pc[k] = cc_; pok[k] = ok_; ppb[k] = (unsigned)R_.z;                                              \
+    }
+#pragma unroll
+    for (int k = 0; k < PF; k++) { const int4 R0 = t.rec[min(e0 + k, e1)]; T_FETCH(k, e0 + k, R0); }
+    t_barrier();
+    for (int e = e0; e < e1; e += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; k++) {
+            const int ee = e + k;                           // entries past e1 are padding of the unrolled loop: barriers only
+            const int4 Rn = shRec[(ee + PF) & 3];           // record of the entry to fetch below (from the mail wave)
+            // ---- entry ee from slot k (idle lanes work on the dummy cell gs; nothing of theirs is stored)
+            {
+                const unsigned c = pc[k];
+                const unsigned cd[4] = {pq[k].x & 0xFFFFu, pq[k].x >> 16, pq[k].y & 0xFFFFu, pq[k].y >> 16};
+                unsigned sl[W];                             // the plan stores the LDS slot itself (of a T_RING ring)
+#pragma unroll
+                for (int s = 0; s < W; s++)
+                    sl[s] = (R == T_RING) ? min(cd[s], (unsigned)(LDS - 1))
+                                          : (cd[s] < (unsigned)T_RING ? (cd[s] & (unsigned)(R - 1)) : min(cd[s] - (unsigned)(T_RING - R), (unsigned)(LDS - 1)));
+                double val[NF];
+#pragma unroll
+                for (int i = 0; i < NF; i++) {
+                    const double d = pd[k][i], v0 = VEC ? pv[k][VEC ? i : 0] : 0.0;
+                    double x[W], v;         // one system: the three LDS reads are issued ahead of the arithmetic (issue-bound path)
+                    if (NF == 1) {
+#pragma unroll
+                        for (int s = 0; s < W; s++) x[s] = ring[i][sl[s]];
+                    }
+#define T_X(s) (NF == 1 ? x[s] : ring[i][sl[s]])
+                    if (MODE == TM_FWD) {
+                        double ri = v0;
+                        if (FUSE) {
+                            if (!fSing) { ri -= fAlpha * pv2[FUSE ? k : 0]; if (pok[k]) *(double *)((char *)aux + c * 8u) = ri; }
+                            fsum += pok[k] ? fabs(ri) : 0.0;
+                        }
+                        v = d * ri;
+#pragma unroll
+                        for (int s = 0; s < W; s++) { const double nv = v - d * pa[k][s] * T_X(s); v = (cd[s] != T_NONE) ? nv : v; }
+                    } else if (MODE == TM_BWD) {
+                        v = v0;
+#pragma unroll
+                        for (int s = W - 1; s >= 0; s--) { const double nv = v - d * pa[k][s] * T_X(s); v = (cd[s] != T_NONE) ? nv : v; }
+                    } else {
+                        v = d;
+#pragma unroll
+                        for (int s = 0; s < W; s++) { const double nv = v - pa[k][s] * pb[k][TWO ? s : 0] / T_X(s); v = (cd[s] != T_NONE) ? nv : v; }
+                    }
+                    val[i] = v;
+#undef T_X
+                }
+                // the stores of an active lane.  One system: two predicated blocks, so that the arithmetic above stays outside them
+                // (issue-bound path, see above); several: one block (the form their register budget was tuned with)
+#define T_PUT(i) { *(double *)((char *)m.w[i] + c * 8u) = (MODE == TM_RD) ? 1.0 / val[i] : val[i]; ring[i][(c - gs) & (unsigned)(R - 1)] = val[i]; }
+#define T_POST(i) { if (cd[3] != T_NONE) t_st(&m.mail[i][ppb[k] + cd[3]], val[i]); }
+                if (NF == 1) {
+                    if (pok[k]) T_PUT(0);
+                    if (FUSE && MODE == TM_BWD) fsum += pok[k] ? val[0] * pv2[FUSE ? k : 0] : 0.0;
+                    if (pok[k]) T_POST(0);
+                } else if (pok[k]) {
+#pragma unroll
+                    for (int i = 0; i < NF; i++) { T_PUT(i); T_POST(i); }
+                }
+#undef T_PUT
+#undef T_POST
+            }
+            // ---- refill slot k with entry ee + PF
+            T_FETCH(k, ee + PF, Rn);
+            t_barrier();                                    // one barrier per level: ring and halo are visible to the next entry
+        }
+    }
+#undef T_FETCH
+    if (FUSE) {             // the four compute waves (the mail wave has left): wave sums through LDS, lane 0 adds them in wave order
+        double v = fsum;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if ((tid & 63u) == 0u) shSum[tid >> 6] = v;
+        t_barrier();
+        if (tid == 0) partials[g] = ((shSum[0] + shSum[1]) + shSum[2]) + shSum[3];
+    }
+}
+
+// The Gauss-Seidel row sweeps of the matrix's own system keep a kernel of their own: as NF = 1 instantiations of k_tile the forward sweep
+// ran 1.4 % slower at 200^3 than this form, whatever read-ahead depth or store order was tried (profiles/README.md), and the sweep is
+// bound by its per-level issue path.  Same plan, same mailbox protocol, same wave roles and barrier discipline as k_tile.
+// TM_GSF: forward row sweep: v = bPrime[c] - sum_k lower[c][k]*psi[l_k] (new values); aux[c] = v (kept for the reverse sweep of
+//         symGaussSeidel); v -= b[c][k] for k = 0..2 (b = upper*psi_old of the upper neighbours, computed by k_tile_gs_products;
+//         +0.0 where there is none); psi[c] = v/diag[c]
+// TM_GSB: reverse row sweep: v = aux[c] - sum_k upper[c][k]*psi[u_k] (new values, k ascending); psi[c] = v/diag[c]
+// (dg = the diagonal, r = bPrime / aux, w = psi)
+template <int MODE>
+__global__ __launch_bounds__(T_THREADS + 64) void k_tile_gs(TileView t, double *mail, const double *__restrict__ ca, const double *__restrict__ cb,
+                                                            const double *__restrict__ dg, const double *__restrict__ r, double *w, double *aux)
+{
+    static_assert(MODE == TM_GSF || MODE == TM_GSB, "the Gauss-Seidel row sweeps");
+    constexpr bool ASC = MODE != TM_GSB;
+    constexpr bool TWO = MODE == TM_GSF;        // a second triple of per-cell doubles (cb)
+    constexpr int W = T_W;
+    constexpr int PF = tile_pf(1, MODE);
+    __shared__ double ring[T_LDS];                    // ring of this group's values, the two halo buffers, the dummy slot
+    double *const halo = ring + T_RING;
+    __shared__ int4 shRec[4];           // entry records handed from the mail wave to the compute waves
+    __shared__ int shG;
+    __shared__ int shAbort;
+    const unsigned tid = threadIdx.x;
+    if (tid == 0) {
+        const unsigned tk = atomicAdd(&t.ticket[0], 1u);
+        const int k = (int)(tk % (unsigned)t.G);
+        shG = ASC ? k : t.G - 1 - k; shAbort = 0;
+    }
+    __syncthreads();
+    const int g = __builtin_amdgcn_readfirstlane(shG);
+    const unsigned gs = (unsigned)__builtin_amdgcn_readfirstlane(t.grpCell[g]);
+    const int e0 = __builtin_amdgcn_readfirstlane(t.grpEnt[g]), e1 = __builtin_amdgcn_readfirstlane(t.grpEnt[g + 1]);
+    if (e0 >= e1) return;
+
+    if (tid >= (unsigned)T_THREADS) {
+        // ------------------------------------------------------------------ mail wave
+        const unsigned lane = tid - (unsigned)T_THREADS;
+        int4 qrec[PF];                // record of entry e + 2*PF .. (slot = (e - e0) % PF)
+        unsigned qne[PF], qxi[PF];  // externals and this lane's mailbox slot of entry e + PF ..
+        double qxv[PF];               // mailbox value of entry e + T_PM ..
+#define Q_REC(k, e) { qrec[k] = t.rec[min((e), e1)]; }
+#define Q_IDX(k, e) { const int4 R_ = qrec[k]; qne[k] = ((e) < e1) ? ((unsigned)R_.y >> 16) : 0u; qxi[k] = (unsigned)t.extSrc[(unsigned)R_.w + (lane < qne[k] ? lane : 0u)]; }
+#define Q_MAIL(k) { qxv[k] = t_ld(&mail[lane < qne[k] ? qxi[k] : 0u]); }
+#define Q_PUT(k, e) {                                                                                    \
+        if (lane < qne[k]) {                                                                              \
+            double v_ = qxv[k];                                                                           \
+            if (__builtin_expect(t_pending(v_), 0)) v_ = t_wait_value(&mail[qxi[k]], t.ticket, &shAbort); \
+            halo[(((e) & 1) * T_XMAX) + lane] = v_;                                                       \
+        }                                                                                                 \
+    }
+#pragma unroll
+        for (int k = 0; k < PF; k++) Q_REC(k, e0 + k);
+#pragma unroll
+        for (int k = 0; k < PF; k++) { Q_IDX(k, e0 + k); Q_REC(k, e0 + PF + k); }
+#pragma unroll
+        for (int k = 0; k < T_PM; k++) Q_MAIL(k);
+        Q_PUT(0, e0);
+        if (lane == 0) shRec[(e0 + PF) & 3] = qrec[0];
+        t_barrier();
+        for (int e = e0; e < e1; e += PF) {
+#pragma unroll
+            for (int k = 0; k < PF; k++) {
+                const int ee = e + k;
+                Q_PUT((k + 1) % PF, ee + 1);          // externals of the next entry
+                if (lane == 0) shRec[(ee + 1 + PF) & 3] = qrec[(k + 1) % PF];     // record the compute waves fetch from next
                 Q_IDX(k, ee + PF);
                 Q_REC(k, ee + 2 * PF);
                 Q_MAIL((k + T_PM) % PF);
@@ -807,82 +686,114 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_m(TileView t, const dou
     }
 
     // ---------------------------------------------------------------------- compute waves
+    // read-ahead registers: slot k serves the entries e with (e - e0) % PF == k
     unsigned pc[PF], ppb[PF];
     bool pok[PF];
     uint2 pq[PF];
-    double pa[PF][W], pb[PF][TWO ? W : 1], pd[PF][NF], pv[PF][TWO ? 1 : NF];
-#define TM_FETCH(k, e, R_) {                                                                            \
+    double pa[PF][W], pb[PF][TWO ? W : 1], pd[PF], pv[PF];
+#define T_FETCH(k, e, R_) {                                                                             \
         const unsigned cnt_ = ((e) < e1) ? ((unsigned)R_.y & 0xFFFFu) : 0u;                              \
         const bool ok_ = tid < cnt_;                                                                     \
         const unsigned cc_ = ok_ ? (ASC ? (unsigned)R_.x + tid : (unsigned)R_.x + cnt_ - 1u - tid) : gs; \
-        const unsigned o8_ = cc_ * 8u, o24_ = cc_ * 24u;                                                 \
+        const unsigned o8_ = cc_ * 8u, o24_ = cc_ * 24u;        /* 32-bit byte offsets: arrays < 4 GiB (host check) */  \
         pq[k] = *(const uint2 *)((const char *)t.code + o8_);                                            \
         { const T3 v_ = *(const T3 *)((const char *)ca + o24_); pa[k][0] = v_.a; pa[k][1] = v_.b; pa[k][2] = v_.c; }     \
         if (TWO) { const T3 v_ = *(const T3 *)((const char *)cb + o24_); pb[k][0] = v_.a; pb[k][TWO ? 1 : 0] = v_.b; pb[k][TWO ? 2 : 0] = v_.c; } \
-        _Pragma("unroll") for (int i_ = 0; i_ < NF; i_++) {                                              \
-            pd[k][i_] = *(const double *)((const char *)m.dg[i_] + o8_);                                 \
-            if (!TWO) pv[k][TWO ? 0 : i_] = *(const double *)((const char *)(MODE == TM_FWD ? m.r[i_] : (const double *)m.w[i_]) + o8_); \
-        }                                                                                                \
+        pd[k] = *(const double *)((const char *)dg + o8_);                                               \
+        pv[k] = *(const double *)((const char *)r + o8_);                                                \
         pc[k] = cc_; pok[k] = ok_; ppb[k] = (unsigned)R_.z;                                              \
     }
 #pragma unroll
-    for (int k = 0; k < PF; k++) { const int4 R0 = t.rec[min(e0 + k, e1)]; TM_FETCH(k, e0 + k, R0); }
+    for (int k = 0; k < PF; k++) { const int4 R0 = t.rec[min(e0 + k, e1)]; T_FETCH(k, e0 + k, R0); }
     t_barrier();
     for (int e = e0; e < e1; e += PF) {
 #pragma unroll
         for (int k = 0; k < PF; k++) {
-            const int ee = e + k;
-            const int4 Rn = shRec[(ee + PF) & 3];
+            const int ee = e + k;                           // entries past e1 are padding of the unrolled loop: barriers only
+            const int4 Rn = shRec[(ee + PF) & 3];         // record of the entry to fetch below (from the mail wave)
+            // ---- entry ee from slot k (idle lanes work on the dummy cell gs; nothing of theirs is stored)
             {
                 const unsigned c = pc[k];
                 const unsigned cd[4] = {pq[k].x & 0xFFFFu, pq[k].x >> 16, pq[k].y & 0xFFFFu, pq[k].y >> 16};
-                unsigned sl[W];
+                double x[W];
 #pragma unroll
-                for (int s = 0; s < W; s++)
-                    sl[s] = (R == T_RING) ? min(cd[s], (unsigned)(LDS - 1))
-                                          : (cd[s] < (unsigned)T_RING ? (cd[s] & (unsigned)(R - 1)) : min(cd[s] - (unsigned)(T_RING - R), (unsigned)(LDS - 1)));
-                double val[NF];
+                for (int s = 0; s < W; s++) x[s] = ring[min(cd[s], (unsigned)(T_LDS - 1))];     // the plan stores the LDS slot itself
+                const double d = pd[k];
+                double val;
+                if (MODE == TM_GSF) {
+                    val = pv[k];
 #pragma unroll
-                for (int i = 0; i < NF; i++) {
-                    const double d = pd[k][i];
-                    double v;
-                    if (MODE == TM_FWD) {
-                        v = d * pv[k][TWO ? 0 : i];
+                    for (int s = 0; s < W; s++) { const double nv = val - pa[k][s] * x[s]; val = (cd[s] != T_NONE) ? nv : val; }
+                    if (pok[k]) *(double *)((char *)aux + c * 8u) = val;
 #pragma unroll
-                        for (int s = 0; s < W; s++) { const double nv = v - d * pa[k][s] * ring[i][sl[s]]; v = (cd[s] != T_NONE) ? nv : v; }
-                    } else if (MODE == TM_BWD) {
-                        v = pv[k][TWO ? 0 : i];
+                    for (int s = 0; s < W; s++) val -= pb[k][TWO ? s : 0];
+                    val = val / d;
+                } else {
+                    val = pv[k];
 #pragma unroll
-                        for (int s = W - 1; s >= 0; s--) { const double nv = v - d * pa[k][s] * ring[i][sl[s]]; v = (cd[s] != T_NONE) ? nv : v; }
-                    } else {
-                        v = d;
-#pragma unroll
-                        for (int s = 0; s < W; s++) { const double nv = v - pa[k][s] * pb[k][TWO ? s : 0] / ring[i][sl[s]]; v = (cd[s] != T_NONE) ? nv : v; }
-                    }
-                    val[i] = v;
+                    for (int s = 0; s < W; s++) { const double nv = val - pa[k][s] * x[s]; val = (cd[s] != T_NONE) ? nv : val; }
+                    val = val / d;
                 }
-                if (pok[k]) {
-#pragma unroll
-                    for (int i = 0; i < NF; i++) {
-                        *(double *)((char *)m.w[i] + c * 8u) = (MODE == TM_RD) ? 1.0 / val[i] : val[i];
-                        ring[i][(c - gs) & (unsigned)(R - 1)] = val[i];
-                        if (cd[3] != T_NONE) t_st(&m.mail[i][ppb[k] + cd[3]], val[i]);
-                    }
-                }
+                if (pok[k]) { *(double *)((char *)w + c * 8u) = val; ring[(c - gs) & (unsigned)(T_RING - 1)] = val; }
+                if (pok[k] && cd[3] != T_NONE) t_st(&mail[ppb[k] + cd[3]], val);
             }
-            TM_FETCH(k, ee + PF, Rn);
-            t_barrier();
+            // ---- refill slot k with entry ee + PF
+            T_FETCH(k, ee + PF, Rn);
+            t_barrier();                                    // one barrier per level: ring and halo are visible to the next entry
         }
     }
-#undef TM_FETCH
+#undef T_FETCH
 }
 
+// out[i] = native[src[i]] (0 where a cell has fewer than T_W neighbours): coefficients in the kernel's cell-major layout
+__global__ void k_tile_gather(long n, const int *__restrict__ src, const double *__restrict__ native, double *__restrict__ out)
+{
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int q = src[i];
+        out[i] = (q >= 0) ? native[q] : 0.0;
+    }
+}
+// mailbox fill before a sweep (pair); it also zeroes the group ticket counter, so that the 32-bit counter never wraps and every
+// launch hands its groups out as ticket % G with ticket < 2 G (forward sweep 0..G-1, backward sweep G..2G-1)
+__global__ void k_tile_fill(long n, unsigned long long *p, unsigned long long v, unsigned int *ticket)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) ticket[0] = 0u;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
+}
 
-bool ffm_tile_multi_usable(const ffm_ldu *A) { return ffm_tile_usable(A); }
+static TileView tview(const ffm_ldu *A, const TileDir &d)
+{
+    TileView t; t.G = A->tile->G; t.grpCell = A->grpCell; t.grpEnt = d.grpEnt; t.extSrc = d.extSrc; t.rec = d.rec;
+    t.code = (const uint2 *)d.code; t.ticket = A->sweepTicket;
+    return t;
+}
+
+// gathered coefficients of one direction, refreshed when the matrix coefficients changed
+static int tile_coef(ffm_ldu *A, TileDir &d, bool upper, const double **out)
+{
+    const long n = (long)T_W * A->nOwned;
+    double *&buf = upper ? d.coefU : d.coefL;
+    unsigned long &ep = upper ? d.epochU : d.epochL;
+    if (!buf) { FFM_HIP(hipMalloc((void **)&buf, sizeof(double) * std::max<long>(n, 1))); ep = ~0ul; }
+    if (ep != A->offDiagEpoch) {
+        const int g = std::max(1, std::min(ffm_grid(n, 256), 8 * RED_BLOCKS));
+        hipLaunchKernelGGL(k_tile_gather, dim3(g), dim3(256), 0, A->ctx->stream, n, d.src, upper ? A->upper : A->lower, buf);
+        ep = A->offDiagEpoch;
+    }
+    *out = buf;
+    return FFM_OK;
+}
+
+static void tile_fill(ffm_ldu *A, double *p, long n)
+{
+    const int g = std::max(1, std::min(ffm_grid(n, 256), 8 * RED_BLOCKS));
+    hipLaunchKernelGGL(k_tile_fill, dim3(g), dim3(256), 0, A->ctx->stream, n, (unsigned long long *)p, T_SENT, A->sweepTicket);
+}
+
 // n systems in one sweep: up to four on the plan's own ring, five on the short one where the plan's ring neighbours are near enough
 bool ffm_tile_multi_fits(const ffm_ldu *A, int n)
 {
-    if (n < 2 || n > FFM_TILE_MAXSYS || !ffm_tile_multi_usable(A)) return false;
+    if (n < 1 || n > FFM_TILE_MAXSYS || !ffm_tile_usable(A)) return false;
     return n <= 4 || std::max(A->tile->f.reach, A->tile->b.reach) <= TM_RING5 - 2 * T_ENT;
 }
 extern "C" int ffm_ldu_tile_reach(const ffm_ldu *A, int *reach, int *limit, int *limit5)
@@ -892,54 +803,126 @@ extern "C" int ffm_ldu_tile_reach(const ffm_ldu *A, int *reach, int *limit, int 
     *reach = std::max(A->tile->f.reach, A->tile->b.reach); *limit = T_RINGD; *limit5 = TM_RING5 - 2 * T_ENT;
     return FFM_OK;
 }
-static int tile_multi_mail(ffm_ldu *A)
+// The mailboxes of n systems, filled with the sentinel for the next sweep (pair): system i's are (*mail) + i*nMail.  One system has
+// the plan's own (fwdOnly: only the forward direction's are filled); several have [FFM_TILE_MAXSYS][nMail] of their own
+static int tile_mail(ffm_ldu *A, int n, bool fwdOnly, double **mail)
 {
     ffm_tile_plan *T = A->tile;
-    if (!T->mailMulti) FFM_HIP(hipMalloc((void **)&T->mailMulti, sizeof(double) * (size_t)FFM_TILE_MAXSYS * (size_t)T->nMail));
+    if (n > 1 && !T->mailMulti) FFM_HIP(hipMalloc((void **)&T->mailMulti, sizeof(double) * (size_t)FFM_TILE_MAXSYS * (size_t)T->nMail));
+    *mail = (n == 1) ? T->mailAll : T->mailMulti;
+    tile_fill(A, *mail, (n == 1 && fwdOnly) ? (long)T->f.nPub + 1 : (long)n * T->nMail);
     return FFM_OK;
 }
-template <int MODE, int NF, int R = T_RING>
-static void tile_multi_launch(ffm_ldu *A, const TileDir &d, const double *ca, const double *cb, const double *const *dg, const double *const *r, double *const *w)
+// one sweep of direction d over NF systems (r: null where the mode has no right-hand side; r[0] null in a fused forward sweep: q = w)
+template <int MODE, int NF, int R = T_RING, bool FUSE = false>
+static void tile_launch(ffm_ldu *A, const TileDir &d, double *mail, const double *ca, const double *cb, const double *const *dg, const double *const *r,
+                        double *const *w, double *aux = nullptr, const double *scal = nullptr, double *partials = nullptr)
 {
     ffm_tile_plan *T = A->tile;
-    TileMulti<NF> m;
-    for (int i = 0; i < NF; i++) { m.dg[i] = dg[i]; m.r[i] = r ? r[i] : nullptr; m.w[i] = w[i]; m.mail[i] = T->mailMulti + (size_t)i * T->nMail + (d.mail - T->mailAll); }
-    hipLaunchKernelGGL((k_tile_m<MODE, NF, R>), dim3(T->G), dim3(T_THREADS + 64), 0, A->ctx->stream, tview(A, d), ca, cb, m);
+    TileSys<NF> m;
+    for (int i = 0; i < NF; i++) { m.dg[i] = dg[i]; m.r[i] = r ? r[i] : nullptr; m.w[i] = w[i]; m.mail[i] = mail + (size_t)i * T->nMail + (d.mail - T->mailAll); }
+    hipLaunchKernelGGL((k_tile<MODE, NF, R, FUSE>), dim3(T->G), dim3(T_THREADS + 64), 0, A->ctx->stream, tview(A, d), ca, cb, m, aux, scal, partials);
 }
-#define TILE_MULTI(MODE, n, ...) switch (n) { case 2: tile_multi_launch<MODE, 2>(__VA_ARGS__); break; case 3: tile_multi_launch<MODE, 3>(__VA_ARGS__); break; \
-                                             case 4: tile_multi_launch<MODE, 4>(__VA_ARGS__); break; \
-                                             default: tile_multi_launch<MODE, 5, TM_RING5>(__VA_ARGS__); break; }
-// DILU / DIC application (not transposed) of n = 2 .. FFM_TILE_MAXSYS systems with the matrix's off-diagonal coefficients and their
-// own reciprocal diagonals: w[i] = precondition(r[i]).
-int ffm_tile_precond_multi(ffm_ldu *A, int precond, int n, const double *const *rD, const double *const *r, double *const *w)
+#define TILE_SWEEP(MODE, n, ...) switch (n) { case 1: tile_launch<MODE, 1>(__VA_ARGS__); break; case 2: tile_launch<MODE, 2>(__VA_ARGS__); break; \
+                                             case 3: tile_launch<MODE, 3>(__VA_ARGS__); break; case 4: tile_launch<MODE, 4>(__VA_ARGS__); break; \
+                                             default: tile_launch<MODE, 5, TM_RING5>(__VA_ARGS__); break; }
+// DILU / DIC application of n = 1 .. FFM_TILE_MAXSYS systems with the matrix's off-diagonal coefficients and their own reciprocal
+// diagonals: w[i] = precondition(r[i])
+int ffm_tile_precond(ffm_ldu *A, int precond, bool transpose, int n, const double *const *rD, const double *const *r, double *const *w)
 {
     ffm_tile_plan *T = A->tile;
-    if (!ffm_tile_multi_fits(A, n)) return FFM_ERR_ARG;
-    const double *cf, *cb;
-    FFM_TRY(tile_coef(A, T->f, precond == FFM_DIC, &cf));
-    FFM_TRY(tile_coef(A, T->b, true, &cb));
-    FFM_TRY(tile_multi_mail(A));
-    tile_fill(A, T->mailMulti, (long)n * T->nMail);
-    TILE_MULTI(TM_FWD, n, A, T->f, cf, nullptr, rD, r, w);
-    TILE_MULTI(TM_BWD, n, A, T->b, cb, nullptr, rD, nullptr, w);
+    if (!ffm_tile_multi_fits(A, n)) { ffm_set_error("ffm_tile_precond: %d systems do not fit this matrix's tile plan", n); return FFM_ERR_ARG; }
+    // forward coefficient: DIC upper; DILU lower; DILU^T upper.  backward: DIC upper; DILU upper; DILU^T lower.
+    const bool fwdUpper = (precond == FFM_DIC) || transpose;
+    const bool bwdUpper = (precond == FFM_DIC) || !transpose;
+    const double *cf, *cb; double *mail;
+    FFM_TRY(tile_coef(A, T->f, fwdUpper, &cf));
+    FFM_TRY(tile_coef(A, T->b, bwdUpper, &cb));
+    FFM_TRY(tile_mail(A, n, false, &mail));
+    TILE_SWEEP(TM_FWD, n, A, T->f, mail, cf, nullptr, rD, r, w);
+    TILE_SWEEP(TM_BWD, n, A, T->b, mail, cb, nullptr, rD, nullptr, w);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
 // D[i] = 1/(diag[i] - sum upper*lower/D[i][l]) in face order for n systems
-int ffm_tile_calc_rD_multi(ffm_ldu *A, int n, const double *const *diag, double *const *D)
+int ffm_tile_calc_rD(ffm_ldu *A, int n, const double *const *diag, double *const *D)
 {
     ffm_tile_plan *T = A->tile;
-    if (!ffm_tile_multi_fits(A, n)) return FFM_ERR_ARG;
-    const double *cu, *cl;
+    if (!ffm_tile_multi_fits(A, n)) { ffm_set_error("ffm_tile_calc_rD: %d systems do not fit this matrix's tile plan", n); return FFM_ERR_ARG; }
+    const double *cu, *cl; double *mail;
     FFM_TRY(tile_coef(A, T->f, true, &cu));
     if (A->lower == A->upper) cl = cu; else FFM_TRY(tile_coef(A, T->f, false, &cl));
-    FFM_TRY(tile_multi_mail(A));
-    tile_fill(A, T->mailMulti, (long)n * T->nMail);
-    TILE_MULTI(TM_RD, n, A, T->f, cu, cl, diag, nullptr, D);
+    FFM_TRY(tile_mail(A, n, true, &mail));
+    TILE_SWEEP(TM_RD, n, A, T->f, mail, cu, cl, diag, nullptr, D);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
 
+__global__ void k_tile_sum_partials(int n, const double *__restrict__ partials, double *__restrict__ scal, int slot);
+// PCG with DIC on a tile plan: the two halves of the preconditioner application with the neighbouring vector
+// updates fused in (k_tile<.., FUSE>).  Forward: rA -= scal[S_ALPHA]*wA, scal[slot] = sum |rA| (local), wA = forward sweep of rA.
+// Backward: finishes wA, scal[slot] = sum wA*rA (local).
+bool ffm_tile_pcg_fusable(const ffm_ldu *A)
+{
+    const char *e = getenv("FFM_PCG_UNFUSED");
+    const bool off = e && atoi(e) != 0;
+    return !off && ffm_tile_usable(A) && A->tile->G <= 4 * RED_BLOCKS;
+}
+int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double *qA)
+{
+    ffm_tile_plan *T = A->tile;
+    hipStream_t s = A->ctx->stream;
+    const double *cf, *cb, *rD = A->rD; double *mail;
+    FFM_TRY(tile_coef(A, T->f, true, &cf));
+    FFM_TRY(tile_coef(A, T->b, true, &cb));
+    FFM_TRY(tile_mail(A, 1, false, &mail));
+    tile_launch<TM_FWD, 1, T_RING, true>(A, T->f, mail, cf, nullptr, &rD, &qA, &wA, rA, A->ctx->scal_d, A->ctx->partials_d);
+    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot)
+{
+    ffm_tile_plan *T = A->tile;
+    hipStream_t s = A->ctx->stream;
+    const double *cb, *rD = A->rD;
+    FFM_TRY(tile_coef(A, T->b, true, &cb));
+    tile_launch<TM_BWD, 1, T_RING, true>(A, T->b, T->mailAll, cb, nullptr, &rD, &rA, &wA, nullptr, A->ctx->scal_d, A->ctx->partials_d);      // (mailboxes: filled by the forward half)
+    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// upper*psi_old of the (owned) upper neighbours of every cell, slot by slot; +0.0 where a cell has fewer than three
+__global__ void k_tile_gs_products(long n3, const int *__restrict__ nbrCell, const double *__restrict__ coef, const double *__restrict__ psi,
+                                   double *__restrict__ out)
+{
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n3; i += (long)gridDim.x * blockDim.x) {
+        const int nb = nbrCell[i];
+        out[i] = (nb >= 0) ? coef[i] * psi[nb] : 0.0;
+    }
+}
+
+// One GaussSeidelSmoother / symGaussSeidelSmoother sweep (forward rows, then reverse rows when sym): psi in place, bP = bPrime
+// (source with the lagged interface terms), bSave = scratch [nCells].  prod = scratch [3*nCells].
+int ffm_tile_gs(ffm_ldu *A, bool sym, double *psi, const double *bP, double *bSave, double *prod)
+{
+    ffm_tile_plan *T = A->tile;
+    hipStream_t s = A->ctx->stream;
+    const double *cl, *cu; double *mail;
+    FFM_TRY(tile_coef(A, T->f, A->lower == A->upper, &cl));        // lower coefficients, lower-neighbour layout
+    FFM_TRY(tile_coef(A, T->b, true, &cu));                         // upper coefficients, upper-neighbour layout
+    const long n3 = (long)T_W * A->nOwned;
+    hipLaunchKernelGGL(k_tile_gs_products, dim3(std::max(1, std::min(ffm_grid(n3, 256), 8 * RED_BLOCKS))), dim3(256), 0, s, n3,
+                       (const int *)T->upNbrCell, cu, (const double *)psi, prod);
+    FFM_TRY(tile_mail(A, 1, false, &mail));
+    hipLaunchKernelGGL(k_tile_gs<TM_GSF>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->f), T->f.mail, cl, (const double *)prod, (const double *)A->diag, bP, psi, bSave);
+    if (sym)
+        hipLaunchKernelGGL(k_tile_gs<TM_GSB>, dim3(T->G), dim3(T_THREADS + 64), 0, s, tview(A, T->b), T->b.mail, cu, (const double *)nullptr, (const double *)A->diag,
+                           (const double *)bSave, psi, (double *)nullptr);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
 
 // ------------------------------------------------------------------ tiled Amul: kernels ---
 struct AmulView {
@@ -1219,8 +1202,8 @@ extern "C" int ffm_debug_set_sweep_ticket(ffm_ldu *A, unsigned int value)
 extern "C" int ffm_debug_tile_occupancy(int *out3)
 {
     if (!out3) return FFM_ERR_ARG;
-    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[0], k_tile<TM_FWD>, T_THREADS + 64, 0));
-    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[1], k_tile<TM_BWD>, T_THREADS + 64, 0));
+    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[0], (k_tile<TM_FWD, 1>), T_THREADS + 64, 0));
+    FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[1], (k_tile<TM_BWD, 1>), T_THREADS + 64, 0));
     FFM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out3[2], k_tile_amul<true>, T_THREADS + 64, 0));
     return FFM_OK;
 }

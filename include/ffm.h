@@ -250,7 +250,7 @@ int ffm_solve(ffm_ldu *ldu, int solver, int precond, double tolerance,
  * its own iteration count and residuals in out[i] -- but for PBiCGStab with DILU / DIC on a tiled matrix in the library's cell order
  * the systems (at most 5 at a time; 5 only where ffm_ldu_tile_reach reports reach <= limit5) advance in lock step and the preconditioner
  * sweeps and calcReciprocalD of those still iterating are one sweep each (coefficients and addressing read once).  Any other selection:
- * one solve after the other.
+ * one solve after the other.  nSys = 1 is that one solve (the same routine: a single lane).
  * diag_d[i] [cells], upper_d / lower_d [native faces; lower_d NULL or == upper_d: symmetric], psi_d[i] in/out, source_d[i].
  * The matrix is left bound to the caller's arrays as by ffm_ldu_bind_coeffs_native_d.                                         */
 int ffm_solve_multi_d(ffm_ldu *ldu, int nSys, int solver, int precond, double tolerance, double relTol, int minIter, int maxIter,

@@ -1,6 +1,6 @@
 """Five lock-step systems (ffm_solve_multi_d with nSys = 5: the four species and h of the plume step) against five ffm_solve_d.
 
-Five LDS rings of the plan's length do not fit a workgroup, so k_tile_m<MODE,5> runs on a ring of 2048 doubles and derives its slots from
+Five LDS rings of the plan's length do not fit a workgroup, so k_tile<MODE,5,2048> runs on a ring of 2048 doubles and derives its slots from
 the plan's codes; it serves plans whose ring neighbours lie within 2048 - 512 cells (ffm_ldu_tile_reach).  Checked here, all bitwise:
 
 * solutions, residuals and iteration counts of five lanes equal those of five single solves, on boxes whose sizes are and are not

@@ -1,7 +1,7 @@
 """The set-up of a solve without its separate vector passes (csrc/ffm_solve.hip: k_prologue; csrc/ffm_tile.hip: the tiled
 calcReciprocalD stores 1/D itself).
 
-(a) calcReciprocalD through the tiled sweeps -- one system (k_tile<TM_RD>) and several systems in one sweep (k_tile_m<TM_RD, NF>) --
+(a) calcReciprocalD through the tiled sweeps -- one system (k_tile<TM_RD, 1>) and several systems in one sweep (k_tile<TM_RD, NF>) --
     gives rD BITWISE equal to the reciprocal of the oracle's face loop (oracle/ffo_precond.c): one system on the meshes of
     test_ldu_gpu.py; several systems on boxes in the library's own cell order, which the lock-step form requires (its `hex_big` box
     among them).
