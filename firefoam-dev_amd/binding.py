@@ -125,6 +125,8 @@ def lib():
                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(Perf)], C.c_int),
         "ffm_ldu_unbind_coeffs": ([vp], C.c_int),
         "ffm_ldu_offdiag_epoch": ([vp], C.c_ulong),
+        "ffm_ldu_tile_coef_read": ([vp, C.c_int, hp], C.c_int),
+        "ffm_ldu_tile_gathers": ([vp], C.c_long),
         "ffm_debug_pool_poison": ([vp, C.c_int], C.c_int),
         "ffm_bench_spmv": ([vp, dp, dp, C.c_int, hp], C.c_int),
         "ffm_bench_precond": ([vp, C.c_int, dp, dp, C.c_int, hp], C.c_int),
@@ -211,6 +213,10 @@ def lib():
         "ffm_fvm_scalar_transport_multi": ([vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, dp, dp, dp, dp, dp, dp]
                                            + [C.POINTER(C.c_void_p)] * 16, C.c_int),
         "ffm_fvm_scalar_transport_multi_w": ([vp, C.c_int, dp, C.c_double, dp, dp, dp, dp, dp, dp] + [C.POINTER(C.c_void_p)] * 12, C.c_int),
+        "ffm_fvm_scalar_transport_multi_ws": ([vp, C.c_int, dp, C.c_double, dp, dp, dp, dp, dp, dp] + [C.POINTER(C.c_void_p)] * 5 + [hp]
+                                              + [C.POINTER(C.c_void_p)] * 7, C.c_int),
+        "ffm_fvm_scalar_transport_multi_ws_direct": ([vp, C.c_int, dp, C.c_double, dp, dp, dp, dp, dp, dp] + [C.POINTER(C.c_void_p)] * 5 + [hp]
+                                                     + [C.POINTER(C.c_void_p)] * 7, C.c_int),
         "ffm_fv_multivariate_weights": ([vp, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double, dp] + [C.POINTER(C.c_void_p)] * 4 + [dp], C.c_int),
         "ffm_fvm_lust_source3": ([vp, C.c_double, dp, dp] + [C.POINTER(C.c_void_p)] * 5, C.c_int),
         "ffm_pc_phig": ([vp, dp, dp, dp, dp], C.c_int),
@@ -221,11 +227,13 @@ def lib():
         "ffm_pc_finish": ([vp, C.c_double, C.c_double] + [dp] * 9 + [C.POINTER(vp)] + [dp] * 4 + [C.POINTER(vp)] + [dp] * 4, C.c_int),
         "ffm_ue_buoyancy_source3": ([vp, dp, dp, dp, dp, C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)], C.c_int),
         "ffm_fvm_transport_scheme": ([vp, C.c_double, dp, dp, C.c_int, dp, C.c_int, dp, dp, dp], C.c_int),
+        "ffm_fvm_transport_scheme_direct": ([vp, C.c_double, dp, dp, C.c_int, dp, C.c_int, dp, dp, dp], C.c_int),
         "ffm_fvc_div_dev2T_gradU": ([vp, C.POINTER(vp), dp, dp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)], C.c_int),
         "ffm_les_keqn_G": ([vp, C.POINTER(vp), dp, dp], C.c_int),
         "ffm_fvm_HbyA3": ([vp, dp, dp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(vp)], C.c_int),
         "ffm_fvc_flux_rho": ([vp, dp, dp, dp, dp, dp], C.c_int),
         "ffm_fvm_pressure_eqn": ([vp, C.c_double] + [dp] * 6 + [C.c_double] + [dp] * 9, C.c_int),
+        "ffm_fvm_pressure_eqn_direct": ([vp, C.c_double] + [dp] * 6 + [C.c_double] + [dp] * 9, C.c_int),
         "ffm_fvc_ddt_corr": ([vp, C.c_double] + [dp] * 6, C.c_int),
         "ffm_fvc_rho_eqn": ([vp, C.c_double] + [dp] * 4, C.c_int),
         "ffm_fvc_div_phiK_terms": ([vp, C.c_int] + [C.c_double] * 4 + [dp] * 14, C.c_int),
@@ -647,6 +655,18 @@ class lduMatrix:
         _check(lib().ffm_ldu_unbind_coeffs(self.h), "ffm_ldu_unbind_coeffs")
         self._bound = None
         return self
+
+    def tile_coef(self, which):
+        """one of the tiled sweeps' coefficient arrays, made current first (ffm_ldu_tile_coef_read): which = 0 forward upper,
+        1 forward lower, 2 backward upper, 3 backward lower; float64 [3*nOwned]"""
+        self.ctx._ready()
+        out = np.empty(3 * self.nOwned, np.float64)
+        _check(lib().ffm_ldu_tile_coef_read(self.h, which, _hp(out)), "ffm_ldu_tile_coef_read")
+        return out
+
+    def tile_gathers(self):
+        """gather passes this matrix has launched to fill those arrays (ffm_ldu_tile_gathers)"""
+        return int(lib().ffm_ldu_tile_gathers(self.h))
 
     @property
     def offdiag_epoch(self):

@@ -152,7 +152,8 @@ int ffm_read_scalars(ffm_ctx *c)
 
 // ------------------------------------------------------------- reductions ---
 // Stage 1: RED_BLOCKS blocks, grid-stride, per-block partial in fixed order.
-// Stage 2: one block sums the partials in fixed order.  No atomics anywhere.
+// Stage 2: one block sums the partials in fixed order.  No atomics anywhere.  A solver's scalar operation that starts from the sum
+// rides on stage 2 (ffm_scal_op): thread 0 runs it after storing the sum.
 enum { R_SUM = 0, R_DOT, R_SUMMAG, R_SUMSQR, R_MIN, R_MAX };
 
 template <int OP>
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce1(long n, const double *_
 
 template <int OP>
 __global__ __launch_bounds__(1024) void k_reduce2(int nPartials, const double *__restrict__ partials,
-                                                  double *__restrict__ scal, int slot)
+                                                  double *__restrict__ scal, int slot, ffm_scal_op t)
 {
     __shared__ double sm[16];
     double acc = (OP == R_MIN) ? 1.79769313486231570e+308 : (OP == R_MAX) ? -1.79769313486231570e+308 : 0.0;
@@ -195,26 +196,26 @@ __global__ __launch_bounds__(1024) void k_reduce2(int nPartials, const double *_
     if (OP == R_MIN) r = block_min(acc, sm);
     else if (OP == R_MAX) r = block_max(acc, sm);
     else r = block_sum(acc, sm);
-    if (threadIdx.x == 0) scal[slot] = r;
+    if (threadIdx.x == 0) { scal[slot] = r; run_scal_op(scal, t); }
 }
 
 template <int OP>
-static int reduce_to_slot(ffm_ctx *c, const double *x, const double *y, long n, int slot)
+static int reduce_to_slot(ffm_ctx *c, const double *x, const double *y, long n, int slot, const ffm_scal_op &t = ffm_scal_op())
 {
     int nb = (int)((n + RED_THREADS - 1) / RED_THREADS);
     if (nb > RED_BLOCKS) nb = RED_BLOCKS;
     if (nb < 1) nb = 1;
     hipLaunchKernelGGL(k_reduce1<OP>, dim3(nb), dim3(RED_THREADS), 0, c->stream, n, x, y, c->partials_d);
     constexpr int OP2 = (OP == R_MIN) ? R_MIN : (OP == R_MAX) ? R_MAX : R_SUM;
-    hipLaunchKernelGGL(k_reduce2<OP2>, dim3(1), dim3(1024), 0, c->stream, nb, c->partials_d, c->scal_d, slot);
+    hipLaunchKernelGGL(k_reduce2<OP2>, dim3(1), dim3(1024), 0, c->stream, nb, c->partials_d, c->scal_d, slot, t);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
 
-int ffm_k_dot(ffm_ctx *c, const double *x, const double *y, long n, int slot) { return reduce_to_slot<R_DOT>(c, x, y, n, slot); }
-int ffm_k_summag(ffm_ctx *c, const double *x, long n, int slot) { return reduce_to_slot<R_SUMMAG>(c, x, nullptr, n, slot); }
-int ffm_k_sum(ffm_ctx *c, const double *x, long n, int slot) { return reduce_to_slot<R_SUM>(c, x, nullptr, n, slot); }
-int ffm_k_sumsqr(ffm_ctx *c, const double *x, long n, int slot) { return reduce_to_slot<R_SUMSQR>(c, x, nullptr, n, slot); }
+int ffm_k_dot(ffm_ctx *c, const double *x, const double *y, long n, int slot, const ffm_scal_op &t) { return reduce_to_slot<R_DOT>(c, x, y, n, slot, t); }
+int ffm_k_summag(ffm_ctx *c, const double *x, long n, int slot, const ffm_scal_op &t) { return reduce_to_slot<R_SUMMAG>(c, x, nullptr, n, slot, t); }
+int ffm_k_sum(ffm_ctx *c, const double *x, long n, int slot, const ffm_scal_op &t) { return reduce_to_slot<R_SUM>(c, x, nullptr, n, slot, t); }
+int ffm_k_sumsqr(ffm_ctx *c, const double *x, long n, int slot, const ffm_scal_op &t) { return reduce_to_slot<R_SUMSQR>(c, x, nullptr, n, slot, t); }
 
 template <int OP>
 static int reduce_public(ffm_ctx *c, const double *x, const double *y, long n, double *out)

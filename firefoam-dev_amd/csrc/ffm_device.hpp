@@ -73,6 +73,62 @@ __device__ __forceinline__ double block_max(double v, double *sm)
     return r;
 }
 
+// --------------------------------------------------------------- scalar ops ---
+// The solvers' scalar operations on the device scalar block (ffm_solve.hip).  One thread runs one: k_scalar_op as a launch of its
+// own, or thread 0 of the one-workgroup launch that has just stored the sum the operation starts from (run_scal_op).
+enum {
+    OP_XREF = 1, OP_NORMF, OP_RES_INIT, OP_RES, OP_PCG_BETA, OP_PCG_ALPHA,
+    OP_BS_RHO, OP_BS_ALPHA, OP_BS_OMEGA, OP_BICG_BETA, OP_BICG_ALPHA, OP_RESET
+};
+
+#define VSMALL_ 1e-300
+
+// in: the slot the operation takes its sum from (the prologue kernel leaves three sums in S_TMP0..S_TMP2).  No __restrict__: the
+// launches that sum partials store into s just before.
+__device__ __forceinline__ void scalar_op_body(double *s, int op, double arg, int iter, int in)
+{
+    switch (op) {
+    case OP_RESET:
+        s[S_SING] = 0.0; s[S_WARA] = 1e+20; s[S_WARA_OLD] = 1e+20; s[S_RA0RA] = 0.0; s[S_ALPHA] = 0.0; s[S_OMEGA] = 0.0;
+        s[S_BETA] = 0.0;
+        break;
+    case OP_XREF: s[S_XREF] = s[S_TMP0] / arg; break;                    // gAverage(psi)
+    case OP_NORMF: s[S_NORMF] = s[S_TMP0] + 1e-20; break;                // + solverPerformance::small_
+    case OP_RES_INIT: s[S_RES] = s[in] / s[S_NORMF]; s[S_RES0] = s[S_RES]; break;
+    case OP_RES: if (s[S_SING] == 0.0) s[S_RES] = s[S_TMP0] / s[S_NORMF]; break;
+    case OP_PCG_BETA: {                                                  // wArAold = wArA; wArA = (wA,rA)
+        const double old = s[S_WARA], nw = s[S_TMP0];
+        s[S_WARA_OLD] = old; s[S_WARA] = nw; s[S_BETA] = nw / old;
+        break; }
+    case OP_PCG_ALPHA: case OP_BICG_ALPHA: {                             // wApA; checkSingularity(|wApA|/normFactor)
+        const double wApA = s[S_TMP0];
+        s[S_WAPA] = wApA;
+        if (fabs(wApA) / s[S_NORMF] > VSMALL_) { s[S_ALPHA] = s[S_WARA] / wApA; }
+        else { s[S_SING] = 1.0; s[S_ALPHA] = 0.0; }
+        break; }
+    case OP_BS_RHO: {                                                    // rA0rAold = rA0rA; rA0rA = (rA0,rA)
+        const double old = s[S_RA0RA], nw = s[in];
+        s[S_RA0RA_OLD] = old; s[S_RA0RA] = nw;
+        if (!(fabs(nw) > VSMALL_)) { s[S_SING] = 1.0; break; }
+        if (iter > 0) {
+            if (!(fabs(s[S_OMEGA]) > VSMALL_)) { s[S_SING] = 1.0; break; }
+            s[S_BETA] = (nw / old) * (s[S_ALPHA] / s[S_OMEGA]);
+        }
+        break; }
+    case OP_BS_ALPHA: if (s[S_SING] == 0.0) { s[S_RA0AYA] = s[S_TMP0]; s[S_ALPHA] = s[S_RA0RA] / s[S_TMP0]; } break;
+    case OP_BS_OMEGA: if (s[S_SING] == 0.0) { s[S_TATA] = s[S_TMP0]; s[S_TASA] = s[S_TMP1]; s[S_OMEGA] = s[S_TMP1] / s[S_TMP0]; } break;
+    case OP_BICG_BETA: {
+        const double old = s[S_WARA], nw = s[S_TMP0];
+        s[S_WARA_OLD] = old; s[S_WARA] = nw; s[S_BETA] = nw / old;
+        break; }
+    }
+}
+// the tail of a launch that sums partials into the scalar block: called by the thread that stored the sum(s), after the store
+__device__ __forceinline__ void run_scal_op(double *scal, const ffm_scal_op &t)
+{
+    if (t.fused) scalar_op_body(scal, t.op, t.arg, t.iter, t.in);
+}
+
 // ------------------------------------------------------ sliced owner-ELL view ---
 // Passed by value to every kernel that walks matrix rows (layout: ffm_internal.hpp).
 struct LduView {
@@ -133,6 +189,22 @@ __device__ __forceinline__ void load_upper(const LduView &v, int c, RowEnt<W> &R
         R.nb[s] = R.on[s] ? n : c;
         R.f[s] = R.on[s] ? idx : 0;
     }
+}
+
+// The tiled sweeps read a matrix's off-diagonal coefficients as cell-major triples (ffm_tile.hip: TileDir::coefU / coefL): slot k of
+// cell c holds the k-th PRESENT entry of the row, in row order, absent slots 0.0 (k_tile_gather's layout, byte for byte).  A kernel
+// that assembles the matrix has a row's values in registers and stores the triple itself: v[s] is the coefficient of row slot s
+// (anything where !on[s]).  Selects, no indexed temporaries; one 24-byte record per lane, consecutive lanes consecutive records.
+struct TileCoefOut { double *fU, *fL, *bU; };       // forward upper / lower (fL null: symmetric), backward upper
+__device__ __forceinline__ void store_triple(double *__restrict__ out, int c, const bool (&on)[FFM_TILE_W], const double (&v)[FFM_TILE_W])
+{
+    static_assert(FFM_TILE_W == 3, "three slots per direction");
+    const double t12 = on[1] ? v[1] : (on[2] ? v[2] : 0.0);                    // first present of slots 1, 2
+    const double k0 = on[0] ? v[0] : t12;
+    const double k1 = on[0] ? t12 : ((on[1] && on[2]) ? v[2] : 0.0);
+    const double k2 = (on[0] && on[1] && on[2]) ? v[2] : 0.0;
+    double *o = out + 3 * (size_t)c;
+    o[0] = k0; o[1] = k1; o[2] = k2;
 }
 
 // (W = 3: hexahedral meshes -- at most 3 lower and 3 upper neighbours per cell -- get their own instantiation: a quarter fewer

@@ -103,6 +103,7 @@ struct ScalarEqns {
     const double *wGiven;                                                // GIVENW: the face weights (a multivariate scheme's common ones)
     int nOffDiag;                                                        // GIVENW: fields 0 .. nOffDiag-1 write their off-diagonals (with common weights and one
                                                                          // diffusivity every field's are the same: the caller shares field 0's, or an earlier pass')
+    TileCoefOut tile;                                                    // TILE (GIVENW, nOffDiag == 1): the sweeps' layout of field 0's off-diagonals
 };
 
 // Occupancy: the fused four-field kernel is bound by the latency of its neighbour gathers; capped at 128 VGPRs (4 waves per SIMD,
@@ -110,9 +111,12 @@ struct ScalarEqns {
 // waves spill too much (25 / 27 ms), and the one-field kernel is better left alone (7.97 vs 8.35 ms).  Measured r02u.
 // GIVENW: the face weights come from a.wGiven (a multivariateSelection scheme's common weights) instead of one limiter per field: no
 // gradient / neighbour-value gathers at all
-template <int W, int NF, bool GIVENW = false, bool SUSCALED = false>
+// TILE (GIVENW only): the off-diagonals, which no field enters, also as the tile plan's triples -- those of the lower faces by the owner's
+// expressions on the same face operands (ffm_device.hpp: store_triple)
+template <int W, int NF, bool GIVENW = false, bool SUSCALED = false, bool TILE = false>
 __global__ __launch_bounds__(256, ((NF > 1 && !GIVENW) ? 4 : 1)) void k_scalar_eqns(MeshView q, ScalarEqns a)
 {
+    static_assert(!TILE || GIVENW, "the triples are written from the common weights");
     CELL_SCHED(ci, q) {
         const int c = (int)ci;
         RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
@@ -129,6 +133,18 @@ __global__ __launch_bounds__(256, ((NF > 1 && !GIVENW) ? 4 : 1)) void k_scalar_e
                 dlx[s] = cx - a.Cx[L.nb[s]]; dly[s] = cy - a.Cy[L.nb[s]]; dlz[s] = cz - a.Cz[L.nb[s]];
                 dux[s] = a.Cx[U.nb[s]] - cx; duy[s] = a.Cy[U.nb[s]] - cy; duz[s] = a.Cz[U.nb[s]] - cz;
             } else { dlx[s] = dly[s] = dlz[s] = dux[s] = duy[s] = duz[s] = 0.0; }
+        }
+        if constexpr (TILE) {
+            double lU[W], lL[W], uU[W];
+#pragma unroll
+            for (int s = 0; s < W; s++) {
+                double lo = -wl[s] * fl[s], up = lo + fl[s];
+                lo = lo - gl[s]; up = up - gl[s];
+                lU[s] = up; lL[s] = lo;
+                lo = -wu[s] * fu[s]; up = lo + fu[s];
+                uU[s] = up - gu[s];
+            }
+            store_triple(a.tile.fU, c, L.on, lU); store_triple(a.tile.fL, c, L.on, lL); store_triple(a.tile.bU, c, U.on, uU);
         }
         const double V = q.V[c], rhoc = a.rho[c], rho0c = a.rho0[c];
         const int j = q.cellB[c];
@@ -591,6 +607,7 @@ extern "C" int ffm_fvm_scalar_transport_multi(ffm_mesh *m, int nf, int scheme, d
     a.rho = rho; a.rho0 = rho0; a.phi = phi_f; a.phib = phi_b; a.gamma = gamma_f; a.gammab = gamma_b;
     a.Cx = m->C[0]; a.Cy = m->C[1]; a.Cz = m->C[2]; a.bMagSf = m->bMagSf; a.bDelta = m->bDelta;
     a.rdt = rDeltaT; a.twoByk = 2.0 / std::max(k, 1e-15); a.lo = lo; a.hi = hi; a.scheme = scheme; a.wGiven = nullptr; a.nOffDiag = nf;
+    m->A->directPending = false;        // (as in scalar_transport_multi_ws)
 #define SE(NF) FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_scalar_eqns<W, NF>), mview(m), a))
     switch (nf) { case 1: SE(1); break; case 2: SE(2); break; case 3: SE(3); break; default: SE(4); break; }
 #undef SE
@@ -622,12 +639,13 @@ extern "C" int ffm_fv_multivariate_weights(ffm_mesh *m, int nf, const int *schem
 // ddt(rho, vf_i) + div(phi, vf_i) [weights w_f] - laplacian(gamma, vf_i) == su_i ... for nf fields in one pass
 // suFactor (nullable): the explicit source of field i is suFactor[i]*su[i], the product formed where it is used -- the species of
 // solver/YEEqn.H share one reaction rate and differ in the stoichiometric factor only
-extern "C" int ffm_fvm_scalar_transport_multi_ws(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
-                                                 const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
-                                                 const double *const *vf0, const double *const *f, const double *const *ref,
-                                                 const double *const *refGrad, const double *const *su, const double *suFactor,
-                                                 const double *const *su2, const double *const *sp, const double *const *expl3,
-                                                 double *const *diag, double *const *upper, double *const *lower, double *const *source)
+// direct: field 0's off-diagonals -- the only ones written -- go to the matrix's tile plan as well (ffm_tile_coef_direct)
+static int scalar_transport_multi_ws(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
+                                     const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
+                                     const double *const *vf0, const double *const *f, const double *const *ref,
+                                     const double *const *refGrad, const double *const *su, const double *suFactor,
+                                     const double *const *su2, const double *const *sp, const double *const *expl3,
+                                     double *const *diag, double *const *upper, double *const *lower, double *const *source, bool direct)
 {
     CHECK_M(m);
     if (suFactor && !su) return FFM_ERR_ARG;
@@ -651,6 +669,21 @@ extern "C" int ffm_fvm_scalar_transport_multi_ws(ffm_mesh *m, int nf, const doub
     // off-diagonals: every field with non-null upper AND lower writes its own; the fields after the first null pair share what was written
     a.nOffDiag = 0;
     for (int i = 0; i < nf; i++) { if (upper[i] && lower[i]) { if (a.nOffDiag != i) return FFM_ERR_ARG; a.nOffDiag = i + 1; } else if ((upper[i] == nullptr) != (lower[i] == nullptr)) return FFM_ERR_ARG; }
+    a.tile = {nullptr, nullptr, nullptr};
+    m->A->directPending = false;        // these arrays are being rewritten: a declaration of an earlier direct write no longer holds
+    if (direct) {
+        // (the forms the time step launches: the four species, or the species and h, with scaled sources)
+        if (a.nOffDiag != 1 || upper[0] == lower[0] || !suFactor || nf < 4) {
+            ffm_set_error("direct sweep-layout coefficients: four or five fields with scaled sources and one shared, asymmetric set of off-diagonals");
+            return FFM_ERR_UNSUPPORTED;
+        }
+        FFM_TRY(ffm_tile_coef_direct(m->A, true, &a.tile.fU, &a.tile.fL, &a.tile.bU));
+        if (nf == 4) LAUNCH_CELLS((k_scalar_eqns<FFM_TILE_W, 4, true, true, true>), mview(m), a);
+        else LAUNCH_CELLS((k_scalar_eqns<FFM_TILE_W, 5, true, true, true>), mview(m), a);
+        FFM_HIP(hipGetLastError());
+        ffm_tile_coef_written(m->A, upper[0], lower[0]);
+        return FFM_OK;
+    }
 #define SEW(NF) do { if (suFactor) FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_scalar_eqns<W, NF, true, true>), mview(m), a)); \
                      else FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_scalar_eqns<W, NF, true, false>), mview(m), a)); } while (0)
     switch (nf) {
@@ -663,6 +696,29 @@ extern "C" int ffm_fvm_scalar_transport_multi_ws(ffm_mesh *m, int nf, const doub
 #undef SEW
     FFM_HIP(hipGetLastError());
     return FFM_OK;
+}
+extern "C" int ffm_fvm_scalar_transport_multi_ws(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
+                                                 const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
+                                                 const double *const *vf0, const double *const *f, const double *const *ref,
+                                                 const double *const *refGrad, const double *const *su, const double *suFactor,
+                                                 const double *const *su2, const double *const *sp, const double *const *expl3,
+                                                 double *const *diag, double *const *upper, double *const *lower, double *const *source)
+{
+    return scalar_transport_multi_ws(m, nf, w_f, rDeltaT, rho, rho0, phi_f, phi_b, gamma_f, gamma_b, vf0, f, ref, refGrad, su, suFactor, su2, sp, expl3,
+                                     diag, upper, lower, source, false);
+}
+// The same with one shared set of off-diagonals (upper[0] / lower[0] alone non-null), whose sweep layout goes to the matrix's tile plan
+// from this launch: binding exactly upper[0] / lower[0] next gathers nothing.  FFM_ERR_UNSUPPORTED with nothing written where the plan
+// cannot take them (ffm_tile_coef_direct) or the fields do not share their off-diagonals: the caller then calls the form above.
+extern "C" int ffm_fvm_scalar_transport_multi_ws_direct(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
+                                                        const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
+                                                        const double *const *vf0, const double *const *f, const double *const *ref,
+                                                        const double *const *refGrad, const double *const *su, const double *suFactor,
+                                                        const double *const *su2, const double *const *sp, const double *const *expl3,
+                                                        double *const *diag, double *const *upper, double *const *lower, double *const *source)
+{
+    return scalar_transport_multi_ws(m, nf, w_f, rDeltaT, rho, rho0, phi_f, phi_b, gamma_f, gamma_b, vf0, f, ref, refGrad, su, suFactor, su2, sp, expl3,
+                                     diag, upper, lower, source, true);
 }
 extern "C" int ffm_fvm_scalar_transport_multi_w(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
                                                 const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
@@ -1116,16 +1172,25 @@ struct PEqn {
     const double *psi, *psi0, *p0, *rho, *rho0, *gh, *gamma, *phiHbyA, *phiHbyAb, *ic, *bc;
     double *upper, *lower, *diag, *src;
     double rdt, pRef;
+    TileCoefOut tile;               // TILE: the sweeps' layout of the same coefficients (ffm_device.hpp: store_triple)
 };
-template <int W>
-__global__ __launch_bounds__(256) void k_p_rgh_eqn(MeshView q, PEqn a)
+// TILE: the cell also stores upper of its lower faces -- the owner's expression on the same face operands, hence the owner's bits (the
+// rule of the passes that form a face field where it is used, below) -- and of its own, as the tile plan's triples
+// (TILE: the extra pointers and slot masks would cost the eighth wave per SIMD in scalar registers; the bound keeps it)
+template <int W, bool TILE = false>
+__global__ __launch_bounds__(256, (TILE ? 8 : 1)) void k_p_rgh_eqn(MeshView q, PEqn a)
 {
     CELL_SCHED(ci, q) {
         const int c = (int)ci;
         RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
         double dLap = 0.0, acc = 0.0;
+        double vl[TILE ? W : 1] = {}, vu[TILE ? W : 1] = {};      // TILE: upper of the lower and of the own faces, kept from the loads below
 #pragma unroll
-        for (int s = 0; s < W; s++) if (L.on[s]) { const int e = L.f[s]; dLap -= a.gamma[e] * q.magSf[e] * q.delta[e]; }
+        for (int s = 0; s < W; s++) if (L.on[s]) {
+            const int e = L.f[s];
+            if constexpr (TILE) { const double g = a.gamma[e] * q.magSf[e] * q.delta[e]; dLap -= g; vl[s] = -g; }
+            else dLap -= a.gamma[e] * q.magSf[e] * q.delta[e];
+        }
 #pragma unroll
         for (int s = 0; s < W; s++) if (U.on[s]) {
             const int e = U.f[s];
@@ -1133,6 +1198,11 @@ __global__ __launch_bounds__(256) void k_p_rgh_eqn(MeshView q, PEqn a)
             dLap -= g;
             a.upper[e] = -g;
             if (a.lower) a.lower[e] = -g;
+            if constexpr (TILE) vu[s] = -g;
+        }
+        if constexpr (TILE) {
+            store_triple(a.tile.fU, c, L.on, vl); store_triple(a.tile.bU, c, U.on, vu);
+            if (a.tile.fL) store_triple(a.tile.fL, c, L.on, vl);
         }
 #pragma unroll
         for (int s = 0; s < W; s++) if (L.on[s]) acc = acc - a.phiHbyA[L.f[s]];
@@ -1161,9 +1231,28 @@ extern "C" int ffm_fvm_pressure_eqn(ffm_mesh *m, double rDeltaT, const double *p
     // lower == NULL: the matrix is symmetric (lower = upper) and the caller reads `upper` in both roles
     if (!psi || !psi0 || !p0 || !rho || !rho0 || !gh || !gamma_f || !phiHbyA_f || !upper || !diagOut || !sourceOut ||
         (m->B && (!phiHbyA_b || !ic || !bc))) return FFM_ERR_ARG;
-    PEqn a{psi, psi0, p0, rho, rho0, gh, gamma_f, phiHbyA_f, phiHbyA_b, ic, bc, upper, lower, diagOut, sourceOut, rDeltaT, pRef};
+    PEqn a{psi, psi0, p0, rho, rho0, gh, gamma_f, phiHbyA_f, phiHbyA_b, ic, bc, upper, lower, diagOut, sourceOut, rDeltaT, pRef, {nullptr, nullptr, nullptr}};
+    m->A->directPending = false;        // (as in scalar_transport_multi_ws)
     FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_p_rgh_eqn<W>, mview(m), a));
     FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+// The same, and the matrix's tile plan gets the sweep layout of upper (and lower) from this launch: binding exactly `upper` / `lower`
+// next (ffm_ldu_bind_coeffs_native_d, ffm_solve_multi_d) gathers nothing.  FFM_ERR_UNSUPPORTED with nothing written where the plan
+// cannot take them (ffm_tile_coef_direct): the caller then calls ffm_fvm_pressure_eqn.
+extern "C" int ffm_fvm_pressure_eqn_direct(ffm_mesh *m, double rDeltaT, const double *psi, const double *psi0, const double *p0, const double *rho,
+                                           const double *rho0, const double *gh, double pRef, const double *gamma_f, const double *phiHbyA_f,
+                                           const double *phiHbyA_b, const double *ic, const double *bc, double *upper, double *lower, double *diagOut,
+                                           double *sourceOut)
+{
+    CHECK_M(m);
+    if (!psi || !psi0 || !p0 || !rho || !rho0 || !gh || !gamma_f || !phiHbyA_f || !upper || !diagOut || !sourceOut ||
+        (m->B && (!phiHbyA_b || !ic || !bc))) return FFM_ERR_ARG;
+    PEqn a{psi, psi0, p0, rho, rho0, gh, gamma_f, phiHbyA_f, phiHbyA_b, ic, bc, upper, lower, diagOut, sourceOut, rDeltaT, pRef, {nullptr, nullptr, nullptr}};
+    FFM_TRY(ffm_tile_coef_direct(m->A, lower && lower != upper, &a.tile.fU, &a.tile.fL, &a.tile.bU));
+    LAUNCH_CELLS((k_p_rgh_eqn<FFM_TILE_W, true>), mview(m), a);
+    FFM_HIP(hipGetLastError());
+    ffm_tile_coef_written(m->A, upper, lower);
     return FFM_OK;
 }
 

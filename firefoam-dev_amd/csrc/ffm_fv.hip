@@ -490,19 +490,36 @@ __device__ __forceinline__ double scheme_weight(int scheme, double flux, double 
     const double p0 = flux >= 0 ? 1.0 : 0.0;
     return scheme == 0 ? p0 : scheme == 1 ? wlin : 0.75 * wlin + 0.25 * p0;
 }
-template <int W, bool SCHEME = false>
-__global__ void k_fvm_transport(MeshView q, double rDeltaT, const double *__restrict__ rho, const double *__restrict__ phi,
+// TILE: upper / lower also as the triples of the matrix's tile plan (ffm_device.hpp: store_triple; t.fL null: upper alone).  A cell
+// needs the coefficients of its lower faces, which another row owns: it forms them as the owner's row does, from the same face-indexed
+// operands, and so gets the owner's bits.
+// (the launch bound of the TILE form keeps the eighth wave per SIMD, which its extra pointers and slot masks would cost in scalar registers)
+template <int W, bool SCHEME = false, bool TILE = false>
+__global__ __launch_bounds__((TILE ? 256 : 1024), (TILE ? 8 : 1)) void k_fvm_transport(MeshView q, double rDeltaT, const double *__restrict__ rho, const double *__restrict__ phi,
                                 const double *__restrict__ wf, int scheme, const double *__restrict__ gamma, double lapSign,
-                                double *__restrict__ diag, double *__restrict__ upper, double *__restrict__ lower)
+                                double *__restrict__ diag, double *__restrict__ upper, double *__restrict__ lower, TileCoefOut t)
 {
     CELL_SCHED(ci, q) {
         const int c = (int)ci;
         RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
         double dDiv = 0.0, dLap = 0.0;
+        double lU[TILE ? W : 1] = {}, lL[TILE ? W : 1] = {}, uU[TILE ? W : 1] = {};        // TILE: upper / lower of the lower faces, upper of the own
         // faces where c is the neighbour: diag -= upper[f]
 #pragma unroll
         for (int s = 0; s < W; s++) if (L.on[s]) {
             const int e = L.f[s];
+            if constexpr (TILE) {       // the same two updates from the owner's coefficients of the face, which the triples take
+                double lo = 0.0, up = 0.0;
+                if (phi) { const double f = phi[e]; lo = -(SCHEME ? scheme_weight(scheme, f, q.w[e]) : wf[e]) * f; up = lo + f; dDiv -= (lo + f); }
+                if (gamma) {
+                    const double g = gamma[e] * q.magSf[e] * q.delta[e];
+                    dLap -= g;
+                    if (phi) { lo = lapSign < 0 ? lo - g : lo + g; up = lapSign < 0 ? up - g : up + g; }
+                    else { lo = lapSign < 0 ? -g : g; up = lo; }
+                }
+                lL[s] = lo; lU[s] = up;
+                continue;
+            }
             if (phi) { const double f = phi[e]; const double lo = -(SCHEME ? scheme_weight(scheme, f, q.w[e]) : wf[e]) * f; dDiv -= (lo + f); }
             if (gamma) dLap -= gamma[e] * q.magSf[e] * q.delta[e];
         }
@@ -520,6 +537,11 @@ __global__ void k_fvm_transport(MeshView q, double rDeltaT, const double *__rest
             }
             if (upper) upper[e] = up;
             if (lower) lower[e] = lo;
+            if constexpr (TILE) uU[s] = up;
+        }
+        if constexpr (TILE) {
+            store_triple(t.fU, c, L.on, lU); store_triple(t.bU, c, U.on, uU);
+            if (t.fL) store_triple(t.fL, c, L.on, lL);
         }
         double d = rho ? rDeltaT * rho[c] * q.V[c] : 0.0;
         if (phi) d = rho ? d + dDiv : dDiv;
@@ -806,7 +828,8 @@ extern "C" int ffm_fvm_transport(ffm_mesh *m, double rDeltaT, const double *rho,
     CHECK_M(m);
     // upper == NULL: no face coefficients wanted (a pure ddt term has none); lower == NULL: a symmetric result (no convection), lower = upper
     if (!diag || ((phi_f || gamma_f) && !upper) || (phi_f && (!w_f || !lower))) return FFM_ERR_ARG;
-    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_fvm_transport<W>, mview(m), rDeltaT, rho, phi_f, w_f, 0, gamma_f, (double)laplacianSign, diag, upper, lower));
+    m->A->directPending = false;        // off-diagonal arrays are being rewritten: a declaration of an earlier direct write (ffm_tile_coef_written) no longer holds
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_fvm_transport<W>, mview(m), rDeltaT, rho, phi_f, w_f, 0, gamma_f, (double)laplacianSign, diag, upper, lower, TileCoefOut()));
     DONE();
 }
 // ffm_fvm_transport with the convection weights of a scheme that needs phi and the mesh weights only (0 upwind, 1 linear, 4 LUST: what
@@ -816,7 +839,22 @@ extern "C" int ffm_fvm_transport_scheme(ffm_mesh *m, double rDeltaT, const doubl
 {
     CHECK_M(m);
     if ((scheme != 0 && scheme != 1 && scheme != 4) || !phi_f || !diag || !upper || !lower) return FFM_ERR_ARG;
-    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_fvm_transport<W, true>), mview(m), rDeltaT, rho, phi_f, nullptr, scheme, gamma_f, (double)laplacianSign, diag, upper, lower));
+    m->A->directPending = false;        // (as in ffm_fvm_transport)
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_fvm_transport<W, true>), mview(m), rDeltaT, rho, phi_f, nullptr, scheme, gamma_f, (double)laplacianSign, diag, upper, lower, TileCoefOut()));
+    DONE();
+}
+// The same, and the matrix's tile plan gets the sweep layout of upper / lower from this launch: binding exactly these two arrays next
+// (ffm_ldu_bind_coeffs_native_d, ffm_solve_multi_d) gathers nothing.  FFM_ERR_UNSUPPORTED with nothing written where the plan cannot
+// take them (ffm_tile_coef_direct): the caller then calls ffm_fvm_transport_scheme.
+extern "C" int ffm_fvm_transport_scheme_direct(ffm_mesh *m, double rDeltaT, const double *rho, const double *phi_f, int scheme,
+                                               const double *gamma_f, int laplacianSign, double *diag, double *upper, double *lower)
+{
+    CHECK_M(m);
+    if ((scheme != 0 && scheme != 1 && scheme != 4) || !phi_f || !diag || !upper || !lower || upper == lower) return FFM_ERR_ARG;
+    TileCoefOut t;
+    FFM_TRY(ffm_tile_coef_direct(m->A, true, &t.fU, &t.fL, &t.bU));
+    LAUNCH_CELLS((k_fvm_transport<FFM_TILE_W, true, true>), mview(m), rDeltaT, rho, phi_f, nullptr, scheme, gamma_f, (double)laplacianSign, diag, upper, lower, t);
+    ffm_tile_coef_written(m->A, upper, lower);
     DONE();
 }
 extern "C" int ffm_fvm_boundary_coeffs(ffm_mesh *m, const double *phib, const double *gammab, int laplacianSign, const double *f,

@@ -37,6 +37,11 @@ enum {
     S_NEG_ALPHA, S_ONE
 };
 
+// A solver's scalar operation (ffm_device.hpp: scalar_op_body) that rides on the one-workgroup launch which sums a reduction's
+// partials: thread 0 runs it after storing the sum.  fused == false: the launch only sums (more than one rank: the all-reduce sits
+// between the sum and the operation, ffm_solve.hip: finish_dot).
+struct ffm_scal_op { int op = 0; double arg = 0.0; int iter = 0; int in = S_TMP0; bool fused = false; };
+
 struct ffm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -180,6 +185,11 @@ struct ffm_ldu {
     int rDKind = -1;               // which preconditioner rD currently holds
     unsigned long coeffEpoch = 0, rDEpoch = ~0ul;
     unsigned long offDiagEpoch = 0;       // bumped when upper / lower change (coeffEpoch: any coefficient, diag included)
+    // the tile plan's coefficient arrays were written by the launch that wrote these native arrays (ffm_tile.hip: ffm_tile_coef_direct);
+    // pending until the next set / bind, which adopts them if it binds exactly these arrays
+    bool directPending = false;
+    const double *directUpper = nullptr, *directLower = nullptr;
+    unsigned long tileGathers = 0;        // k_tile_gather launches of this matrix (tests)
     double *diagBuf = nullptr, *upperBuf = nullptr;     // the library's own coefficient storage; diag/upper/lower may instead
                                                         // point at caller arrays (ffm_ldu_bind_coeffs_native_d)
 
@@ -227,7 +237,7 @@ int ffm_ldu_work(ffm_ldu *A, int idx, double **out);           // lazily allocat
 int ffm_to_internal(ffm_ldu *A, const double *x_d, int slot, const double **out);
 int ffm_from_internal(ffm_ldu *A, const double *xin, double *x_d);
 int ffm_k_spmv(ffm_ldu *A, const double *x, double *y, bool transpose);
-int ffm_k_spmv_dot(ffm_ldu *A, const double *x, double *y, int slot);  // y=Ax, scal[slot]=x.y (local)
+int ffm_k_spmv_dot(ffm_ldu *A, const double *x, double *y, int slot, const ffm_scal_op &t = ffm_scal_op());  // y=Ax, scal[slot]=x.y (local)
 int ffm_k_residual(ffm_ldu *A, const double *x, const double *b, double *r);
 int ffm_k_sumA(ffm_ldu *A, double *s);
 int ffm_k_spmv_sumA_rows(ffm_ldu *A, const double *x, double *y, double *s);   // this rank's rows, no ghost refresh
@@ -249,18 +259,22 @@ int ffm_ghost_exchange_split(ffm_ldu *A, const double *sendFrom, double *ghostIn
 int ffm_ghost_exchange_end(ffm_ldu *A);                  // the main stream waits for it
 int ffm_tile_gs(ffm_ldu *A, bool sym, double *psi, const double *bP, double *bSave, double *prod3);
 bool ffm_tile_amul_usable(const ffm_ldu *A);
-int ffm_tile_amul(ffm_ldu *A, const double *x, double *y, int dotSlot);     // returns 1 if the dot product is left to the caller
+int ffm_tile_amul(ffm_ldu *A, const double *x, double *y, int dotSlot, const ffm_scal_op &t = ffm_scal_op());     // returns 1 if the dot product is left to the caller
 void ffm_tile_free(ffm_ldu *A);
 bool ffm_tile_usable(const ffm_ldu *A);
 struct FfmFvSegs { int nSeg; const int4 *seg; const int4 *rec; };
 bool ffm_tile_fv_segments(ffm_ldu *A, int runLength, FfmFvSegs *out);   // single block, tile plan present: FV face passes through LDS (ffm_fused.hip)
+bool ffm_tile_coef_direct_ok(const ffm_ldu *A);          // no ghost cells, a tile plan, rows of at most FFM_TILE_W entries per side
+int ffm_tile_coef_direct(ffm_ldu *A, bool lower, double **fU, double **fL, double **bU);   // the plan's coefficient arrays, to be written by an assembly kernel
+void ffm_tile_coef_written(ffm_ldu *A, const double *upper_d, const double *lower_d);
+void ffm_tile_coef_adopt(ffm_ldu *A);
 bool ffm_tile_pcg_fusable(const ffm_ldu *A);
-int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double *qA = nullptr);
+int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double *qA = nullptr, const ffm_scal_op &t = ffm_scal_op());
 bool ffm_tile_amul_pcg_usable(const ffm_ldu *A);
 bool ffm_tile_amul_asym_usable(const ffm_ldu *A);
 int ffm_tile_amul_asym(ffm_ldu *A, const double *x, double *y);
-int ffm_tile_amul_pcg(ffm_ldu *A, const double *w, const double *pin, double *pout, double *psi, double *y, int dotSlot);
-int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot);
+int ffm_tile_amul_pcg(ffm_ldu *A, const double *w, const double *pin, double *pout, double *psi, double *y, int dotSlot, const ffm_scal_op &t = ffm_scal_op());
+int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot, const ffm_scal_op &t = ffm_scal_op());
 // n = 1 .. FFM_TILE_MAXSYS systems with the matrix's off-diagonal coefficients in one sweep (ffm_tile.hip: k_tile); n = 1: the matrix's own
 #define FFM_TILE_MAXSYS 5
 bool ffm_tile_multi_fits(const ffm_ldu *A, int n);      // n systems fit the LDS rings of one sweep (five: the short ring)
@@ -275,10 +289,10 @@ int ffm_halo_exchange(ffm_ldu *A, const double *x);
 int ffm_ghost_exchange(ffm_ldu *A, double *x);                 // refresh x[nOwned..nCells) from the neighbour ranks          // pack x[faceCells], exchange into haloRecv
 int ffm_read_scalars(ffm_ctx *ctx);  // scal_d -> scal_h, synchronises the stream
 
-// reductions into device scalar slots (local partial sums; caller all-reduces)
-int ffm_k_dot(ffm_ctx *ctx, const double *x, const double *y, long n, int slot);
-int ffm_k_summag(ffm_ctx *ctx, const double *x, long n, int slot);
-int ffm_k_sum(ffm_ctx *ctx, const double *x, long n, int slot);
-int ffm_k_sumsqr(ffm_ctx *ctx, const double *x, long n, int slot);
+// reductions into device scalar slots (local partial sums; caller all-reduces); t: an operation for the summing launch to run
+int ffm_k_dot(ffm_ctx *ctx, const double *x, const double *y, long n, int slot, const ffm_scal_op &t = ffm_scal_op());
+int ffm_k_summag(ffm_ctx *ctx, const double *x, long n, int slot, const ffm_scal_op &t = ffm_scal_op());
+int ffm_k_sum(ffm_ctx *ctx, const double *x, long n, int slot, const ffm_scal_op &t = ffm_scal_op());
+int ffm_k_sumsqr(ffm_ctx *ctx, const double *x, long n, int slot, const ffm_scal_op &t = ffm_scal_op());
 
 static inline int ffm_grid(long n, int threads) { return (int)((n + threads - 1) / threads); }

@@ -237,7 +237,7 @@ extern "C" int ffm_ldu_set_coeffs_d(ffm_ldu *A, const double *diag_d, const doub
     if (!A || !diag_d || (A->nFaces && !upper_d)) return FFM_ERR_ARG;
     hipStream_t s = A->ctx->stream;
     const size_t nb = sizeof(double) * A->nCells, fb = sizeof(double) * std::max(A->upTotal, 1);
-    A->diag = A->diagBuf; A->upper = A->upperBuf;
+    A->diag = A->diagBuf; A->upper = A->upperBuf; A->directPending = false;
     if (lower_d && lower_d != upper_d) {
         if (!A->lowerBuf) FFM_HIP(hipMalloc((void **)&A->lowerBuf, fb));
         A->lower = A->lowerBuf; A->symmetric = false;
@@ -279,7 +279,7 @@ extern "C" int ffm_ldu_set_coeffs_native_d(ffm_ldu *A, const double *diag_d, con
     if (!A->identity) { ffm_set_error("native coefficient layout needs the library's cell order (ffm_renumber_levels)"); return FFM_ERR_UNSUPPORTED; }
     hipStream_t s = A->ctx->stream;
     const size_t nb = sizeof(double) * A->nCells, fb = sizeof(double) * A->upTotal;
-    A->diag = A->diagBuf; A->upper = A->upperBuf;
+    A->diag = A->diagBuf; A->upper = A->upperBuf; A->directPending = false;
     if (lower_d && lower_d != upper_d) {
         if (!A->lowerBuf) FFM_HIP(hipMalloc((void **)&A->lowerBuf, std::max(fb, sizeof(double))));
         A->lower = A->lowerBuf; A->symmetric = false;
@@ -294,6 +294,7 @@ extern "C" int ffm_ldu_set_coeffs_native_d(ffm_ldu *A, const double *diag_d, con
 // Zero-copy form: the matrix uses the caller's device arrays (native layout) until the next set / bind call; the caller keeps
 // them alive and unchanged meanwhile.  offDiagUnchanged != 0: upper / lower hold the same values as at the previous call
 // (e.g. the components of a vector equation, which differ in the boundary diagonal only), so layouts derived from them are kept.
+// Arrays whose sweep layout the assembly kernel wrote beside them (ffm_tile_coef_written) bring it along: no gather for this epoch.
 extern "C" int ffm_ldu_bind_coeffs_native_d(ffm_ldu *A, const double *diag_d, const double *upper_d, const double *lower_d,
                                             int offDiagUnchanged)
 {
@@ -305,6 +306,9 @@ extern "C" int ffm_ldu_bind_coeffs_native_d(ffm_ldu *A, const double *diag_d, co
     else { A->lower = A->upper; A->symmetric = true; }
     A->coeffEpoch++;
     if (!offDiagUnchanged) A->offDiagEpoch++;
+    const bool adopt = A->directPending && !offDiagUnchanged && upper_d == A->directUpper && (A->symmetric ? !A->directLower : lower_d == A->directLower);
+    A->directPending = false;
+    if (adopt) ffm_tile_coef_adopt(A);
     return FFM_OK;
 }
 
@@ -313,7 +317,7 @@ extern "C" int ffm_ldu_bind_coeffs_native_d(ffm_ldu *A, const double *diag_d, co
 extern "C" int ffm_ldu_unbind_coeffs(ffm_ldu *A)
 {
     if (!A) return FFM_ERR_ARG;
-    A->diag = A->diagBuf; A->upper = A->upperBuf;
+    A->diag = A->diagBuf; A->upper = A->upperBuf; A->directPending = false;
     if (A->symmetric || !A->lowerBuf) { A->lower = A->upper; A->symmetric = true; } else A->lower = A->lowerBuf;
     // (the layouts derived from the off-diagonal coefficients stay as they are: a following bind with offDiagUnchanged != 0 -- the same
     // values again, e.g. the next specie sharing its coefficient arrays -- finds them current; any other set / bind renews them)
@@ -390,13 +394,13 @@ __global__ __launch_bounds__(256) void k_rows(LduView v, const double *__restric
     }
 }
 
-__global__ __launch_bounds__(1024) void k_sum_partials(int n, const double *__restrict__ partials, double *__restrict__ scal, int slot)
+__global__ __launch_bounds__(1024) void k_sum_partials(int n, const double *__restrict__ partials, double *__restrict__ scal, int slot, ffm_scal_op t)
 {
     __shared__ double sm[16];
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) acc += partials[i];
     double r = block_sum(acc, sm);
-    if (threadIdx.x == 0) scal[slot] = r;
+    if (threadIdx.x == 0) { scal[slot] = r; run_scal_op(scal, t); }
 }
 
 // grid of the row kernels: a multiple of 8 so that schedule entry i always meets blockIdx % 8 == i % 8
@@ -492,23 +496,23 @@ int ffm_k_spmv_multi(ffm_ldu *A, int n, const double *const *diag, const double 
     return FFM_OK;
 }
 
-int ffm_k_spmv_dot(ffm_ldu *A, const double *x, double *y, int slot)
+int ffm_k_spmv_dot(ffm_ldu *A, const double *x, double *y, int slot, const ffm_scal_op &t)
 {
     if (!A->ifaces.empty()) {  // the halo term changes y after the row kernel: separate dot
         FFM_TRY(ffm_k_spmv(A, x, y, false));
-        return ffm_k_dot(A->ctx, y, x, A->nOwned, slot);
+        return ffm_k_dot(A->ctx, y, x, A->nOwned, slot, t);
     }
     if (amul_form(A, false) == AMUL_TILE_SYM) {
         if (!A->ghNbrRank.empty()) FFM_TRY(ffm_ghost_exchange_begin(A, const_cast<double *>(x)));
-        const int rc = ffm_tile_amul(A, x, y, slot);
-        if (rc == 1) return ffm_k_dot(A->ctx, y, x, A->nOwned, slot);      // ghost faces were added after the tiled kernel
+        const int rc = ffm_tile_amul(A, x, y, slot, t);
+        if (rc == 1) return ffm_k_dot(A->ctx, y, x, A->nOwned, slot, t);      // ghost faces were added after the tiled kernel
         return rc;
     }
     if (!A->ghNbrRank.empty()) FFM_TRY(ffm_ghost_exchange(A, const_cast<double *>(x)));
     const int g = rows_grid(A);
     FFM_DISPATCH_W(A->maxW, hipLaunchKernelGGL((k_rows<0, true, W>), dim3(g), dim3(256), 0, A->ctx->stream, ffm_view(A), A->diag,
                                                A->upper, A->lower, x, (const double *)nullptr, y, A->ctx->partials_d));
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, A->ctx->stream, g, A->ctx->partials_d, A->ctx->scal_d, slot);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, A->ctx->stream, g, A->ctx->partials_d, A->ctx->scal_d, slot, t);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }

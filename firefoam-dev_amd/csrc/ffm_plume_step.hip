@@ -122,6 +122,13 @@ static int u_sources(ffm_plume *P, const double *mub)
     return ffm_fvm_lust_source3(m, P->rdt, P->phi, P->rho0, u0, ggx, ggy, ggz, P->Usrc);
 }
 
+// A fused assembly pass on a single block writes the sweeps' coefficient layout beside the native one (the *_direct entry points:
+// the solve that binds the arrays next gathers nothing); where the matrix's tile plan cannot take it, the plain form and the gather
+// (asked of the matrix first: a block that would be refused is not put to the call, and no refusal text is left behind a good step)
+#define DIRECT_OR(P, direct, plain) \
+    do { int rc_ = ((P)->oneBlock && ffm_tile_coef_direct_ok((P)->A)) ? (direct) : FFM_ERR_UNSUPPORTED; \
+         if (rc_ == FFM_ERR_UNSUPPORTED) rc_ = (plain); FFM_TRY(rc_); } while (0)
+
 static int u_eqn(ffm_plume *P)
 {
     ffm_mesh *m = P->mesh; const int N = P->N; const bool ops = !P->fused;
@@ -134,7 +141,8 @@ static int u_eqn(ffm_plume *P)
     forN(P, P->nNat, [=] __device__(long e) { muf[e] = MU; });
     forN(P, P->B, [=] __device__(long k) { mub[k] = MU; });
     if (ops) FFM_TRY(ffm_fvm_transport(m, P->rdt, P->rho, P->phi, wU, muf, -1, P->Udiag, P->Uupper, P->Ulower));
-    else FFM_TRY(ffm_fvm_transport_scheme(m, P->rdt, P->rho, P->phi, 4, muf, -1, P->Udiag, P->Uupper, P->Ulower));
+    else DIRECT_OR(P, ffm_fvm_transport_scheme_direct(m, P->rdt, P->rho, P->phi, 4, muf, -1, P->Udiag, P->Uupper, P->Ulower),
+                   ffm_fvm_transport_scheme(m, P->rdt, P->rho, P->phi, 4, muf, -1, P->Udiag, P->Uupper, P->Ulower));
     FFM_TRY(u_buoyancy(P, rec));
     FFM_TRY(u_sources(P, mub));
     // fvMatrix::solveSegregated: the three components share the face coefficients -- one lock-step solve (ffm_solve_multi_d).
@@ -309,8 +317,10 @@ static int species_eqns(ffm_plume *P, bool *offDiagBound, bool withH)
         vf0q[ns] = P->hs0; fq5[ns] = P->fH; rq5[ns] = P->refH; gq5[ns] = P->zeroB; suq5[ns] = P->Qdot; fac[ns] = 1.0; su2q[ns] = shSu; spq[ns] = shSp;
         expl[3 * ns] = kt.ddtK; expl[3 * ns + 1] = kt.divK; expl[3 * ns + 2] = kt.ndpdt;
         dd[ns] = P->dWork; ss[ns] = P->sWork; nmq[ns] = "h"; pq[ns] = P->hs;
-        FFM_TRY(ffm_fvm_scalar_transport_multi_ws(m, nq, P->wMv, rdt, P->rho, P->rho0, P->phi, P->phib, af, afb, vf0q, fq5, rq5, gq5, suq5, fac, su2q,
-                                                  spq, expl, dd, uu, ll, ss));
+        DIRECT_OR(P, ffm_fvm_scalar_transport_multi_ws_direct(m, nq, P->wMv, rdt, P->rho, P->rho0, P->phi, P->phib, af, afb, vf0q, fq5, rq5, gq5, suq5, fac,
+                                                              su2q, spq, expl, dd, uu, ll, ss),
+                  ffm_fvm_scalar_transport_multi_ws(m, nq, P->wMv, rdt, P->rho, P->rho0, P->phi, P->phib, af, afb, vf0q, fq5, rq5, gq5, suq5, fac, su2q,
+                                                    spq, expl, dd, uu, ll, ss));
         FFM_TRY(solve_named_multi(P, nq, nmq, 1e-8, dd, P->spU[0], P->spL[0], pq, ss));
         for (int j = 0; j < nq; j++) FFM_TRY(HX(P, pq[j]));
         P->jointSteps++;
@@ -319,8 +329,10 @@ static int species_eqns(ffm_plume *P, bool *offDiagBound, bool withH)
         // differ, through the patch conditions and the sources): written once, gathered into the sweeps' layout once; the assembly
         // pass forms nu_i*wFuel itself
         double *uShared[ns] = {P->spU[0], nullptr, nullptr, nullptr}, *lShared[ns] = {P->spL[0], nullptr, nullptr, nullptr};
-        FFM_TRY(ffm_fvm_scalar_transport_multi_ws(m, ns, P->wMv, rdt, P->rho, P->rho0, P->phi, P->phib, af, afb, vf0, fq, rq, gq, suq, nuq, nullptr,
-                                                  nullptr, nullptr, P->spD, uShared, lShared, P->spS));
+        DIRECT_OR(P, ffm_fvm_scalar_transport_multi_ws_direct(m, ns, P->wMv, rdt, P->rho, P->rho0, P->phi, P->phib, af, afb, vf0, fq, rq, gq, suq, nuq,
+                                                              nullptr, nullptr, nullptr, P->spD, uShared, lShared, P->spS),
+                  ffm_fvm_scalar_transport_multi_ws(m, ns, P->wMv, rdt, P->rho, P->rho0, P->phi, P->phib, af, afb, vf0, fq, rq, gq, suq, nuq, nullptr,
+                                                    nullptr, nullptr, P->spD, uShared, lShared, P->spS));
         const char *nmq[ns]; double *pq[ns];
         for (int j = 0; j < ns; j++) { nmq[j] = SPN[sp[j]]; pq[j] = P->Y[sp[j]]; }
         FFM_TRY(solve_named_multi(P, ns, nmq, 1e-8, P->spD, P->spU[0], P->spL[0], pq, P->spS));
@@ -569,9 +581,11 @@ static int pc_p_rgh_eqn(ffm_plume *P, const PCorr &w, bool final)
     if (ops) FFM_TRY(ffm_fvm_transport(m, P->rdt, P->psi, nullptr, nullptr, w.rhorAUf, -1, P->diag, P->upper, P->lower));
     FFM_TRY(ffm_fvm_boundary_coeffs(m, nullptr, w.rhorAUfb, -1, P->fP, P->refP, P->gradP, P->ic[0], P->bc[0]));
     // (the fused form writes no `lower`: the matrix is symmetric, the solve and pc_flux_U read `upper` in both roles)
-    FFM_TRY(!ops ? ffm_fvm_pressure_eqn(m, P->rdt, P->psi, P->psi0, P->p_rgh0, P->rho, P->rho0, P->gh, PREF, w.rhorAUf, w.phiHbyA, w.phiHbyAb,
-                                            P->ic[0], P->bc[0], P->upper, nullptr, P->dWork, P->sWork)
-                     : pc_p_rgh_eqn_ops(P, w));
+    if (ops) FFM_TRY(pc_p_rgh_eqn_ops(P, w));
+    else DIRECT_OR(P, ffm_fvm_pressure_eqn_direct(m, P->rdt, P->psi, P->psi0, P->p_rgh0, P->rho, P->rho0, P->gh, PREF, w.rhorAUf, w.phiHbyA, w.phiHbyAb,
+                                                  P->ic[0], P->bc[0], P->upper, nullptr, P->dWork, P->sWork),
+                   ffm_fvm_pressure_eqn(m, P->rdt, P->psi, P->psi0, P->p_rgh0, P->rho, P->rho0, P->gh, PREF, w.rhorAUf, w.phiHbyA, w.phiHbyAb,
+                                        P->ic[0], P->bc[0], P->upper, nullptr, P->dWork, P->sWork));
     FFM_TRY(solve_named(P, "p_rgh", FFM_PCG, FFM_DIC, 1e-6, final ? 0.0 : 0.01, P->dWork, P->upper, nullptr, P->p_rgh, P->sWork));
     return HX(P, P->p_rgh);
 }

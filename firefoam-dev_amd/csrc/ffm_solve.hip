@@ -34,52 +34,11 @@
 
 
 // --------------------------------------------------------------- scalar ops ---
-enum {
-    OP_XREF = 1, OP_NORMF, OP_RES_INIT, OP_RES, OP_PCG_BETA, OP_PCG_ALPHA,
-    OP_BS_RHO, OP_BS_ALPHA, OP_BS_OMEGA, OP_BICG_BETA, OP_BICG_ALPHA, OP_RESET
-};
-
-#define VSMALL_ 1e-300
-
-// in: the slot the operation takes its sum from (the prologue kernel leaves three sums in S_TMP0..S_TMP2)
-__global__ void k_scalar_op(double *__restrict__ s, int op, double arg, int iter, int in)
+// (the operations: ffm_device.hpp, scalar_op_body)
+__global__ void k_scalar_op(double *s, int op, double arg, int iter, int in)
 {
     if (threadIdx.x || blockIdx.x) return;
-    switch (op) {
-    case OP_RESET:
-        s[S_SING] = 0.0; s[S_WARA] = 1e+20; s[S_WARA_OLD] = 1e+20; s[S_RA0RA] = 0.0; s[S_ALPHA] = 0.0; s[S_OMEGA] = 0.0;
-        s[S_BETA] = 0.0;
-        break;
-    case OP_XREF: s[S_XREF] = s[S_TMP0] / arg; break;                    // gAverage(psi)
-    case OP_NORMF: s[S_NORMF] = s[S_TMP0] + 1e-20; break;                // + solverPerformance::small_
-    case OP_RES_INIT: s[S_RES] = s[in] / s[S_NORMF]; s[S_RES0] = s[S_RES]; break;
-    case OP_RES: if (s[S_SING] == 0.0) s[S_RES] = s[S_TMP0] / s[S_NORMF]; break;
-    case OP_PCG_BETA: {                                                  // wArAold = wArA; wArA = (wA,rA)
-        const double old = s[S_WARA], nw = s[S_TMP0];
-        s[S_WARA_OLD] = old; s[S_WARA] = nw; s[S_BETA] = nw / old;
-        break; }
-    case OP_PCG_ALPHA: case OP_BICG_ALPHA: {                             // wApA; checkSingularity(|wApA|/normFactor)
-        const double wApA = s[S_TMP0];
-        s[S_WAPA] = wApA;
-        if (fabs(wApA) / s[S_NORMF] > VSMALL_) { s[S_ALPHA] = s[S_WARA] / wApA; }
-        else { s[S_SING] = 1.0; s[S_ALPHA] = 0.0; }
-        break; }
-    case OP_BS_RHO: {                                                    // rA0rAold = rA0rA; rA0rA = (rA0,rA)
-        const double old = s[S_RA0RA], nw = s[in];
-        s[S_RA0RA_OLD] = old; s[S_RA0RA] = nw;
-        if (!(fabs(nw) > VSMALL_)) { s[S_SING] = 1.0; break; }
-        if (iter > 0) {
-            if (!(fabs(s[S_OMEGA]) > VSMALL_)) { s[S_SING] = 1.0; break; }
-            s[S_BETA] = (nw / old) * (s[S_ALPHA] / s[S_OMEGA]);
-        }
-        break; }
-    case OP_BS_ALPHA: if (s[S_SING] == 0.0) { s[S_RA0AYA] = s[S_TMP0]; s[S_ALPHA] = s[S_RA0RA] / s[S_TMP0]; } break;
-    case OP_BS_OMEGA: if (s[S_SING] == 0.0) { s[S_TATA] = s[S_TMP0]; s[S_TASA] = s[S_TMP1]; s[S_OMEGA] = s[S_TMP1] / s[S_TMP0]; } break;
-    case OP_BICG_BETA: {
-        const double old = s[S_WARA], nw = s[S_TMP0];
-        s[S_WARA_OLD] = old; s[S_WARA] = nw; s[S_BETA] = nw / old;
-        break; }
-    }
+    scalar_op_body(s, op, arg, iter, in);
 }
 
 static int scalar_op(ffm_ctx *c, int op, double arg = 0.0, int iter = 0, int in = S_TMP0)
@@ -88,11 +47,19 @@ static int scalar_op(ffm_ctx *c, int op, double arg = 0.0, int iter = 0, int in 
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
-// local sum sits in S_TMP0(..S_TMP0+n-1): all-reduce over ranks, then derive
-static int finish_dot(ffm_ctx *c, int op, int nSlots = 1, double arg = 0.0, int iter = 0)
+// The operation that follows a reduction.  One rank: it rides on the reduction's one-workgroup launch that sums the partials (the
+// reduction calls take it as their last argument) and finish_dot has nothing left to do.  More ranks: the local sum sits in
+// S_TMP0(..S_TMP0+n-1), finish_dot adds the ranks' and then derives, in a launch of its own.
+static ffm_scal_op tail_op(ffm_ctx *c, int op, double arg = 0.0, int iter = 0)
 {
-    if (c->nRanks > 1 || c->comm) FFM_TRY(ffm_allreduce_slots(c, S_TMP0, nSlots));
-    return scalar_op(c, op, arg, iter);
+    ffm_scal_op t; t.op = op; t.arg = arg; t.iter = iter; t.fused = c->nRanks == 1 && !c->comm;
+    return t;
+}
+static int finish_dot(ffm_ctx *c, const ffm_scal_op &t, int nSlots = 1)
+{
+    if (t.fused) return FFM_OK;
+    FFM_TRY(ffm_allreduce_slots(c, S_TMP0, nSlots));
+    return scalar_op(c, t.op, t.arg, t.iter);
 }
 
 // ----------------------------------------------------------- vector kernels ---
@@ -106,14 +73,15 @@ __global__ void k_copy(long n, double *__restrict__ d, const double *__restrict_
 { GRID_STRIDE(i, n) d[i] = s[i]; }
 
 // The prologue of a solve once xRef is known, one pass over Apsi, source and sumA:
-//   rA = source - Apsi;  partials[0..] = the normFactor sum |Apsi - xRef*sumA| + |source - xRef*sumA|;  partials[RED_BLOCKS..] = sum |rA|;
-//   BS (PBiCGStab): rA0 = rA, pA = rA (the search direction of iteration 0) and partials[2*RED_BLOCKS..] = rA0.rA = sum rA*rA.
+//   r = source - Apsi;  partials[0..] = the normFactor sum |Apsi - xRef*sumA| + |source - xRef*sumA|;  partials[RED_BLOCKS..] = sum |r|;
+//   BS (PBiCGStab): also partials[2*RED_BLOCKS..] = rA0.rA = sum r*r.  There r is rA0: at iteration 0 rA, rA0 and the search
+//   direction pA are one vector, which is written once and read under all three names (pbicgstab_lanes).
 // Grid, block, stride and block_sum are those of the reductions of ffm_ctx.hip (k_reduce1), so every sum keeps its partition and
-// its tree.  sumA may be the vector pA is written to: every load of a cell precedes its stores, hence no __restrict__ on the two.
+// its tree.
 template <bool BS>
-__global__ __launch_bounds__(256) void k_prologue(long n, const double *__restrict__ Ax, const double *__restrict__ b, const double *sumA,
-                                                  const double *__restrict__ scal, double *__restrict__ r, double *__restrict__ r0,
-                                                  double *p, double *__restrict__ partials)
+__global__ __launch_bounds__(256) void k_prologue(long n, const double *__restrict__ Ax, const double *__restrict__ b,
+                                                  const double *__restrict__ sumA, const double *__restrict__ scal, double *__restrict__ r,
+                                                  double *__restrict__ partials)
 {
     __shared__ double sm[4];
     const double xRef = scal[S_XREF];
@@ -124,7 +92,7 @@ __global__ __launch_bounds__(256) void k_prologue(long n, const double *__restri
         accN += fabs(ax - t) + fabs(bi - t);
         accR += fabs(ri);
         r[i] = ri;
-        if (BS) { accD += ri * ri; r0[i] = ri; p[i] = ri; }
+        if (BS) accD += ri * ri;
     }
     const double sN = block_sum(accN, sm);
     const double sR = block_sum(accR, sm);
@@ -178,13 +146,14 @@ __global__ void k_axmy_alpha(long n, double *__restrict__ r, const double *__res
     GRID_STRIDE(i, n) r[i] -= alpha * w[i];
 }
 
-// PBiCGStab: pA = rA + beta*(pA - omega*AyA)      (iteration 0, pA = rA: k_prologue)
-__global__ void k_bs_p(long n, double *__restrict__ p, const double *__restrict__ r, const double *__restrict__ AyA,
+// PBiCGStab: pA = rA + beta*(pOld - omega*AyA).  pOld is pA itself (an element is loaded before it is stored: no __restrict__ on
+// the two) except at iteration 1, where the direction of iteration 0 is rA0 (k_prologue).
+__global__ void k_bs_p(long n, double *p, const double *pOld, const double *__restrict__ r, const double *__restrict__ AyA,
                        const double *__restrict__ scal)
 {
     if (scal[S_SING] != 0.0) return;
     const double beta = scal[S_BETA], omega = scal[S_OMEGA];
-    GRID_STRIDE(i, n) p[i] = r[i] + beta * (p[i] - omega * AyA[i]);
+    GRID_STRIDE(i, n) p[i] = r[i] + beta * (pOld[i] - omega * AyA[i]);
 }
 
 // sA = rA - alpha*AyA; partial |sA|
@@ -221,7 +190,7 @@ __global__ __launch_bounds__(256) void k_dot2(long n, const double *__restrict__
 }
 
 __global__ __launch_bounds__(1024) void k_sum_partials2(int n, const double *__restrict__ partials, double *__restrict__ scal,
-                                                        int slot, int nSums)
+                                                        int slot, int nSums, ffm_scal_op t)
 {
     __shared__ double sm[16];
     for (int k = 0; k < nSums; k++) {
@@ -230,6 +199,7 @@ __global__ __launch_bounds__(1024) void k_sum_partials2(int n, const double *__r
         const double r = block_sum(acc, sm);
         if (threadIdx.x == 0) scal[slot + k] = r;
     }
+    if (threadIdx.x == 0) run_scal_op(scal, t);
 }
 
 // psi += alpha*yA + omega*zA; rA = sA - omega*tA; partial |rA|
@@ -261,9 +231,9 @@ __global__ void k_mul(long n, double *__restrict__ w, const double *__restrict__
 __global__ void k_recip(long n, double *__restrict__ d, const double *__restrict__ s)
 { GRID_STRIDE(i, n) d[i] = 1.0 / s[i]; }
 
-static int partial_sum_to(ffm_ctx *c, int nb, int slot, int nSums = 1)
+static int partial_sum_to(ffm_ctx *c, int nb, int slot, int nSums = 1, const ffm_scal_op &t = ffm_scal_op())
 {
-    hipLaunchKernelGGL(k_sum_partials2, dim3(1), dim3(1024), 0, c->stream, nb, c->partials_d, c->scal_d, slot, nSums);
+    hipLaunchKernelGGL(k_sum_partials2, dim3(1), dim3(1024), 0, c->stream, nb, c->partials_d, c->scal_d, slot, nSums, t);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
@@ -572,27 +542,30 @@ static inline bool check_convergence(ffm_perf *p, const Controls &k)
 }
 
 // rA = source - Apsi, normFactor and the initial residual: Apsi = A psi already computed, tmp holds sumA on entry
-// (ffm_k_spmv_sumA at the top of every solver).  PBiCGStab passes rA0 and pA (pA may be tmp) and gets rA0 = pA = rA and
-// rA0.rA in S_TMP2 as well (k_prologue).  The sums' ranks are added in one all-reduce.
+// (ffm_k_spmv_sumA at the top of every solver).  PBiCGStab (bs) passes its rA0 as rA: the one vector that is rA, rA0 and pA at
+// iteration 0, and gets rA0.rA in S_TMP2 as well (k_prologue); tmp may be its pA, which is not written before iteration 1.
+// The sums' ranks are added in one all-reduce.
 static int norm_and_initial(ffm_ldu *A, const double *psi, const double *source, const double *Apsi, const double *tmp,
-                            double *rA, ffm_perf *perf, double *rA0 = nullptr, double *pA = nullptr, bool rowsOnly = false)
+                            double *rA, ffm_perf *perf, bool bs = false, bool rowsOnly = false)
 {
     ffm_ctx *c = A->ctx; hipStream_t s = c->stream; const long N = A->nOwned;
-    FFM_TRY(ffm_k_sum(c, psi, N, S_TMP0));
-    if (rowsOnly) {     // the norms of this rank's rows alone (ffm_solve_triangular_rows_d): no sum over ranks
+    if (rowsOnly) {
+        FFM_TRY(ffm_k_sum(c, psi, N, S_TMP0));     // the norms of this rank's rows alone (ffm_solve_triangular_rows_d): no sum over ranks
         FFM_TRY(scalar_op(c, OP_XREF, (double)N));
-        hipLaunchKernelGGL(k_prologue<false>, dim3(sgrid(N)), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, (double *)nullptr, (double *)nullptr, c->partials_d);
+        hipLaunchKernelGGL(k_prologue<false>, dim3(sgrid(N)), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, c->partials_d);
         FFM_TRY(partial_sum_to(c, sgrid(N), S_TMP0, 2));
         FFM_TRY(scalar_op(c, OP_NORMF));
         FFM_TRY(scalar_op(c, OP_RES_INIT, 0.0, 0, S_TMP1));
         return FFM_OK;
     }
-    FFM_TRY(finish_dot(c, OP_XREF, 1, (double)A->globalCells));
-    const int g = sgrid(N), nSums = rA0 ? 3 : 2;
-    if (rA0) hipLaunchKernelGGL(k_prologue<true>, dim3(g), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, rA0, pA, c->partials_d);
-    else hipLaunchKernelGGL(k_prologue<false>, dim3(g), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, (double *)nullptr, (double *)nullptr, c->partials_d);
-    FFM_TRY(partial_sum_to(c, g, S_TMP0, nSums));
-    FFM_TRY(finish_dot(c, OP_NORMF, nSums));
+    const ffm_scal_op xref = tail_op(c, OP_XREF, (double)A->globalCells), normf = tail_op(c, OP_NORMF);
+    FFM_TRY(ffm_k_sum(c, psi, N, S_TMP0, xref));
+    FFM_TRY(finish_dot(c, xref));
+    const int g = sgrid(N), nSums = bs ? 3 : 2;
+    if (bs) hipLaunchKernelGGL(k_prologue<true>, dim3(g), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, c->partials_d);
+    else hipLaunchKernelGGL(k_prologue<false>, dim3(g), dim3(256), 0, s, N, Apsi, source, tmp, c->scal_d, rA, c->partials_d);
+    FFM_TRY(partial_sum_to(c, g, S_TMP0, nSums, normf));
+    FFM_TRY(finish_dot(c, normf, nSums));
     FFM_TRY(scalar_op(c, OP_RES_INIT, 0.0, 0, S_TMP1));
     FFM_TRY(ffm_read_scalars(c));
     perf->initialResidual = c->scal_h[S_RES0];
@@ -612,6 +585,7 @@ static int pcg(ffm_ldu *A, int precond, const Controls &k, double *psi, const do
     FFM_TRY(norm_and_initial(A, psi, source, wA, pA, rA, perf));
     if (k.minIter > 0 || !check_convergence(perf, k)) {
         FFM_TRY(ffm_precond_setup_i(A, precond));
+        const ffm_scal_op beta = tail_op(c, OP_PCG_BETA), alpha = tail_op(c, OP_PCG_ALPHA), res = tail_op(c, OP_RES);
         if (precond == FFM_DIC && A->sweepMode == 2 && ffm_tile_pcg_fusable(A)) {
             // The same iteration with the vector updates carried by the sweeps (ffm_tile.hip, k_tile<.., FUSE>): the residual
             // update and its norm ride on the forward sweep of the NEXT preconditioner application (which is therefore started
@@ -626,22 +600,22 @@ static int pcg(ffm_ldu *A, int precond, const Controls &k, double *psi, const do
             do {
                 if (perf->nIterations == 0) {
                     FFM_TRY(ffm_precond_apply_i(A, precond, false, rA, wA));
-                    FFM_TRY(ffm_k_dot(c, wA, rA, N, S_TMP0));
-                } else FFM_TRY(ffm_tile_pcg_bwd(A, rA, wA, S_TMP0));
-                FFM_TRY(finish_dot(c, OP_PCG_BETA));
+                    FFM_TRY(ffm_k_dot(c, wA, rA, N, S_TMP0, beta));
+                } else FFM_TRY(ffm_tile_pcg_bwd(A, rA, wA, S_TMP0, beta));
+                FFM_TRY(finish_dot(c, beta));
                 if (perf->nIterations == 0) {
                     hipLaunchKernelGGL(k_p_update, dim3(g), dim3(256), 0, s, N, pA, wA, c->scal_d, 1);
-                    FFM_TRY(ffm_k_spmv_dot(A, pA, qA, S_TMP0));
+                    FFM_TRY(ffm_k_spmv_dot(A, pA, qA, S_TMP0, alpha));
                 } else if (fuseP) {
-                    FFM_TRY(ffm_tile_amul_pcg(A, wA, pA, pB, psi, qA, S_TMP0));
+                    FFM_TRY(ffm_tile_amul_pcg(A, wA, pA, pB, psi, qA, S_TMP0, alpha));
                     std::swap(pA, pB);
                 } else {
                     hipLaunchKernelGGL(k_p_psi, dim3(g), dim3(256), 0, s, N, psi, pA, wA, c->scal_d);
-                    FFM_TRY(ffm_k_spmv_dot(A, pA, qA, S_TMP0));
+                    FFM_TRY(ffm_k_spmv_dot(A, pA, qA, S_TMP0, alpha));
                 }
-                FFM_TRY(finish_dot(c, OP_PCG_ALPHA));
-                FFM_TRY(ffm_tile_pcg_fwd(A, rA, wA, S_TMP0, qA == wA ? nullptr : qA));
-                FFM_TRY(finish_dot(c, OP_RES));
+                FFM_TRY(finish_dot(c, alpha));
+                FFM_TRY(ffm_tile_pcg_fwd(A, rA, wA, S_TMP0, qA == wA ? nullptr : qA, res));
+                FFM_TRY(finish_dot(c, res));
                 FFM_TRY(ffm_read_scalars(c));
                 if (c->scal_h[S_SING] != 0.0) { perf->singular = 1; break; }
                 perf->finalResidual = c->scal_h[S_RES];
@@ -652,14 +626,14 @@ static int pcg(ffm_ldu *A, int precond, const Controls &k, double *psi, const do
         }
         do {
             FFM_TRY(ffm_precond_apply_i(A, precond, false, rA, wA));
-            FFM_TRY(ffm_k_dot(c, wA, rA, N, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_PCG_BETA));
+            FFM_TRY(ffm_k_dot(c, wA, rA, N, S_TMP0, beta));
+            FFM_TRY(finish_dot(c, beta));
             hipLaunchKernelGGL(k_p_update, dim3(g), dim3(256), 0, s, N, pA, wA, c->scal_d, perf->nIterations == 0 ? 1 : 0);
-            FFM_TRY(ffm_k_spmv_dot(A, pA, wA, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_PCG_ALPHA));
+            FFM_TRY(ffm_k_spmv_dot(A, pA, wA, S_TMP0, alpha));
+            FFM_TRY(finish_dot(c, alpha));
             hipLaunchKernelGGL(k_pcg_xr, dim3(g), dim3(256), 0, s, N, psi, rA, pA, wA, c->scal_d, c->partials_d);
-            FFM_TRY(partial_sum_to(c, g, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_RES));
+            FFM_TRY(partial_sum_to(c, g, S_TMP0, 1, res));
+            FFM_TRY(finish_dot(c, res));
             FFM_TRY(ffm_read_scalars(c));
             if (c->scal_h[S_SING] != 0.0) { perf->singular = 1; break; }
             perf->finalResidual = c->scal_h[S_RES];
@@ -681,6 +655,7 @@ struct Lane {
     double *scal_d, *scal_h;
     int work;                   // its work vectors are ffm_ldu_work(work + 1 .. work + 8)
     double *rD, *pA, *yA, *rA, *AyA, *sA, *zA, *tA, *rA0;
+    double *dir, *res;          // the search direction and the residual this iteration reads: pA and rA, at iteration 0 both rA0
     bool active;
 };
 struct LaneGuard {          // the context's scalar block and the matrix's diagonal / reciprocal diagonal are switched per lane
@@ -743,7 +718,7 @@ static int pbicgstab_lanes(ffm_ldu *A, int precond, const Controls &k, int n, La
     }
     for (int i = 0; i < n; i++) {
         Lane &l = L[i]; G.use(l);
-        FFM_TRY(norm_and_initial(A, l.psi, l.source, l.yA, l.pA, l.rA, l.perf, l.rA0, l.pA));          // (reads this lane's scalars back)
+        FFM_TRY(norm_and_initial(A, l.psi, l.source, l.yA, l.pA, l.rA0, l.perf, true));          // (sumA in pA; reads this lane's scalars back)
         l.active = k.minIter > 0 || !check_convergence(l.perf, k);
         if (!l.active) continue;
         FFM_TRY(ffm_ldu_work(A, l.work + 4, &l.AyA)); FFM_TRY(ffm_ldu_work(A, l.work + 5, &l.sA)); FFM_TRY(ffm_ldu_work(A, l.work + 6, &l.zA));
@@ -757,25 +732,31 @@ static int pbicgstab_lanes(ffm_ldu *A, int precond, const Controls &k, int n, La
         else if (m == 1) { G.use(L[only]); if (n > 1) A->rDKind = -1; FFM_TRY(ffm_precond_setup_i(A, precond)); }
         if (n > 1) { A->rDKind = precond; A->rDEpoch = A->coeffEpoch; }
     }
+    // Iteration 0: rA, rA0 and pA are one vector, the rA0 that the prologue wrote, read wherever the iteration reads rA or pA.  It
+    // ends with k_bs_xr writing rA; iteration 1 forms pA, with rA0 as the direction before it.
+    const ffm_scal_op alpha = tail_op(c, OP_BS_ALPHA), res = tail_op(c, OP_RES), omega = tail_op(c, OP_BS_OMEGA);
     for (;;) {
         bool any = false;
         for (int i = 0; i < n; i++) if (L[i].active) {
             Lane &l = L[i]; G.use(l); any = true;
-            if (l.perf->nIterations == 0) { FFM_TRY(scalar_op(c, OP_BS_RHO, 0.0, 0, S_TMP2)); continue; }       // rA0.rA and pA = rA came with the prologue
-            FFM_TRY(ffm_k_dot(c, l.rA0, l.rA, N, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_BS_RHO, 1, 0.0, l.perf->nIterations));
-            hipLaunchKernelGGL(k_bs_p, dim3(g), dim3(256), 0, s, N, l.pA, l.rA, l.AyA, c->scal_d);
+            const int it = l.perf->nIterations;
+            if (it == 0) { l.dir = l.res = l.rA0; FFM_TRY(scalar_op(c, OP_BS_RHO, 0.0, 0, S_TMP2)); continue; }       // rA0.rA came with the prologue
+            const ffm_scal_op rho = tail_op(c, OP_BS_RHO, 0.0, it);
+            FFM_TRY(ffm_k_dot(c, l.rA0, l.rA, N, S_TMP0, rho));
+            FFM_TRY(finish_dot(c, rho));
+            hipLaunchKernelGGL(k_bs_p, dim3(g), dim3(256), 0, s, N, l.pA, (const double *)l.dir, l.rA, l.AyA, c->scal_d);
+            l.dir = l.pA; l.res = l.rA;
         }
         if (!any) break;
-        FFM_TRY(precond_lanes(A, precond, L, n, &Lane::pA, &Lane::yA, G));
+        FFM_TRY(precond_lanes(A, precond, L, n, &Lane::dir, &Lane::yA, G));
         FFM_TRY(amul_lanes(A, L, n, &Lane::yA, &Lane::AyA, G));
         for (int i = 0; i < n; i++) if (L[i].active) {
             Lane &l = L[i]; G.use(l);
-            FFM_TRY(ffm_k_dot(c, l.rA0, l.AyA, N, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_BS_ALPHA));
-            hipLaunchKernelGGL(k_bs_s, dim3(g), dim3(256), 0, s, N, l.sA, l.rA, l.AyA, c->scal_d, c->partials_d);
-            FFM_TRY(partial_sum_to(c, g, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_RES));
+            FFM_TRY(ffm_k_dot(c, l.rA0, l.AyA, N, S_TMP0, alpha));
+            FFM_TRY(finish_dot(c, alpha));
+            hipLaunchKernelGGL(k_bs_s, dim3(g), dim3(256), 0, s, N, l.sA, (const double *)l.res, l.AyA, c->scal_d, c->partials_d);
+            FFM_TRY(partial_sum_to(c, g, S_TMP0, 1, res));
+            FFM_TRY(finish_dot(c, res));
         }
         FFM_TRY(read_lane_scalars(c, L, n));
         for (int i = 0; i < n; i++) if (L[i].active) {
@@ -793,11 +774,11 @@ static int pbicgstab_lanes(ffm_ldu *A, int precond, const Controls &k, int n, La
         for (int i = 0; i < n; i++) if (L[i].active) {
             Lane &l = L[i]; G.use(l);
             hipLaunchKernelGGL(k_dot2, dim3(g), dim3(256), 0, s, N, l.tA, l.sA, c->partials_d);
-            FFM_TRY(partial_sum_to(c, g, S_TMP0, 2));
-            FFM_TRY(finish_dot(c, OP_BS_OMEGA, 2));
+            FFM_TRY(partial_sum_to(c, g, S_TMP0, 2, omega));
+            FFM_TRY(finish_dot(c, omega, 2));
             hipLaunchKernelGGL(k_bs_xr, dim3(g), dim3(256), 0, s, N, l.psi, l.rA, l.yA, l.zA, l.sA, l.tA, c->scal_d, c->partials_d);
-            FFM_TRY(partial_sum_to(c, g, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_RES));
+            FFM_TRY(partial_sum_to(c, g, S_TMP0, 1, res));
+            FFM_TRY(finish_dot(c, res));
         }
         FFM_TRY(read_lane_scalars(c, L, n));
         for (int i = 0; i < n; i++) if (L[i].active) {
@@ -829,22 +810,23 @@ static int pbicg(ffm_ldu *A, int precond, const Controls &k, double *psi, const 
     FFM_TRY(norm_and_initial(A, psi, source, wA, pA, rA, perf));
     if (k.minIter > 0 || !check_convergence(perf, k)) {
         FFM_TRY(ffm_precond_setup_i(A, precond));
+        const ffm_scal_op beta = tail_op(c, OP_BICG_BETA), alpha = tail_op(c, OP_BICG_ALPHA), res = tail_op(c, OP_RES);
         do {
             FFM_TRY(ffm_precond_apply_i(A, precond, false, rA, wA));
             FFM_TRY(ffm_precond_apply_i(A, precond, true, rT, wT));
-            FFM_TRY(ffm_k_dot(c, wA, rT, N, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_BICG_BETA));
+            FFM_TRY(ffm_k_dot(c, wA, rT, N, S_TMP0, beta));
+            FFM_TRY(finish_dot(c, beta));
             const int first = perf->nIterations == 0 ? 1 : 0;
             hipLaunchKernelGGL(k_p_update, dim3(g), dim3(256), 0, s, N, pA, wA, c->scal_d, first);
             hipLaunchKernelGGL(k_p_update, dim3(g), dim3(256), 0, s, N, pT, wT, c->scal_d, first);
             FFM_TRY(ffm_k_spmv(A, pA, wA, false));
             FFM_TRY(ffm_k_spmv(A, pT, wT, true));
-            FFM_TRY(ffm_k_dot(c, wA, pT, N, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_BICG_ALPHA));
+            FFM_TRY(ffm_k_dot(c, wA, pT, N, S_TMP0, alpha));
+            FFM_TRY(finish_dot(c, alpha));
             hipLaunchKernelGGL(k_axmy_alpha, dim3(g), dim3(256), 0, s, N, rT, wT, c->scal_d);
             hipLaunchKernelGGL(k_pcg_xr, dim3(g), dim3(256), 0, s, N, psi, rA, pA, wA, c->scal_d, c->partials_d);
-            FFM_TRY(partial_sum_to(c, g, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_RES));
+            FFM_TRY(partial_sum_to(c, g, S_TMP0, 1, res));
+            FFM_TRY(finish_dot(c, res));
             FFM_TRY(ffm_read_scalars(c));
             if (c->scal_h[S_SING] != 0.0) { perf->singular = 1; break; }
             perf->finalResidual = c->scal_h[S_RES];
@@ -865,11 +847,12 @@ static int smooth(ffm_ldu *A, int smoother, const Controls &k, double *psi, cons
     FFM_TRY(ffm_k_spmv_sumA(A, psi, Apsi, tmp));
     FFM_TRY(norm_and_initial(A, psi, source, Apsi, tmp, res, perf));
     if (k.minIter > 0 || !check_convergence(perf, k)) {
+        const ffm_scal_op resOp = tail_op(c, OP_RES);
         do {
             FFM_TRY(ffm_gs_smooth_i(A, smoother == FFM_SYMGS, nSweeps, psi, source));
             FFM_TRY(ffm_k_residual(A, psi, source, res));
-            FFM_TRY(ffm_k_summag(c, res, N, S_TMP0));
-            FFM_TRY(finish_dot(c, OP_RES));
+            FFM_TRY(ffm_k_summag(c, res, N, S_TMP0, resOp));
+            FFM_TRY(finish_dot(c, resOp));
             FFM_TRY(ffm_read_scalars(c));
             perf->finalResidual = c->scal_h[S_RES];
         } while (((perf->nIterations += nSweeps) < k.maxIter && !check_convergence(perf, k)) || perf->nIterations < k.minIter);
@@ -946,7 +929,7 @@ static int exact_solve_begin(ffm_ldu *A, bool ranks, const double *psi, const do
     FFM_TRY(ffm_ldu_work(A, 1, &sumA)); FFM_TRY(ffm_ldu_work(A, 2, &Apsi)); FFM_TRY(ffm_ldu_work(A, 3, rA));
     FFM_TRY(scalar_op(A->ctx, OP_RESET));
     FFM_TRY(ranks ? ffm_k_spmv_sumA(A, psi, Apsi, sumA) : ffm_k_spmv_sumA_rows(A, psi, Apsi, sumA));
-    return norm_and_initial(A, psi, source, Apsi, sumA, *rA, out, nullptr, nullptr, !ranks);
+    return norm_and_initial(A, psi, source, Apsi, sumA, *rA, out, false, !ranks);
 }
 // v[0 .. n) -> their sum (isMax 0) or maximum (1) over the ranks; n <= 4
 static int allreduce_host_values(ffm_ctx *c, double *v, int n, int isMax)

@@ -779,10 +779,59 @@ static int tile_coef(ffm_ldu *A, TileDir &d, bool upper, const double **out)
         const int g = std::max(1, std::min(ffm_grid(n, 256), 8 * RED_BLOCKS));
         hipLaunchKernelGGL(k_tile_gather, dim3(g), dim3(256), 0, A->ctx->stream, n, d.src, upper ? A->upper : A->lower, buf);
         ep = A->offDiagEpoch;
+        A->tileGathers++;
     }
     *out = buf;
     return FFM_OK;
 }
+
+// The same arrays written by the kernel that assembles the matrix (ffm_device.hpp: store_triple) instead of gathered from its native
+// coefficients: the forward direction's upper (and, lower: lower) coefficients and the backward direction's upper ones, handed out
+// for writing.  They count as stale from here on; ffm_tile_coef_written declares them current for native arrays that the same
+// launch wrote, and the bind of exactly those arrays (ffm_ldu_bind_coeffs_native_d) adopts them for the epoch it opens.  Any
+// other set / bind, and any plain assembly entry point of the mesh (it may refill the same arrays), drops the declaration and the
+// next sweep gathers.  b.coefL (transposed DILU) is always gathered.
+// FFM_ERR_UNSUPPORTED, nothing touched: a block with ghost cells (their faces are dropped from the triples), no tile plan, rows
+// wider than T_W (the assembly kernel's slots would not be the plan's).
+bool ffm_tile_coef_direct_ok(const ffm_ldu *A) { return ffm_tile_usable(A) && A->nCells == A->nOwned && A->maxW <= T_W && A->identity; }
+int ffm_tile_coef_direct(ffm_ldu *A, bool lower, double **fU, double **fL, double **bU)
+{
+    if (!ffm_tile_coef_direct_ok(A)) {
+        ffm_set_error("sweep-layout coefficients cannot be written directly: ghost cells, no tile plan or rows wider than %d", T_W);
+        return FFM_ERR_UNSUPPORTED;
+    }
+    ffm_tile_plan *T = A->tile;
+    const size_t bytes = sizeof(double) * std::max<long>((long)T_W * A->nOwned, 1);
+    double **buf[3] = {&T->f.coefU, lower ? &T->f.coefL : nullptr, &T->b.coefU};
+    for (double **b : buf) if (b && !*b) FFM_HIP(hipMalloc((void **)b, bytes));
+    T->f.epochU = T->b.epochU = ~0ul;
+    if (lower) T->f.epochL = ~0ul;
+    A->directPending = false;
+    *fU = T->f.coefU; *fL = lower ? T->f.coefL : nullptr; *bU = T->b.coefU;
+    return FFM_OK;
+}
+void ffm_tile_coef_written(ffm_ldu *A, const double *upper_d, const double *lower_d)
+{
+    A->directPending = true; A->directUpper = upper_d; A->directLower = (lower_d && lower_d != upper_d) ? lower_d : nullptr;
+}
+// (called by the bind that found its arrays declared: the epoch is the one it has just opened)
+void ffm_tile_coef_adopt(ffm_ldu *A)
+{
+    ffm_tile_plan *T = A->tile;
+    T->f.epochU = T->b.epochU = A->offDiagEpoch;
+    if (A->directLower) T->f.epochL = A->offDiagEpoch;
+}
+// tests: one of the plan's arrays as a sweep would find it -- made current first -- on the host; which: 0 f.coefU, 1 f.coefL,
+// 2 b.coefU, 3 b.coefL; out_h [3*nOwned].  And the number of gathers this matrix has launched.
+extern "C" int ffm_ldu_tile_coef_read(ffm_ldu *A, int which, double *out_h)
+{
+    if (!A || !out_h || which < 0 || which > 3) return FFM_ERR_ARG;
+    if (!ffm_tile_usable(A)) { ffm_set_error("ffm_ldu_tile_coef_read: the matrix has no tile plan"); return FFM_ERR_UNSUPPORTED; }
+    const double *p;
+    FFM_TRY(tile_coef(A, which < 2 ? A->tile->f : A->tile->b, !(which & 1), &p));
+    return ffm_d2h(A->ctx, out_h, p, sizeof(double) * (size_t)T_W * A->nOwned);
+}
+extern "C" long ffm_ldu_tile_gathers(const ffm_ldu *A) { return A ? (long)A->tileGathers : -1; }
 
 static void tile_fill(ffm_ldu *A, double *p, long n)
 {
@@ -858,17 +907,17 @@ int ffm_tile_calc_rD(ffm_ldu *A, int n, const double *const *diag, double *const
     return FFM_OK;
 }
 
-__global__ void k_tile_sum_partials(int n, const double *__restrict__ partials, double *__restrict__ scal, int slot);
+__global__ void k_tile_sum_partials(int n, const double *__restrict__ partials, double *__restrict__ scal, int slot, ffm_scal_op t);
 // PCG with DIC on a tile plan: the two halves of the preconditioner application with the neighbouring vector
 // updates fused in (k_tile<.., FUSE>).  Forward: rA -= scal[S_ALPHA]*wA, scal[slot] = sum |rA| (local), wA = forward sweep of rA.
-// Backward: finishes wA, scal[slot] = sum wA*rA (local).
+// Backward: finishes wA, scal[slot] = sum wA*rA (local).  t: the scalar operation that follows the sum, run by the launch that sums.
 bool ffm_tile_pcg_fusable(const ffm_ldu *A)
 {
     const char *e = getenv("FFM_PCG_UNFUSED");
     const bool off = e && atoi(e) != 0;
     return !off && ffm_tile_usable(A) && A->tile->G <= 4 * RED_BLOCKS;
 }
-int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double *qA)
+int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double *qA, const ffm_scal_op &t)
 {
     ffm_tile_plan *T = A->tile;
     hipStream_t s = A->ctx->stream;
@@ -877,18 +926,18 @@ int ffm_tile_pcg_fwd(ffm_ldu *A, double *rA, double *wA, int slot, const double 
     FFM_TRY(tile_coef(A, T->b, true, &cb));
     FFM_TRY(tile_mail(A, 1, false, &mail));
     tile_launch<TM_FWD, 1, T_RING, true>(A, T->f, mail, cf, nullptr, &rD, &qA, &wA, rA, A->ctx->scal_d, A->ctx->partials_d);
-    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
+    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot, t);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
-int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot)
+int ffm_tile_pcg_bwd(ffm_ldu *A, const double *rA, double *wA, int slot, const ffm_scal_op &t)
 {
     ffm_tile_plan *T = A->tile;
     hipStream_t s = A->ctx->stream;
     const double *cb, *rD = A->rD;
     FFM_TRY(tile_coef(A, T->b, true, &cb));
     tile_launch<TM_BWD, 1, T_RING, true>(A, T->b, T->mailAll, cb, nullptr, &rD, &rA, &wA, nullptr, A->ctx->scal_d, A->ctx->partials_d);      // (mailboxes: filled by the forward half)
-    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot);
+    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->G, (const double *)A->ctx->partials_d, A->ctx->scal_d, slot, t);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
@@ -1112,13 +1161,13 @@ int ffm_tile_gs_ghost_terms(ffm_ldu *A, const double *psi, double *bP)
     return FFM_OK;
 }
 
-__global__ __launch_bounds__(1024) void k_tile_sum_partials(int n, const double *__restrict__ partials, double *__restrict__ scal, int slot)
+__global__ __launch_bounds__(1024) void k_tile_sum_partials(int n, const double *__restrict__ partials, double *__restrict__ scal, int slot, ffm_scal_op t)
 {
     __shared__ double sm[16];
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) acc += partials[i];
     const double r = block_sum(acc, sm);
-    if (threadIdx.x == 0) scal[slot] = r;
+    if (threadIdx.x == 0) { scal[slot] = r; run_scal_op(scal, t); }
 }
 
 bool ffm_tile_amul_usable(const ffm_ldu *A) { return ffm_tile_usable(A) && A->tile->amulUsable && A->symmetric && A->ifaces.empty(); }
@@ -1152,7 +1201,7 @@ bool ffm_tile_amul_pcg_usable(const ffm_ldu *A)
 {
     return ffm_tile_amul_usable(A) && A->tile->nTail == 0 && A->ghNbrRank.empty();
 }
-int ffm_tile_amul_pcg(ffm_ldu *A, const double *w, const double *pin, double *pout, double *psi, double *y, int dotSlot)
+int ffm_tile_amul_pcg(ffm_ldu *A, const double *w, const double *pin, double *pout, double *psi, double *y, int dotSlot, const ffm_scal_op &t)
 {
     ffm_tile_plan *T = A->tile;
     hipStream_t s = A->ctx->stream;
@@ -1161,13 +1210,13 @@ int ffm_tile_amul_pcg(ffm_ldu *A, const double *w, const double *pin, double *po
     AmulView v; v.G = T->G; v.grpCell = A->grpCell; v.grpEnt = T->f.grpEnt; v.rec = T->arec; v.seg = T->aseg; v.code = T->acode; v.ext = T->aext;
     hipLaunchKernelGGL((k_tile_amul<true, true>), dim3(T->nSeg), dim3(T_THREADS + 64), 0, s, v, bcoef, (const double *)A->upper, (const double *)A->diag, w, y,
                        T->amulPartials, pin, pout, psi, (const double *)A->ctx->scal_d);
-    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->nSeg, (const double *)T->amulPartials, A->ctx->scal_d, dotSlot);
+    hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->nSeg, (const double *)T->amulPartials, A->ctx->scal_d, dotSlot, t);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
 
-// y = A x (symmetric A); dotSlot >= 0: also scal[dotSlot] = x.y over the owned rows (local part)
-int ffm_tile_amul(ffm_ldu *A, const double *x, double *y, int dotSlot)
+// y = A x (symmetric A); dotSlot >= 0: also scal[dotSlot] = x.y over the owned rows (local part), followed by the operation t
+int ffm_tile_amul(ffm_ldu *A, const double *x, double *y, int dotSlot, const ffm_scal_op &t)
 {
     ffm_tile_plan *T = A->tile;
     hipStream_t s = A->ctx->stream;
@@ -1178,7 +1227,7 @@ int ffm_tile_amul(ffm_ldu *A, const double *x, double *y, int dotSlot)
     if (fusedDot) {
         FFM_TRY(ffm_ghost_exchange_end(A));          // (no ghost faces on this rank: nothing in flight that the kernel would need)
         hipLaunchKernelGGL((k_tile_amul<true>), dim3(T->nSeg), dim3(T_THREADS + 64), 0, s, v, bcoef, (const double *)A->upper, (const double *)A->diag, x, y, T->amulPartials);
-        hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->nSeg, (const double *)T->amulPartials, A->ctx->scal_d, dotSlot);
+        hipLaunchKernelGGL(k_tile_sum_partials, dim3(1), dim3(1024), 0, s, T->nSeg, (const double *)T->amulPartials, A->ctx->scal_d, dotSlot, t);
     } else {
         hipLaunchKernelGGL((k_tile_amul<false>), dim3(T->nSeg), dim3(T_THREADS + 64), 0, s, v, bcoef, (const double *)A->upper, (const double *)A->diag, x, y, (double *)nullptr);
         FFM_TRY(ffm_ghost_exchange_end(A));          // an overlapped ghost refresh (ffm_ghost_exchange_begin) must have landed before the tail

@@ -193,6 +193,12 @@ int ffm_ldu_unbind_coeffs(ffm_ldu *ldu);
  * a bind with offDiagUnchanged != 0 do not.  A caller that remembers which arrays it bound last may pass offDiagUnchanged != 0 only
  * while this value is the one it saw after that bind: nobody else has given the matrix other off-diagonals meanwhile          */
 unsigned long ffm_ldu_offdiag_epoch(const ffm_ldu *ldu);
+/* test support of the tiled sweeps' coefficient arrays (three doubles per cell and array: the present entries of a row in row order,
+ * then 0.0): one of them, made current first as a sweep would, copied to the host -- which: 0 forward upper, 1 forward lower,
+ * 2 backward upper, 3 backward lower; out_h [3 * owned cells]; FFM_ERR_UNSUPPORTED without a tile plan -- and the number of gather passes
+ * the matrix has launched to fill them (the *_direct assembly entry points below fill them without one)                        */
+int ffm_ldu_tile_coef_read(ffm_ldu *ldu, int which, double *out_h);
+long ffm_ldu_tile_gathers(const ffm_ldu *ldu);
 
 /* processor patches (lduInterface / interfaceBouCoeffs / interfaceIntCoeffs):
  * face i of patch p couples cell faceCells[p][i] (caller numbering) with face i
@@ -365,6 +371,13 @@ int ffm_fvm_transport(ffm_mesh *m, double rDeltaT, const double *rho,
  * ffm_fvm_transport. */
 int ffm_fvm_transport_scheme(ffm_mesh *m, double rDeltaT, const double *rho, const double *phi_f, int scheme,
                              const double *gamma_f, int laplacianSign, double *diag, double *upper, double *lower);
+/* The *_direct form of an assembly entry point writes what the plain form writes, and from the same launch the layout in which the
+ * tiled sweeps of the mesh's matrix read upper / lower.  The solve that binds EXACTLY these upper / lower arrays next
+ * (ffm_ldu_bind_coeffs_native_d, ffm_solve_multi_d), unchanged, then needs no gather pass; any other set / bind in between, and any
+ * plain assembly entry point of the mesh called in between (it may refill the same arrays), makes that solve gather as ever.  FFM_ERR_UNSUPPORTED, nothing written, where the matrix has ghost cells, no tile plan or rows of more than three lower or
+ * upper entries: call the plain form.  upper != lower. */
+int ffm_fvm_transport_scheme_direct(ffm_mesh *m, double rDeltaT, const double *rho, const double *phi_f, int scheme,
+                                    const double *gamma_f, int laplacianSign, double *diag, double *upper, double *lower);
 /* internalCoeffs / boundaryCoeffs of the same terms for a patch field in
  * `mixed` form (valueFraction f, refValue, refGradient); fixedValue,
  * zeroGradient, fixedGradient, inletOutlet are special cases               */
@@ -405,6 +418,11 @@ int ffm_fvm_pressure_eqn(ffm_mesh *m, double rDeltaT, const double *psi, const d
                          const double *rho, const double *rho0, const double *gh, double pRef, const double *gamma_f,
                          const double *phiHbyA_f, const double *phiHbyA_b, const double *internalCoeffs,
                          const double *boundaryCoeffs, double *upper, double *lower, double *diagOut, double *sourceOut);
+/* its *_direct form (see ffm_fvm_transport_scheme_direct) */
+int ffm_fvm_pressure_eqn_direct(ffm_mesh *m, double rDeltaT, const double *psi, const double *psi0, const double *p0,
+                                const double *rho, const double *rho0, const double *gh, double pRef, const double *gamma_f,
+                                const double *phiHbyA_f, const double *phiHbyA_b, const double *internalCoeffs,
+                                const double *boundaryCoeffs, double *upper, double *lower, double *diagOut, double *sourceOut);
 /* three face passes of the pressure corrector (solver/pEqn.H:9-19,43-44), each two per-operator passes in one with their arithmetic:
  * phig = -rhorAUf*ghf*fvc::snGrad(rho)*magSf;  phiHbyA = (fvc::flux(rho*HbyA) + rhorAUf*ddtCorr) + phig;
  * fl = p_rghEqn.flux(), phi = phiHbyA + fl, t = (fl + phig)/rhorAUf (internal faces, native layout; symmetric matrix: lower = upper) */
@@ -499,6 +517,14 @@ int ffm_fvm_scalar_transport_multi_ws(ffm_mesh *m, int nf, const double *w_f, do
                                       const double *const *refGrad, const double *const *su, const double *suFactor,
                                       const double *const *su2, const double *const *sp, const double *const *expl3,
                                       double *const *diag, double *const *upper, double *const *lower, double *const *source);
+/* its *_direct form (see ffm_fvm_transport_scheme_direct) for the forms the time step uses: nf = 4 or 5 fields with suFactor given that
+ * share one set of off-diagonals, upper[0] / lower[0] non-NULL and different, all others NULL (anything else: FFM_ERR_UNSUPPORTED) */
+int ffm_fvm_scalar_transport_multi_ws_direct(ffm_mesh *m, int nf, const double *w_f, double rDeltaT, const double *rho, const double *rho0,
+                                             const double *phi_f, const double *phi_b, const double *gamma_f, const double *gamma_b,
+                                             const double *const *vf0, const double *const *f, const double *const *ref,
+                                             const double *const *refGrad, const double *const *su, const double *suFactor,
+                                             const double *const *su2, const double *const *sp, const double *const *expl3,
+                                             double *const *diag, double *const *upper, double *const *lower, double *const *source);
 /* momentum source of solver/UEqn.H:5 with `div(phi,U) Gauss LUST grad(U)`: source_c = rDeltaT*rho0*U0_c*V
  * - V*fvc::surfaceIntegrate(phi*LUST::correction(U_c)) for the three components from their gradients                  */
 int ffm_fvm_lust_source3(ffm_mesh *m, double rDeltaT, const double *phi_f, const double *rho0, const double *const *U0,
