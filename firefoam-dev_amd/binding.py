@@ -267,6 +267,10 @@ def lib():
         "ffm_plume_step": ([vp], C.c_int),
         "ffm_plume_set_tight": ([vp, C.c_int], C.c_int),
         "ffm_plume_set_solvers": ([vp, C.c_int], C.c_int),
+        "ffm_plume_set_turbulence": ([vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, hp], C.c_int),
+        "ffm_les_keqn_terms": ([vp, C.POINTER(vp), dp, dp, dp, dp, dp, dp, dp, C.c_double, dp, dp, dp], C.c_int),
+        "ffm_les_face_diffusivity": ([vp, C.c_int, C.c_double, dp, dp, dp, dp, dp, dp], C.c_int),
+        "ffm_les_keqn_update": ([vp, C.c_long, C.c_double, C.c_double, C.c_double, dp, dp, dp, dp, dp], C.c_int),
         "ffm_plume_set_radiation": ([vp, C.c_int, C.c_int, C.c_int, vp, vp], C.c_int),
         "ffm_plume_set_radiation_model": ([vp, C.c_double, C.c_double, C.c_double], C.c_int),
         "ffm_plume_set_radiation_ordering": ([vp, C.c_int], C.c_int),
@@ -882,6 +886,19 @@ class Plume:
     def set_solvers(self, steckler=True):
         """transport equations with smoothSolver + symGaussSeidel (maxIter 10) as cases/steckler/system/fvSolution:49-62"""
         _check(lib().ffm_plume_set_solvers(self.h, 1 if steckler else 0), "ffm_plume_set_solvers")
+
+    def set_turbulence(self, model="kEqn", Ck=0.094, Ce=1.048, Prt=1.0, kInlet=1e-4, k0=None):
+        """the step's sub-grid model (ffm_plume_set_turbulence): "kEqn" -- LES kEqn with delta cubeRootVol, the coefficients of
+        cases/steckler/constant/turbulenceProperties:18-30 -- or None / "none"; k0: k per cell in natural order, None = kInlet"""
+        names = {None: 0, "none": 0, "kEqn": 1}
+        if model not in names:
+            raise ValueError("set_turbulence: model %r (None, 'none' or 'kEqn')" % (model,))
+        if k0 is not None:
+            k0 = np.ascontiguousarray(k0, np.float64)
+            if k0.shape != (self.nCells,):
+                raise ValueError("set_turbulence: k0 holds one value per cell")
+        _check(lib().ffm_plume_set_turbulence(self.h, names[model], float(Ck), float(Ce), float(Prt), float(kInlet), None if k0 is None else _hp(k0)),
+               "ffm_plume_set_turbulence")
 
     def set_radiation(self, solverFreq=100, nPhi=2, nTheta=4, rays=None):
         """fvDOM stand-in: 4*nPhi*nTheta upwind ray solves every solverFreq steps; rays = [(dAve[3], omega)] or None"""

@@ -1356,25 +1356,29 @@ extern "C" int ffm_fvc_div_dev2T_gradU(ffm_mesh *m, const double *const *g, cons
 }
 
 // kEqn::correct (LESModels/kEqn/kEqn.C): G = nut*(gradU && dev(twoSymm(gradU))), per cell
+__device__ __forceinline__ double les_G_of(const double g[3][3], double nut)
+{
+    double ts[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) ts[a][b] = g[a][b] + g[b][a];
+    const double tr = (ts[0][0] + ts[1][1]) + ts[2][2];
+#pragma unroll
+    for (int a = 0; a < 3; a++) ts[a][a] = ts[a][a] - (1.0 / 3.0) * tr;
+    double s = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) s += g[a][b] * ts[a][b];
+    return nut * s;
+}
 __global__ void k_les_G(long n, const double *g00, const double *g01, const double *g02, const double *g10, const double *g11, const double *g12,
                         const double *g20, const double *g21, const double *g22, const double *__restrict__ nut, double *__restrict__ G)
 {
     GRID_STRIDE(i, n) {
         const double g[3][3] = {{g00[i], g01[i], g02[i]}, {g10[i], g11[i], g12[i]}, {g20[i], g21[i], g22[i]}};
-        double ts[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int b = 0; b < 3; b++) ts[a][b] = g[a][b] + g[b][a];
-        const double tr = (ts[0][0] + ts[1][1]) + ts[2][2];
-#pragma unroll
-        for (int a = 0; a < 3; a++) ts[a][a] = ts[a][a] - (1.0 / 3.0) * tr;
-        double s = 0.0;
-#pragma unroll
-        for (int a = 0; a < 3; a++)
-#pragma unroll
-            for (int b = 0; b < 3; b++) s += g[a][b] * ts[a][b];
-        G[i] = nut[i] * s;
+        G[i] = les_G_of(g, nut[i]);
     }
 }
 extern "C" int ffm_les_keqn_G(ffm_mesh *m, const double *const *g, const double *nut, double *G)
@@ -1383,6 +1387,127 @@ extern "C" int ffm_les_keqn_G(ffm_mesh *m, const double *const *g, const double 
     if (!g || !nut || !G) return FFM_ERR_ARG;
     for (int k = 0; k < 9; k++) if (!g[k]) return FFM_ERR_ARG;
     LAUNCH(k_les_G, m->N, (long)m->N, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], nut, G);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// ---- kEqn in the compiled time step (ffm_plume_step.hip: k_eqn, u_eqn, standin_combustion) -----------------------------------------
+// The explicit terms of kEqn::correct (LESModels/kEqn/kEqn.C) in one owner-row pass: divU = fvc::surfaceIntegrate(phi/interpolate(rho))
+// from the row's faces and patch faces in k_face_sum's order (lower faces -, upper faces +, patch faces +, then /V), G from the nine
+// cell gradients, and from them the three arrays a scalar transport assembly takes:
+//   su = rho*G      su2 = -(min(s, 0)*k)      sp = max(s, 0) + Ce*rho*sqrt(k)/delta,      s = (2/3)*rho*divU
+// i.e. rho*G - fvm::SuSp(s, k) - fvm::Sp(Ce rho sqrt(k)/delta, k) with SuSp's split; the two implicit parts are summed in that order.
+// Equal, bit for bit, to ffm_fvc_interpolate + phi/rho_f + ffm_fvc_surface_integrate + ffm_les_keqn_G + the cell algebra.
+struct LesTerms {
+    const double *g[3][3];          // [i][j] = d_i U_j
+    const double *nut, *rho, *rhob, *k, *delta, *phi, *phib;
+    double Ce;
+    double *su, *su2, *sp;
+};
+template <int W>
+__global__ __launch_bounds__(256) void k_les_keqn_terms(MeshView q, LesTerms a)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci;
+        RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
+        const double rP = a.rho[c];
+        double acc = 0.0;
+        // (slots that are off point at face 0 and at c itself: their loads are in bounds and their quotient is dropped)
+#pragma unroll
+        for (int s = 0; s < W; s++) {       // owner of the face: the neighbour cell
+            const int e = L.f[s]; const double w = q.w[e];
+            const double t = a.phi[e] / (w * a.rho[L.nb[s]] + (1.0 - w) * rP);
+            if (L.on[s]) acc = acc - t;
+        }
+#pragma unroll
+        for (int s = 0; s < W; s++) {
+            const int e = U.f[s]; const double w = q.w[e];
+            const double t = a.phi[e] / (w * rP + (1.0 - w) * a.rho[U.nb[s]]);
+            if (U.on[s]) acc += t;
+        }
+        const int j = q.cellB[c];
+        if (j >= 0) for (int t = q.bcStart[j]; t < q.bcStart[j + 1]; t++) { const int k = q.bcItem[t]; acc += a.phib[k] / a.rhob[k]; }
+        const double divU = acc / q.V[c];
+        double g[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int jj = 0; jj < 3; jj++) g[i][jj] = a.g[i][jj][c];
+        const double G = les_G_of(g, a.nut[c]), kc = a.k[c];
+        const double ss = (2.0 / 3.0) * rP * divU;
+        a.su[c] = rP * G;
+        a.su2[c] = -(fmin(ss, 0.0) * kc);
+        a.sp[c] = fmax(ss, 0.0) + a.Ce * rP * sqrt(kc) / a.delta[c];
+    }
+}
+// g: nine device pointers, g[3*i + j] = d_i U_j; rho_b: patch values of rho [B]
+extern "C" int ffm_les_keqn_terms(ffm_mesh *m, const double *const *g, const double *nut, const double *rho, const double *rho_b, const double *k,
+                                  const double *delta, const double *phi_f, const double *phi_b, double Ce, double *su, double *su2, double *sp)
+{
+    CHECK_M(m);
+    if (!g || !nut || !rho || !k || !delta || !phi_f || !su || !su2 || !sp || (m->B && (!rho_b || !phi_b))) return FFM_ERR_ARG;
+    LesTerms a;
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { if (!g[3 * i + j]) return FFM_ERR_ARG; a.g[i][j] = g[3 * i + j]; }
+    a.nut = nut; a.rho = rho; a.rhob = rho_b; a.k = k; a.delta = delta; a.phi = phi_f; a.phib = phi_b; a.Ce = Ce; a.su = su; a.su2 = su2; a.sp = sp;
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_les_keqn_terms<W>, mview(m), a));
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// A linearly interpolated face field and its patch values from a cell expression formed on the fly, one owner-row pass, no cell field:
+//   mode 0: rho*nuEff as the product rho*(x + c0/rho), x = nut, c0 = mu     (divDevRhoReff's and kEqn's diffusivity; patch: rho_b, x_b)
+//   mode 1: c0 + x, x = alphat, c0 = alpha                                    (alphaEff; patch: c0 + x_b; rho is not read)
+// Equal, bit for bit, to the cell expression followed by ffm_fvc_interpolate(NULL, .) and the same expression on the patch faces.
+struct LesFaceDiff { const double *rho, *rhob, *x, *xb; double c0; double *outf, *outb; };
+template <int MODE> __device__ __forceinline__ double les_diff_of(double c0, double rho, double x) { return MODE == 0 ? rho * (x + c0 / rho) : c0 + x; }
+template <int W, int MODE>
+__global__ __launch_bounds__(256) void k_les_face_diffusivity(MeshView q, LesFaceDiff a)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci;
+        RowEnt<W> U; load_upper<W>(q.v, c, U);
+        const double P = les_diff_of<MODE>(a.c0, MODE == 0 ? a.rho[c] : 0.0, a.x[c]);
+#pragma unroll
+        for (int s = 0; s < W; s++) if (U.on[s]) {
+            const int e = U.f[s], n = U.nb[s]; const double w = q.w[e];
+            a.outf[e] = w * P + (1.0 - w) * les_diff_of<MODE>(a.c0, MODE == 0 ? a.rho[n] : 0.0, a.x[n]);
+        }
+        const int j = q.cellB[c];
+        if (j >= 0) for (int t = q.bcStart[j]; t < q.bcStart[j + 1]; t++) {
+            const int k = q.bcItem[t];
+            a.outb[k] = les_diff_of<MODE>(a.c0, MODE == 0 ? a.rhob[k] : 0.0, a.xb[k]);
+        }
+    }
+}
+extern "C" int ffm_les_face_diffusivity(ffm_mesh *m, int mode, double c0, const double *rho, const double *rho_b, const double *x, const double *x_b,
+                                        double *out_f, double *out_b)
+{
+    CHECK_M(m);
+    if ((mode != 0 && mode != 1) || !x || !out_f || (mode == 0 && !rho) || (m->B && (!x_b || !out_b || (mode == 0 && !rho_b)))) return FFM_ERR_ARG;
+    LesFaceDiff a = {rho, rho_b, x, x_b, c0, out_f, out_b};
+    if (mode == 0) FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_les_face_diffusivity<W, 0>), mview(m), a));
+    else FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_les_face_diffusivity<W, 1>), mview(m), a));
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// bound(k, kMin) and kEqn::correctNut in one cell pass: k = max(k, kMin), nut = Ck sqrt(k) delta, alphat = rho nut/Prt over the first
+// n <= nCells + ghost cells (ffm_les_keqn_nut_d's expressions on the bounded k)
+__global__ void k_les_keqn_update(long n, double kMin, double Ck, double Prt, double *__restrict__ k, const double *__restrict__ delta,
+                                  const double *__restrict__ rho, double *__restrict__ nut, double *__restrict__ alphat)
+{
+    GRID_STRIDE(i, n) {
+        const double kc = fmax(k[i], kMin);
+        const double v = Ck * sqrt(kc) * delta[i];
+        k[i] = kc; nut[i] = v; alphat[i] = rho[i] * v / Prt;
+    }
+}
+extern "C" int ffm_les_keqn_update(ffm_mesh *m, long n, double kMin, double Ck, double Prt, double *k, const double *delta, const double *rho,
+                                   double *nut, double *alphat)
+{
+    CHECK_M(m);
+    if (n < 0 || n > m->N || !k || !delta || !rho || !nut || !alphat || !(Prt > 0)) return FFM_ERR_ARG;
+    if (n) LAUNCH(k_les_keqn_update, n, n, kMin, Ck, Prt, k, delta, rho, nut, alphat);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }

@@ -336,10 +336,68 @@ extern "C" int ffm_plume_override_mv_weights(ffm_plume *P, const double *w)
     return FFM_OK;
 }
 extern "C" int ffm_plume_set_solvers(ffm_plume *P, int stecklerSelection) { if (!P) return FFM_ERR_ARG; P->stecklerSolvers = stecklerSelection != 0; return FFM_OK; }
+
+// give a buffer of the handle back (ffm_plume_set_turbulence 0); the caller has synchronised the stream
+static void dfree(ffm_plume *P, double *&p)
+{
+    if (!p) return;
+    P->pool.erase(std::remove(P->pool.begin(), P->pool.end(), p), P->pool.end());
+    hipFree(p); p = nullptr;
+}
+// the sub-grid model of the step: see include/ffm.h
+extern "C" int ffm_plume_set_turbulence(ffm_plume *P, int model, double Ck, double Ce, double Prt, double kInlet, const double *k0)
+{
+    if (!P) return FFM_ERR_ARG;
+    if (model != 0 && model != 1) { ffm_set_error("ffm_plume_set_turbulence: unknown model %d (0 none, 1 kEqn)", model); return FFM_ERR_ARG; }
+    const int N = P->N, nOwn = P->nOwn, B = P->B;
+    if (model == 1) {
+        if (!(Ck >= 0) || !(Ce >= 0) || !(Prt > 0) || !(kInlet > 0) || !std::isfinite(Ck) || !std::isfinite(Ce) || !std::isfinite(Prt) || !std::isfinite(kInlet)) {
+            ffm_set_error("ffm_plume_set_turbulence: Ck >= 0, Ce >= 0, Prt > 0, kInlet > 0 wanted"); return FFM_ERR_ARG;
+        }
+        if (k0) for (int c = 0; c < nOwn; c++) if (!(k0[c] > 0) || !std::isfinite(k0[c])) {
+            ffm_set_error("ffm_plume_set_turbulence: k0[%d] is not finite and positive", c); return FFM_ERR_ARG;
+        }
+    }
+    PL_HIP(hipSetDevice(P->ctx->device));
+    PL_HIP(hipStreamSynchronize(P->ctx->stream));
+    if (model == 0) {
+        P->turbModel = 0;
+        dfree(P, P->kSgs); dfree(P, P->nut); dfree(P, P->alphat); dfree(P, P->lesDelta);
+        dfree(P, P->kb); dfree(P, P->nutb); dfree(P, P->alphatb); dfree(P, P->refK);
+        for (auto &gc : P->lesG) for (double *&g : gc) dfree(P, g);
+        return FFM_OK;
+    }
+    if (!P->kSgs) {
+        const size_t nPool = P->pool.size();
+        P->kSgs = dalloc(P, N); P->nut = dalloc(P, N); P->alphat = dalloc(P, N); P->lesDelta = dalloc(P, N);
+        P->kb = dalloc(P, B); P->nutb = dalloc(P, B); P->alphatb = dalloc(P, B); P->refK = dalloc(P, B);
+        if (!P->fused) for (auto &gc : P->lesG) for (double *&g : gc) g = dalloc(P, N);
+        if (P->pool.size() != nPool + (P->fused ? 8 : 17)) { ffm_set_error("plume: out of device memory"); return FFM_ERR_HIP; }
+        // delta cubeRootVol, on the host as the oracle forms it
+        std::vector<double> v(N);
+        FFM_TRY(ffm_d2h(P->ctx, v.data(), ffm_mesh_geom(P->mesh, 0), sizeof(double) * N));
+        for (int c = 0; c < N; c++) v[c] = std::cbrt(v[c]);
+        FFM_TRY(ffm_memcpy_h2d(P->ctx, P->lesDelta, v.data(), sizeof(double) * N));
+    }
+    P->Ck = Ck; P->Ce = Ce; P->Prt = Prt; P->kInlet = kInlet;
+    {
+        std::vector<double> v(N, kInlet);
+        if (k0) for (int c = 0; c < nOwn; c++) v[c] = k0[P->newToOld[c]];
+        FFM_TRY(ffm_memcpy_h2d(P->ctx, P->kSgs, v.data(), sizeof(double) * N));
+        if (k0) FFM_TRY(HX(P, P->kSgs));
+    }
+    const double *kind = P->kind_d; double *rK = P->refK;
+    forN(P, B, [=] __device__(long q) { rK[q] = (kind[q] < 0.5 || kind[q] > 1.5) ? kInlet : 0.0; });
+    P->turbModel = 1;
+    FFM_TRY(plume_turbulence_init(P));
+    PL_HIP(hipStreamSynchronize(P->ctx->stream));
+    return FFM_OK;
+}
 extern "C" int ffm_plume_ncells(const ffm_plume *P) { return P ? P->nOwn : FFM_ERR_ARG; }
 extern "C" int ffm_plume_nfaces(const ffm_plume *P) { return P ? P->F : FFM_ERR_ARG; }
 
-// copy a cell field to the host in NATURAL blockMesh cell order; name in rho,p,p_rgh,T,h,K,Ux,Uy,Uz,psi,<specie>
+// copy a cell field to the host in NATURAL blockMesh cell order; name in rho,p,p_rgh,T,h,K,Ux,Uy,Uz,psi,<specie>,
+// and k,nut,alphat with the kEqn model on
 extern "C" int ffm_plume_get_field(ffm_plume *P, const char *name, double *out)
 {
     if (!P || !name || !out) return FFM_ERR_ARG;
@@ -348,6 +406,7 @@ extern "C" int ffm_plume_get_field(ffm_plume *P, const char *name, double *out)
     if (n == "rho") src = P->rho; else if (n == "p") src = P->p; else if (n == "p_rgh") src = P->p_rgh; else if (n == "T") src = P->T;
     else if (n == "h") src = P->hs; else if (n == "K") src = P->K; else if (n == "Ux") src = P->U[0]; else if (n == "Uy") src = P->U[1];
     else if (n == "Uz") src = P->U[2]; else if (n == "psi") src = P->psi; else if (n == "ph_rgh") src = P->ph_rgh;
+    else if (n == "k") src = P->kSgs; else if (n == "nut") src = P->nut; else if (n == "alphat") src = P->alphat;      // (null while the model is off)
     else if (n == "G") src = P->G; else if (n == "ShSu") src = P->radShSu; else if (n == "ShSp") src = P->radShSp; else if (n == "radE") src = P->radE;
     else if (n.size() > 1 && n[0] == 'I' && isdigit((unsigned char)n[1])) { const int i = atoi(n.c_str() + 1); if (i < (int)P->I.size()) src = P->I[i]; }
     else for (int i = 0; i < NSP; i++) if (n == SPN[i]) src = P->Y[i];

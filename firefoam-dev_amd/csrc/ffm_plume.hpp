@@ -112,7 +112,20 @@ struct ffm_plume {
     double *radE = nullptr, *radShSu = nullptr, *radShSp = nullptr; bool radHaveG = false;
     bool stecklerSolvers = false;          // transport equations with smoothSolver + symGaussSeidel, maxIter 10
                                            // (cases/steckler/system/fvSolution:49-62) instead of PBiCGStab + DILU
+    // LES kEqn sub-grid model (ffm_plume_set_turbulence; cases/steckler/constant/turbulenceProperties:18-30): 0 = none, every pointer null
+    int turbModel = 0;
+    double Ck = 0.094, Ce = 1.048, Prt = 1.0, kInlet = 1e-4;
+    double *kSgs = nullptr, *nut = nullptr, *alphat = nullptr, *lesDelta = nullptr;      // cells; delta = cbrt(V)
+    double *kb = nullptr, *nutb = nullptr, *alphatb = nullptr, *refK = nullptr;           // patch faces; kb: k's values after its last solve, before bound()
+    double *lesG[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};   // (ops) grad(U_c)[d]; the fused form has gM[c][d]
+    // Scratch of the model's passes, beside the table above:
+    //   u_eqn: wN[8] rho*nuEff, wN[9-11] div(rho nuEff dev2(T(grad U)))
+    //   standin_combustion (ops): wN[11] alpha + alphat
+    //   k_eqn: wN[5-7] su, su2, sp -> the assembly | wF[0], wB[4] rho*nuEff on faces / patch faces -> | wB[6] rhob | fused: gM[0-2] grad(U), gM[3] grad(k) |
+    //          (ops) wN[8] G, wN[9] divU, wN[10] rho*nuEff, wF[1] rhof, wF[2] phi/rhof, wB[5] phib/rhob, then scalar_transport's own slots
 };
+
+constexpr double K_MIN = 1.0e-15;          // bound(k, kMin): kMin = SMALL
 
 #define PL_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ffm_set_error("%s:%d %s", __FILE__, __LINE__, hipGetErrorString(e_)); return FFM_ERR_HIP; } } while (0)
 
@@ -197,3 +210,5 @@ static inline int solve_named_multi(ffm_plume *P, int n, const char *const *name
 // ffm_plume_rad.hip: radiation->correct() of solver/YEEqn.H:80, and RadFraction of constRadFractionEmission (e_eqn's radiation->Sh wants it too)
 int radiation_correct(ffm_plume *P);
 int plume_rad_fraction(ffm_plume *P, double *out);
+// ffm_plume_step.hip: k's patch values from its condition with the present phib, then bound(k) + correctNut() (ffm_plume_set_turbulence)
+int plume_turbulence_init(ffm_plume *P);

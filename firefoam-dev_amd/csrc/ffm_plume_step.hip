@@ -1,6 +1,8 @@
 // ffm_plume_step.hip -- one fireFoam time step of the plume case (solver/fireFoam.C:76-121 with PIMPLE 1/2/0, cases/steckler/system/
 // fvSolution:84-89) against the C ABI of include/ffm.h: ffm_plume_step at the end of the file is the reference's sequence, one stage per snippet
 //   rhoEqn  solver/rhoEqn.H:33-43      UEqn  solver/UEqn.H:3-33      YEEqn   solver/YEEqn.H:37-118      pEqn  solver/pEqn.H:1-60 (x2)
+//   turbulence->correct()  solver/fireFoam.C:113-116: k_eqn, only with the LES kEqn model selected (ffm_plume_set_turbulence; oracle:
+//   tests/plume_keqn_ref.py); without it the step is the stand-in's constant mu and mu/Pr and launches nothing more than before
 // bench.py's workload and the subject of tests/test_plume_gpu.py (oracle: oracle/plume.py, same sequence in numpy).  A stage whose assembly has
 // a fused pass (ffm_fused.hip) reads P->fused once; its per-operator form, one launch per fvc:: / fvm:: operator (FFM_PLUME_UNFUSED, bitwise
 // equal), is the function <stage>_ops next to it, and what both forms run is in the stage.  Scratch slots: the table in ffm_plume.hpp.
@@ -95,7 +97,9 @@ static int u_buoyancy(ffm_plume *P, double *const rec[3])
 static int u_source_ops(ffm_plume *P, int c)
 {
     ffm_mesh *m = P->mesh; const double rdt = P->rdt; const double *V = ffm_mesh_geom(m, 0);
-    double *gx = P->wN[1], *gy = P->wN[2], *gz = P->wN[3], *corr = P->wF[4], *divc = P->wN[4];
+    // (with the kEqn model the three gradients live on for the stress divergence: u_stress_divergence)
+    double *gx = P->turbModel ? P->lesG[c][0] : P->wN[1], *gy = P->turbModel ? P->lesG[c][1] : P->wN[2], *gz = P->turbModel ? P->lesG[c][2] : P->wN[3];
+    double *corr = P->wF[4], *divc = P->wN[4];
     FFM_TRY(ffm_fvc_grad(m, P->U[c], P->Ub[c], gx, gy, gz));
     FFM_TRY(HX(P, gx)); FFM_TRY(HX(P, gy)); FFM_TRY(HX(P, gz));
     FFM_TRY(ffm_fv_lust_correction(m, P->phi, gx, gy, gz, corr));
@@ -129,6 +133,51 @@ static int u_sources(ffm_plume *P, const double *mub)
     do { int rc_ = ((P)->oneBlock && ffm_tile_coef_direct_ok((P)->A)) ? (direct) : FFM_ERR_UNSUPPORTED; \
          if (rc_ == FFM_ERR_UNSUPPORTED) rc_ = (plain); FFM_TRY(rc_); } while (0)
 
+// ---------------- the kEqn model's parts of UEqn.H and YEEqn.H (ffm_plume_set_turbulence; oracle: tests/plume_keqn_ref.py) ----------
+// the nine cell gradients g[3*i + j] = d_i U_j where the form in use keeps them: gM[c] (fused), lesG[c] (per-operator)
+static void les_gradU(ffm_plume *P, const double *g9[9])
+{ for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) g9[3 * i + j] = P->fused ? P->gM[j][i] : P->lesG[j][i]; }
+
+// rho*nuEff = rho*(nut + mu/rho) with the present rho: linear interpolation -> gf, patch values -> gb (rho_b: the zero-gradient copy).
+// The fused form is one owner-row pass from rho and nut (ffm_les_face_diffusivity); the per-operator form goes through the cell field,
+// which the fused form writes only where a later pass wants it (wantCell: the stress divergence of u_eqn)
+static int les_rho_nuEff_faces(ffm_plume *P, double *gamCell, bool wantCell, double *rhob, double *gf, double *gb)
+{
+    ffm_mesh *m = P->mesh;
+    const double *rho = P->rho, *nut = P->nut, *nutb = P->nutb;
+    zg(P, rhob, rho);
+    if (!P->fused || wantCell) forN(P, P->N, [=] __device__(long i) { gamCell[i] = rho[i] * (nut[i] + MU / rho[i]); });
+    if (P->fused) return ffm_les_face_diffusivity(m, 0, MU, rho, rhob, nut, nutb, gf, gb);
+    FFM_TRY(ffm_fvc_interpolate(m, nullptr, gamCell, gf));
+    forN(P, P->B, [=] __device__(long k) { gb[k] = rhob[k] * (nutb[k] + MU / rhob[k]); });
+    return FFM_OK;
+}
+
+// turbulence->divDevRhoReff(U), explicit part (solver/UEqn.H:7): Usrc_c += V*fvc::div(rho nuEff dev2(T(grad U)))_c from the gradients
+// u_sources formed for LUST and U's patch values; the same two launches in both forms
+static int u_stress_divergence(ffm_plume *P, const double *gam, const double *gamb)
+{
+    const double *g9[9]; les_gradU(P, g9);
+    const double *U[3] = {P->U[0], P->U[1], P->U[2]}, *Ub[3] = {P->Ub[0], P->Ub[1], P->Ub[2]};
+    double *dv[3] = {P->wN[9], P->wN[10], P->wN[11]};
+    FFM_TRY(ffm_fvc_div_dev2T_gradU(P->mesh, g9, gam, gamb, U, Ub, dv));
+    const double *V = ffm_mesh_geom(P->mesh, 0), *d0 = dv[0], *d1 = dv[1], *d2 = dv[2]; double *s0 = P->Usrc[0], *s1 = P->Usrc[1], *s2 = P->Usrc[2];
+    forN(P, P->nOwn, [=] __device__(long i) { s0[i] = s0[i] + V[i] * d0[i]; s1[i] = s1[i] + V[i] * d1[i]; s2[i] = s2[i] + V[i] * d2[i]; });
+    return FFM_OK;
+}
+
+// turbulence->alphaEff() (solver/YEEqn.H:12): alpha + alphat with the alphat of the last correctNut(), one diffusivity for species and h
+static int les_alpha_eff(ffm_plume *P)
+{
+    ffm_mesh *m = P->mesh;
+    double *af = P->alphaEff_f, *afb = P->alphaEff_b, *a = P->wN[11]; const double *alphat = P->alphat, *alphatb = P->alphatb;
+    if (P->fused) return ffm_les_face_diffusivity(m, 1, MU / PR, nullptr, nullptr, alphat, alphatb, af, afb);
+    forN(P, P->N, [=] __device__(long i) { a[i] = MU / PR + alphat[i]; });
+    FFM_TRY(ffm_fvc_interpolate(m, nullptr, a, af));
+    forN(P, P->B, [=] __device__(long k) { afb[k] = MU / PR + alphatb[k]; });
+    return FFM_OK;
+}
+
 static int u_eqn(ffm_plume *P)
 {
     ffm_mesh *m = P->mesh; const int N = P->N; const bool ops = !P->fused;
@@ -138,13 +187,18 @@ static int u_eqn(ffm_plume *P)
     // div(phi,U) Gauss LUST grad(U) (cases/steckler/system/fvSchemes:32): LUST weights for the implicit part -- a function of phi and the
     // mesh weights alone, formed inside the assembly pass by the fused form; the explicit correction goes into the source (u_sources)
     if (ops) FFM_TRY(ffm_fv_limited_weights(m, 4, 1.0, 0.0, 1.0, P->phi, nullptr, nullptr, nullptr, nullptr, wU));
-    forN(P, P->nNat, [=] __device__(long e) { muf[e] = MU; });
-    forN(P, P->B, [=] __device__(long k) { mub[k] = MU; });
+    double *gam = P->wN[8];         // kEqn: rho*nuEff on the cells, for the stress divergence (wB[6] is u_buoyancy's rhob next)
+    if (P->turbModel) FFM_TRY(les_rho_nuEff_faces(P, gam, true, P->wB[6], muf, mub));
+    else {
+        forN(P, P->nNat, [=] __device__(long e) { muf[e] = MU; });
+        forN(P, P->B, [=] __device__(long k) { mub[k] = MU; });
+    }
     if (ops) FFM_TRY(ffm_fvm_transport(m, P->rdt, P->rho, P->phi, wU, muf, -1, P->Udiag, P->Uupper, P->Ulower));
     else DIRECT_OR(P, ffm_fvm_transport_scheme_direct(m, P->rdt, P->rho, P->phi, 4, muf, -1, P->Udiag, P->Uupper, P->Ulower),
                    ffm_fvm_transport_scheme(m, P->rdt, P->rho, P->phi, 4, muf, -1, P->Udiag, P->Uupper, P->Ulower));
     FFM_TRY(u_buoyancy(P, rec));
     FFM_TRY(u_sources(P, mub));
+    if (P->turbModel) FFM_TRY(u_stress_divergence(P, gam, mub));
     // fvMatrix::solveSegregated: the three components share the face coefficients -- one lock-step solve (ffm_solve_multi_d).
     // UdW = Udiag + sum ic, UsW = Usrc + sum bc + V*rec; Usrc, Uic and Ubc stay as they are for the correctors.  The fused form: one
     // cell pass from rho, p_rgh and u_buoyancy's patch part, no face flux and no rec (a hex block's rows have at most 6 entries, see
@@ -164,8 +218,10 @@ static int u_eqn(ffm_plume *P)
 static void standin_combustion(ffm_plume *P)
 {
     double *af = P->alphaEff_f, *afb = P->alphaEff_b, *wFuel = P->wFuel, *Qdot = P->Qdot, *Yt = P->Yt;
-    forN(P, P->nNat, [=] __device__(long e) { af[e] = 0.5 * (MU / PR) + (1.0 - 0.5) * (MU / PR); });
-    forN(P, P->B, [=] __device__(long k) { afb[k] = MU / PR; });
+    if (!P->turbModel) {            // (kEqn: les_alpha_eff, called next)
+        forN(P, P->nNat, [=] __device__(long e) { af[e] = 0.5 * (MU / PR) + (1.0 - 0.5) * (MU / PR); });
+        forN(P, P->B, [=] __device__(long k) { afb[k] = MU / PR; });
+    }
     const double *rho = P->rho, *fuel = P->Y[2], *o2 = P->Y[0];
     // (the per-operator species loop sums Yt as it goes and wants it zero)
     if (P->fused) forN(P, P->N, [=] __device__(long i) { const double w = rho[i] * fmin(fuel[i], o2[i] / S_O2) / TAU; wFuel[i] = w; Qdot[i] = w * HC; });
@@ -233,14 +289,15 @@ static int mv_weights(ffm_plume *P)
 // terms in `expl`); convected with the weights wGiven, or with those of its own limiter where wGiven is null
 static int scalar_transport(ffm_plume *P, const char *name, int scheme, double *vf, const double *vf0, const double *fBC, const double *ref,
                             const double *gamma_f, const double *gamma_b, const double *su, const double *const *expl, double tol,
-                            const double *su2, const double *sp, const double *wGiven)
+                            const double *su2, const double *sp, const double *wGiven, const double *vbStored = nullptr)
 {
     ffm_mesh *m = P->mesh; const int N = P->N;
     double *vb = P->wB[2], *gx = P->wN[1], *gy = P->wN[2], *gz = P->wN[3], *wOwn = P->wF[3], *sSu = P->wN[4];
     const double *w = wGiven;
     if (!wGiven) {
-        FFM_TRY(ffm_bc_values(m, fBC, ref, P->zeroB, vf, vb));
-        FFM_TRY(ffm_fvc_grad(m, vf, vb, gx, gy, gz));
+        // (vbStored: the field keeps the patch values of its last evaluation -- k -- instead of evaluating its condition again)
+        if (!vbStored) FFM_TRY(ffm_bc_values(m, fBC, ref, P->zeroB, vf, vb));
+        FFM_TRY(ffm_fvc_grad(m, vf, vbStored ? vbStored : vb, gx, gy, gz));
         FFM_TRY(HX(P, gx)); FFM_TRY(HX(P, gy)); FFM_TRY(HX(P, gz));
         FFM_TRY(ffm_fv_limited_weights(m, scheme, 1.0, 0.0, 1.0, P->phi, vf, gx, gy, gz, wOwn));
         w = wOwn;
@@ -643,6 +700,90 @@ static int p_corrector(ffm_plume *P, bool final)
     return pc_flux_U(P, w);
 }
 
+// ---------------- turbulence->correct() (solver/fireFoam.C:113-116): kEqn::correct
+// bound(k, kMin) and correctNut(): nut = Ck sqrt(k) delta, alphat = rho nut/Prt with the present rho, over the ghost cells too (k and rho
+// are refreshed there and delta is theirs: the values a refresh of nut and alphat would bring); then the patch values, zeroGradient
+// and 0 on the floor.  The fused form is one cell pass (ffm_les_keqn_update)
+static int correct_nut(ffm_plume *P)
+{
+    double *k = P->kSgs, *nut = P->nut, *alphat = P->alphat, *nutb = P->nutb, *alphatb = P->alphatb;
+    if (P->fused) FFM_TRY(ffm_les_keqn_update(P->mesh, P->N, K_MIN, P->Ck, P->Prt, k, P->lesDelta, P->rho, nut, alphat));
+    else {
+        forN(P, P->N, [=] __device__(long i) { k[i] = fmax(k[i], K_MIN); });
+        FFM_TRY(ffm_les_keqn_nut_d(P->ctx, P->N, P->Ck, P->Prt, k, P->lesDelta, P->rho, nut, alphat));
+    }
+    const int *fc = ffm_mesh_bcells(P->mesh); const double *kind = P->kind_d;
+    forN(P, P->B, [=] __device__(long q) {
+        const bool floor = kind[q] > 0.5 && kind[q] < 1.5;
+        nutb[q] = floor ? 0.0 : nut[fc[q]]; alphatb[q] = floor ? 0.0 : alphat[fc[q]];
+    });
+    return FFM_OK;
+}
+
+int plume_turbulence_init(ffm_plume *P)
+{
+    bc_update_f(P, P->fS, P->fStaticS);
+    FFM_TRY(ffm_bc_values(P->mesh, P->fS, P->refK, P->zeroB, P->kSgs, P->kb));
+    return correct_nut(P);
+}
+
+// divU = surfaceIntegrate(phi/interpolate(rho)), G = nut (grad U && dev(twoSymm(grad U))) and the three source arrays, one operator per launch
+static int k_eqn_terms_ops(ffm_plume *P, const double *const *g9, const double *rhob, double *su, double *su2, double *sp)
+{
+    ffm_mesh *m = P->mesh;
+    double *G = P->wN[8], *divU = P->wN[9], *rhof = P->wF[1], *pr = P->wF[2], *prb = P->wB[5];
+    const double *phi = P->phi, *phib = P->phib, *rho = P->rho, *k = P->kSgs, *delta = P->lesDelta; const double Ce = P->Ce;
+    FFM_TRY(ffm_fvc_interpolate(m, nullptr, rho, rhof));
+    forN(P, P->nNat, [=] __device__(long e) { pr[e] = phi[e] / rhof[e]; });
+    forN(P, P->B, [=] __device__(long q) { prb[q] = phib[q] / rhob[q]; });
+    FFM_TRY(ffm_fvc_surface_integrate(m, pr, prb, divU));
+    FFM_TRY(ffm_les_keqn_G(m, g9, P->nut, G));
+    forN(P, P->nOwn, [=] __device__(long i) { su[i] = rho[i] * G[i]; });
+    forN(P, P->nOwn, [=] __device__(long i) { const double ss = (2.0 / 3.0) * rho[i] * divU[i]; su2[i] = -(fmin(ss, 0.0) * k[i]); });
+    forN(P, P->nOwn, [=] __device__(long i) { const double ss = (2.0 / 3.0) * rho[i] * divU[i]; sp[i] = fmax(ss, 0.0) + Ce * rho[i] * sqrt(k[i]) / delta[i]; });
+    return FFM_OK;
+}
+
+// ddt(rho,k) + div(phi,k) [Gauss limitedLinear 1, the limiter from grad(k) with k's stored patch values] - laplacian(rho nuEff, k)
+//   == rho G - SuSp(2/3 rho divU, k) - Sp(Ce rho sqrt(k)/delta, k);  bound(k, SMALL);  correctNut()
+// after the second corrector, with its phi, U and rho (rhoEqn.H's, before rho = thermo.rho()) and the nut of the last correctNut().  k's
+// condition is the species' pattern (fS).  The fused form: the explicit terms in one owner-row pass (ffm_les_keqn_terms), the face
+// diffusivity in one (ffm_les_face_diffusivity), the assembly in one (ffm_fvm_scalar_transport_multi, as e_eqn with a limiter of its own).
+// grad(U) is read at a row's own cell only and is not refreshed; grad(k) and k are
+static int k_eqn(ffm_plume *P)
+{
+    ffm_mesh *m = P->mesh; const bool ops = !P->fused;
+    double *su = P->wN[5], *su2 = P->wN[6], *sp = P->wN[7], *Dkf = P->wF[0], *Dkb = P->wB[4], *rhob = P->wB[6], *k = P->kSgs;
+    FFM_TRY(update_bcs(P));
+    FFM_TRY(U_boundary(P));
+    const double *g9[9]; les_gradU(P, g9);
+    if (ops) { for (int c = 0; c < 3; c++) FFM_TRY(ffm_fvc_grad(m, P->U[c], P->Ub[c], P->lesG[c][0], P->lesG[c][1], P->lesG[c][2])); }
+    else {
+        const double *uf[3] = {P->U[0], P->U[1], P->U[2]}, *ub[3] = {P->Ub[0], P->Ub[1], P->Ub[2]};
+        double *ggx[3] = {P->gM[0][0], P->gM[1][0], P->gM[2][0]}, *ggy[3] = {P->gM[0][1], P->gM[1][1], P->gM[2][1]}, *ggz[3] = {P->gM[0][2], P->gM[1][2], P->gM[2][2]};
+        FFM_TRY(ffm_fvc_grad_multi(m, 3, uf, ub, ggx, ggy, ggz));
+    }
+    FFM_TRY(les_rho_nuEff_faces(P, P->wN[10], false, rhob, Dkf, Dkb));
+    if (ops) FFM_TRY(k_eqn_terms_ops(P, g9, rhob, su, su2, sp));
+    else FFM_TRY(ffm_les_keqn_terms(m, g9, P->nut, P->rho, rhob, k, P->lesDelta, P->phi, P->phib, P->Ce, su, su2, sp));
+    if (ops) FFM_TRY(scalar_transport(P, "k", 2, k, k, P->fS, P->refK, Dkf, Dkb, su, nullptr, 1e-8, su2, sp, nullptr, P->kb));
+    else {
+        const double *vf[1] = {k}, *vb[1] = {P->kb}, *fq[1] = {P->fS}, *rq[1] = {P->refK}, *gq[1] = {P->zeroB}, *suq[1] = {su}, *su2q[1] = {su2}, *spq[1] = {sp};
+        double *ggx[1] = {P->gM[3][0]}, *ggy[1] = {P->gM[3][1]}, *ggz[1] = {P->gM[3][2]};
+        const double *cgx[1] = {ggx[0]}, *cgy[1] = {ggy[0]}, *cgz[1] = {ggz[0]};
+        double *dd[1] = {P->dWork}, *uu[1] = {P->upper}, *ll[1] = {P->lower}, *ss[1] = {P->sWork};
+        FFM_TRY(ffm_fvc_grad_multi(m, 1, vf, vb, ggx, ggy, ggz));
+        FFM_TRY(HX(P, ggx[0])); FFM_TRY(HX(P, ggy[0])); FFM_TRY(HX(P, ggz[0]));
+        // (the old-time k is k itself until the solve: nothing has written it since the last step's correct())
+        FFM_TRY(ffm_fvm_scalar_transport_multi(m, 1, 2, 1.0, 0.0, 1.0, P->rdt, P->rho, P->rho0, P->phi, P->phib, Dkf, Dkb, vf, cgx, cgy, cgz, vf,
+                                               fq, rq, gq, suq, su2q, spq, nullptr, dd, uu, ll, ss));
+        FFM_TRY(solve_named(P, "k", FFM_PBICGSTAB, FFM_DILU, 1e-8, 0.0, P->dWork, P->upper, P->lower, k, P->sWork));
+        FFM_TRY(HX(P, k));
+    }
+    FFM_TRY(ffm_bc_values(m, P->fS, P->refK, P->zeroB, k, P->kb));
+    return correct_nut(P);
+}
+
 extern "C" int ffm_plume_step(ffm_plume *P)
 {
     if (!P) return FFM_ERR_ARG;
@@ -652,6 +793,7 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     FFM_TRY(rho_eqn(P));
     FFM_TRY(u_eqn(P));
     standin_combustion(P);
+    if (P->turbModel) FFM_TRY(les_alpha_eff(P));
     FFM_TRY(mv_weights(P));
     bool spOffDiagBound;
     const bool radNow = P->radFreq > 0 && P->stepNo % P->radFreq == 0;
@@ -662,6 +804,7 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     standin_thermo(P);
     FFM_TRY(p_corrector(P, false));
     FFM_TRY(p_corrector(P, true));
+    if (P->turbModel) FFM_TRY(k_eqn(P));
     mul(P, P->rho, P->psi, P->p, P->N);
     P->time += P->dt; P->stepNo++;
     PL_HIP(hipStreamSynchronize(P->ctx->stream));

@@ -668,6 +668,25 @@ int ffm_plume_set_tight(ffm_plume *p, int on);
 /* linear solvers of the transport equations (U, Yi, h): 0 = PBiCGStab + DILU (default, the kernels BASELINE names),
  * 1 = smoothSolver + symGaussSeidel with maxIter 10, the selection of cases/steckler/system/fvSolution:49-62 */
 int ffm_plume_set_solvers(ffm_plume *plume, int stecklerSelection);
+/* The sub-grid model of the step: 0 none (default: constant mu and mu/Pr, as before), 1 the LES kEqn model with delta cubeRootVol that
+ * every BASELINE case selects (cases/steckler/constant/turbulenceProperties:18-30).  With model 1
+ *   UEqn   (solver/UEqn.H:7, turbulence->divDevRhoReff(U)): - fvm::laplacian(rho nuEff, U) - fvc::div(rho nuEff dev2(T(grad U))),
+ *          rho nuEff = rho (nut + mu/rho);
+ *   YEEqn  (solver/YEEqn.H:12, turbulence->alphaEff()): alpha + alphat for the species and h;
+ *   turbulence->correct() after the second pressure corrector (solver/fireFoam.C:113-116): kEqn::correct -- ddt(rho,k) + div(phi,k)
+ *          [limitedLinear 1] - laplacian(rho nuEff, k) == rho G - SuSp(2/3 rho divU, k) - Sp(Ce rho sqrt(k)/delta, k), solved by the
+ *          selection and tolerance of h (one more solve-log entry "k" after the second p_rgh), bound(k, SMALL), correctNut():
+ *          nut = Ck sqrt(k) delta, alphat = rho nut/Prt.
+ * Patches: k fixed kInlet on the inlet, inletOutlet(kInlet) on top / sides, zeroGradient on the floor; nut and alphat zeroGradient,
+ * 0 on the floor.  k0: host, the start value of k per owned cell in the cell order ffm_plume_set_initial_state takes its fields in
+ * (a block's own natural order on a decomposed box), or NULL for kInlet everywhere.  Callable between steps (and after
+ * ffm_plume_set_initial_state, which it does not follow); model 1 evaluates correctNut() once with the current rho, model 0 releases
+ * the model's fields: the step is then the code and the launches of a handle that never had it.  FFM_ERR_ARG with the handle
+ * unchanged: an unknown model, Ck < 0, Ce < 0, Prt <= 0, kInlet <= 0, a k0 entry that is not finite and positive.  Fields "k", "nut",
+ * "alphat" become readable with ffm_plume_get_field while the model is on.  Parity of the plume with kEqn is unpinned by reference
+ * data, as the plume itself is: the check is oracle/steckler_case.py's kEqn restated on the plume box (tests/plume_keqn_ref.py).  */
+int ffm_plume_set_turbulence(ffm_plume *plume, int model /* 0 none (default), 1 kEqn */, double Ck, double Ce, double Prt, double kInlet,
+                             const double *k0);
 /* SURVEY 8(f) N1 stand-in: the reference's radiation->correct() (solver/YEEqn.H:80; fvDOM with nPhi 2, nTheta 4, solverFreq 100,
  * cases/steckler/constant/radiationProperties:32-40) as 4*nPhi*nTheta upwind ray-transport solves every `solverFreq` steps
  * (0 = off, the default).  dAve[3*nRay], omega[nRay]: the rays' mean directions and solid angles as fvDOM.C:55-90 builds
@@ -842,6 +861,23 @@ int ffm_les_keqn_nut_d(ffm_ctx *ctx, long n, double Ck, double Prt, const double
 int ffm_fvc_div_dev2T_gradU(ffm_mesh *m, const double *const *g, const double *gamma, const double *gamma_b,
                             const double *const *U, const double *const *U_b, double *const *out);
 int ffm_les_keqn_G(ffm_mesh *m, const double *const *g, const double *nut, double *G);
+/* kEqn in the compiled time step (ffm_plume_set_turbulence), row kernels of ffm_fused.hip:
+ * ffm_les_keqn_terms: the explicit terms of kEqn::correct in one owner-row pass -- divU = fvc::surfaceIntegrate(phi/interpolate(rho))
+ *   (rho_b: patch values of rho), G as ffm_les_keqn_G, and the arrays a scalar transport assembly (ffm_fvm_scalar_transport_multi) takes
+ *   as su / su2 / sp:  su = rho G,  su2 = -(min(s,0) k),  sp = max(s,0) + Ce rho sqrt(k)/delta  with  s = (2/3) rho divU,  i.e.
+ *   rho G - fvm::SuSp(s, k) - fvm::Sp(Ce rho sqrt(k)/delta, k).  Bitwise equal to ffm_fvc_interpolate, the quotient, ffm_fvc_surface_integrate,
+ *   ffm_les_keqn_G and the cell algebra in that order.
+ * ffm_les_face_diffusivity: out_f = linear interpolation, out_b = patch values of a cell expression formed on the fly, no cell field:
+ *   mode 0  rho*(x + c0/rho)  (rho nuEff: x = nut, c0 = mu; patch rho_b*(x_b + c0/rho_b));  mode 1  c0 + x  (alphaEff: x = alphat, c0 =
+ *   alpha; rho, rho_b not read).  Bitwise equal to the cell expression + ffm_fvc_interpolate(NULL, .).
+ * ffm_les_keqn_update: bound(k, kMin) and kEqn::correctNut on the first n cells: k = max(k, kMin), nut = Ck sqrt(k) delta,
+ *   alphat = rho nut/Prt (ffm_les_keqn_nut_d's expressions). */
+int ffm_les_keqn_terms(ffm_mesh *m, const double *const *g, const double *nut, const double *rho, const double *rho_b, const double *k,
+                       const double *delta, const double *phi_f, const double *phi_b, double Ce, double *su, double *su2, double *sp);
+int ffm_les_face_diffusivity(ffm_mesh *m, int mode, double c0, const double *rho, const double *rho_b, const double *x, const double *x_b,
+                             double *out_f, double *out_b);
+int ffm_les_keqn_update(ffm_mesh *m, long n, double kMin, double Ck, double Prt, double *k, const double *delta, const double *rho,
+                        double *nut, double *alphat);
 
 /* ------------------------------------------------------------------------ GAMG */
 /* pairGAMGAgglomeration::forward_ is a static upstream: the cell-visiting direction of the next pair agglomeration, toggled by every
