@@ -307,6 +307,7 @@ def lib():
         "ffm_renumber_hint": ([C.c_int, C.c_int, C.c_int, ip, ip, ip, ip, ip], C.c_int),
         "ffm_ldu_create_ext": ([vp, C.c_int, C.c_int, C.c_int, ip, ip, C.POINTER(vp)], C.c_int),
         "ffm_renumber_levels_ext": ([C.c_int, C.c_int, C.c_int, ip, ip, ip, ip], C.c_int),
+        "ffm_ldu_check_layout": ([C.c_int, C.c_int, C.c_int, ip, ip], C.c_int),
         "ffm_ldu_set_ghost_exchange": ([vp, C.c_int, ip, ip, ip, ip], C.c_int),
         "ffm_halo_refresh_d": ([vp, dp], C.c_int),
         "ffm_ldu_nowned": ([vp], C.c_int),
@@ -438,6 +439,15 @@ def renumber_levels(nCells, lowerAddr, upperAddr, groupHint=None, nGhost=0):
         gh = np.ascontiguousarray(groupHint, np.int32)
         _check(lib().ffm_renumber_hint(nCells, nGhost, len(l), _ip(l), _ip(u), _ip(gh), _ip(c2), _ip(f2)), "ffm_renumber_hint")
     return c2, f2
+
+
+def check_layout(nCells, lowerAddr, upperAddr, nGhost=0):
+    """Would lduMatrix accept this addressing?  Pure host code in libffm (ffm_ldu_check_layout), no device: returns
+    (code, message), (0, "") where the row layout holds the matrix."""
+    l = np.ascontiguousarray(lowerAddr, np.int32)
+    u = np.ascontiguousarray(upperAddr, np.int32)
+    rc = lib().ffm_ldu_check_layout(nCells, nGhost, len(l), _ip(l), _ip(u))
+    return rc, (lib().ffm_last_error().decode() if rc else "")
 
 
 class Context:

@@ -133,6 +133,7 @@ __device__ __forceinline__ void run_scal_op(double *scal, const ffm_scal_op &t)
 // Passed by value to every kernel that walks matrix rows (layout: ffm_internal.hpp).
 struct LduView {
     int N;                      // number of ROWS (owned cells); column indices may reach the ghost cells beyond
+    int loShift;                // bits of the slot field of a lower entry (4, or 5 for a matrix with more than 16 owned upper faces in a row)
     const int *upOff, *loOff;   // [nSlices+1]
     const int *upNbr;           // [upTotal]
     const int *loEnt;           // [loTotal]
@@ -170,8 +171,8 @@ __device__ __forceinline__ void load_lower(const LduView &v, int c, RowEnt<W> &R
 #pragma unroll
     for (int s = 0; s < W; s++) {
         R.on[s] = e[s] >= 0;
-        R.nb[s] = R.on[s] ? (e[s] >> 4) : c;
-        R.f[s] = R.on[s] ? face_of(v, R.nb[s], e[s] & 15) : 0;
+        R.nb[s] = R.on[s] ? (e[s] >> v.loShift) : c;
+        R.f[s] = R.on[s] ? face_of(v, R.nb[s], (int)__builtin_amdgcn_ubfe((unsigned)e[s], 0u, (unsigned)v.loShift)) : 0;   // the low loShift bits
     }
 }
 

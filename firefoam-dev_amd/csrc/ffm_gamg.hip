@@ -127,7 +127,7 @@ void agglomerate_addressing(const std::vector<int> &l, const std::vector<int> &u
     std::vector<int> fmap(nCF);
     int k = 0;
     // decomposed levels (nCoarseOwned given): the faces of an owner towards OWNED cells first, then its cut faces towards ghost cells, each
-    // group in order of discovery -- the layout of every decomposed ffm_ldu (the packed lower entries need the owned faces in the first 16 slots)
+    // group in order of discovery -- the layout of every decomposed ffm_ldu (only the owned faces have packed lower entries: up to 16 of them keep the slot field at four bits)
     for (int c = 0; c < nCoarse; c++) for (int pass = 0; pass < (nCoarseOwned >= 0 ? 2 : 1); pass++) for (int i = 0; i < cCellnFaces[c]; i++) {
         const int cf = cCellFaces[(size_t)maxN * c + i];
         if (nCoarseOwned >= 0 && (initNbr[cf] >= nCoarseOwned) != (pass == 1)) continue;
@@ -399,8 +399,13 @@ extern "C" int ffm_gamg_create(ffm_ctx *ctx, ffm_ldu *finest, int nCells, int nF
         }
         else if (!hint.empty()) rc = ffm_ldu_create_hint(ctx, nCoarse, 0, nCF, cl.data(), cu.data(), hint.data(), &Ac);
         else rc = ffm_ldu_create(ctx, nCoarse, nCF, cl.data(), cu.data(), &Ac);
-        if (rc) return fail(rc);
-        if (Ac->sweepMode != 2) hint.clear();           // the planner gave up here: no tiles further down either
+        if (rc) {
+            // (a level the row layout cannot hold -- more than 32 faces on one side of a coarse cell -- is the caller's to know by name)
+            const std::string why = ffm_last_error();
+            ffm_set_error("GAMG coarse level %d (%d cells): %s", k + 1, nCoarse, why.c_str());
+            return fail(rc);
+        }
+        if (Ac->sweepMode != 2) hint.clear();          // the planner gave up here: no tiles further down either
         if (getenv("FFM_VERBOSE")) fprintf(stderr, "ffm gamg: coarse level %d: %d cells (+ %d ghost), %s sweeps\n", k + 1, nCoarse, nCoarseGhost, Ac->sweepMode == 2 ? "tiled" : "level-scheduled");
         G->lev.emplace_back();
         Level &Lf = G->lev[k], &Lc = G->lev[k + 1];

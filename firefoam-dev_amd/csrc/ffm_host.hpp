@@ -75,6 +75,7 @@ struct LduAnalysis {
 struct LduLayout {
     int nSlices = 0, upTotal = 0, loTotal = 0;
     int upWidthUniform = -1, loWidthUniform = -1, maxW = 0;
+    int loShift = 4;                             // bits of the slot field of loEnt: 4, or 5 where a cell owns more than 16 faces towards owned cells
     std::vector<int> upOff, loOff;               // [nSlices+1]
     std::vector<int> upNbr, faceSrc;             // [max(upTotal, 1)]
     std::vector<int> loEnt;                      // [max(loTotal, 1)]

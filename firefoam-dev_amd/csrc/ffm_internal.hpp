@@ -152,14 +152,17 @@ struct ffm_ldu {
     //       upper[e] / lower[e] = the face's upper / lower coefficient (0 on padding)
     //     e is the library's NATIVE FACE INDEX; the owner of a native face is implicit.
     //   lower part: entry q = loOff[sl] + s*64 + lane
-    //       loEnt[q] = (owner cell << 4) | slot of that face in the owner's row  (-1 = padding)
-    //     listing the faces whose NEIGHBOUR is the cell, in the caller's face order.
+    //       loEnt[q] = (owner cell << loShift) | slot of that face in the owner's row  (-1 = padding)
+    //     listing the faces whose NEIGHBOUR is the cell, in the caller's face order.  loShift is 4 unless some cell owns more than
+    //     16 faces towards owned cells (wide coarse GAMG levels): then 5, and the matrix may have 2^26 cells instead of 2^27
+    //     (ffm_ldu_analysis.cpp: check_layout_limits).  Every decoder takes the shift from the handle or from LduView.
     // Every load of an index or coefficient array is unit-stride across the wave; the symmetric
     // coefficient is stored once and re-read through the (nbr, slot) pair by the neighbour row.
     int nSlices = 0, upTotal = 0, loTotal = 0;
     int upWidthUniform = -1;                     // >= 0: every slice has this upper width
     int loWidthUniform = -1;
     int maxW = 0;                                // max slots (lower or upper) of any row
+    int loShift = 4;                             // bits of the slot field of loEnt
     int *upOff = nullptr, *loOff = nullptr;      // [nSlices+1]
     int *upNbr = nullptr;                        // [upTotal]
     int *loEnt = nullptr;                        // [loTotal]

@@ -131,7 +131,7 @@ static int ldu_create_impl(ffm_ctx *ctx, int nOwn, int nGhost, int F, const int 
     A->nLevels = std::max((int)a.fwdLevelStart.size() - 1, 0);
     A->h_newToOldCell = a.newToOldCell; A->h_newToOldFace = a.newToOldFace;
     A->nSlices = L.nSlices; A->upTotal = L.upTotal; A->loTotal = L.loTotal;
-    A->upWidthUniform = L.upWidthUniform; A->loWidthUniform = L.loWidthUniform; A->maxW = L.maxW;
+    A->upWidthUniform = L.upWidthUniform; A->loWidthUniform = L.loWidthUniform; A->maxW = L.maxW; A->loShift = L.loShift;
     A->h_upOff = L.upOff; A->h_loOff = L.loOff;
     A->h_callerToNative = std::move(L.callerToNative);
     const int rc = ldu_upload(A, a, L);
@@ -329,7 +329,7 @@ extern "C" unsigned long ffm_ldu_offdiag_epoch(const ffm_ldu *A) { return A ? A-
 
 LduView ffm_view(const ffm_ldu *A)
 {
-    LduView v; v.N = A->nOwned; v.upOff = A->upOff; v.loOff = A->loOff; v.upNbr = A->upNbr; v.loEnt = A->loEnt;
+    LduView v; v.N = A->nOwned; v.upOff = A->upOff; v.loOff = A->loOff; v.upNbr = A->upNbr; v.loEnt = A->loEnt; v.loShift = A->loShift;
     v.upW = A->upWidthUniform; v.loW = A->loWidthUniform; v.sched = A->rowSched; v.nSched = A->nSched;
     return v;
 }

@@ -600,14 +600,17 @@ static void slice_widths(const LduAnalysis &a, int nOwn, int N, int F, int nSl, 
         for (int c = sl * 64; c < std::min(nOwn, sl * 64 + 64); c++) { wu[sl] = std::max(wu[sl], upCnt[c]); wl[sl] = std::max(wl[sl], loCnt[c]); }
 }
 
-// What the sliced layout cannot hold.  At most 32 upper and 32 lower faces per cell (the widest instantiation of the row kernels); the
-// packed entries are int32; of the upper faces, those towards OWNED cells must sit in the first 16 slots (a lower entry packs
-// owner << 4 | slot) -- the faces towards ghost cells, which follow them in a decomposed matrix and have no lower entry, may use the
-// slots above (coarse GAMG levels at rank boundaries).
-static int check_layout_limits(const LduAnalysis &a, int nOwn, int N, int F, const std::vector<int> &wu, const std::vector<int> &wl)
+// What the sliced layout cannot hold, and the width of the slot field of the packed lower entries (loShift).  At most 32 upper and 32
+// lower faces per cell (the widest instantiation of the row kernels).  The packed entries are int32: a lower entry packs
+// owner << loShift | slot.  Four bits hold the slot of every face that an owned cell reads through a lower entry unless some cell owns
+// more than 16 faces towards OWNED cells (coarse GAMG levels of polyhedral and unstructured meshes): such a matrix takes five bits, and
+// only such a matrix is limited to 2^26 cells instead of 2^27.  The faces towards ghost cells, which follow the owned ones in a
+// decomposed matrix and have no lower entry, never count: they may use the slots above 16 of a four-bit matrix.
+static int check_layout_limits(const LduAnalysis &a, int nOwn, int N, int F, const std::vector<int> &wu, const std::vector<int> &wl, int &loShift)
 {
     const int nSl = (int)wu.size();
     int widest = 0;
+    loShift = 4;
     for (int sl = 0; sl < nSl; sl++) {
         if (wu[sl] > 32 || wl[sl] > 32) { ffm_set_error("a cell has %d upper / %d lower faces (> 32): not supported by the sliced layout", wu[sl], wl[sl]); return FFM_ERR_UNSUPPORTED; }
         widest = std::max(widest, wu[sl]);
@@ -617,7 +620,11 @@ static int check_layout_limits(const LduAnalysis &a, int nOwn, int N, int F, con
     int prev = -1, slot = 0;
     for (int f = 0; f < F; f++) {
         slot = (a.l[f] == prev) ? slot + 1 : 0; prev = a.l[f];
-        if (slot >= 16 && a.u[f] < nOwn) { ffm_set_error("a cell owns more than 16 faces towards owned cells (or they follow its faces towards ghost cells): not supported by the packed layout"); return FFM_ERR_UNSUPPORTED; }
+        if (slot >= 16 && a.u[f] < nOwn) { loShift = 5; break; }
+    }
+    if (loShift == 5 && N >= (1 << 26)) {
+        ffm_set_error("mesh too large for int32 packed entries: a cell owns more than 16 faces towards owned cells, which limits the matrix to 2^26 cells");
+        return FFM_ERR_UNSUPPORTED;
     }
     return FFM_OK;
 }
@@ -646,7 +653,7 @@ static void fill_entries(const LduAnalysis &a, int nOwn, int N, int F, LduLayout
     L.upNbr.assign(std::max(L.upTotal, 1), -1); L.faceSrc.assign(std::max(L.upTotal, 1), -1); L.loEnt.assign(std::max(L.loTotal, 1), -1);
     L.callerToNative.assign(F, -1);
     // upper slots: faces of one owner are consecutive in a.l (owner-sorted), caller order inside (check_layout_limits walks the slots
-    // the same way for the 16-slot rule of the packed lower entries: change the slot order in both)
+    // the same way to choose the width of the slot field of the packed lower entries: change the slot order in both)
     std::vector<int> slotOfFace(F);
     int prev = -1, slot = 0;
     for (int f = 0; f < F; f++) {
@@ -665,7 +672,7 @@ static void fill_entries(const LduAnalysis &a, int nOwn, int N, int F, LduLayout
         const int f = oldToNewFace[of], c = a.u[f];
         if (c >= nOwn) continue;                      // ghost cells have no rows
         const int q = L.loOff[c >> 6] + fill[c]++ * 64 + (c & 63);
-        L.loEnt[q] = (a.l[f] << 4) | slotOfFace[f];
+        L.loEnt[q] = (a.l[f] << L.loShift) | slotOfFace[f];
     }
 }
 
@@ -701,9 +708,22 @@ int ffm_ldu_layout(const LduAnalysis &a, int nOwn, int nGhost, int F, LduLayout 
     const int N = nOwn + nGhost, nSl = (nOwn + 63) / 64;
     std::vector<int> wu, wl;
     slice_widths(a, nOwn, N, F, nSl, wu, wl);
-    FFM_TRY(check_layout_limits(a, nOwn, N, F, wu, wl));
+    FFM_TRY(check_layout_limits(a, nOwn, N, F, wu, wl, L.loShift));
     slice_offsets(wu, wl, L);
     fill_entries(a, nOwn, N, F, L);
     row_schedule(a, nOwn, L);
     return FFM_OK;
+}
+
+// Would ffm_ldu_create* accept this addressing?  The analysis and the layout of ffm_ldu_create_ext on the host, without a device or a
+// context; the refusal's message is left in ffm_last_error.  (The size that no int32 entry can hold is refused before the analysis
+// allocates its per-cell arrays.)
+extern "C" int ffm_ldu_check_layout(int nOwned, int nGhost, int nFaces, const int *l, const int *u)
+{
+    if (nOwned < 0 || nGhost < 0 || nFaces < 0 || (nFaces && (!l || !u))) { ffm_set_error("ffm_ldu_check_layout: bad argument"); return FFM_ERR_ARG; }
+    if ((long)nOwned + nGhost >= (1L << 27)) { ffm_set_error("mesh too large for int32 packed entries"); return FFM_ERR_UNSUPPORTED; }
+    LduAnalysis a;
+    FFM_TRY(analyse(nOwned + nGhost, nOwned, nFaces, l, u, true, false, a, nullptr, -1));
+    LduLayout L;
+    return ffm_ldu_layout(a, nOwned, nGhost, nFaces, L);
 }

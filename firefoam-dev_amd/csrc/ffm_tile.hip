@@ -126,7 +126,7 @@ static int build_dir(ffm_ldu *A, bool fwd, const std::vector<int> &lvl, const st
                      const std::vector<int> &grpOfCell, TileDir &D, bool &ok, std::vector<int4> *recOut = nullptr,
                      std::vector<int> *grpEntOut = nullptr)
 {
-    const int G = (int)grpCell.size() - 1, nOwn = A->nOwned, W = T_W;
+    const int G = (int)grpCell.size() - 1, nOwn = A->nOwned, W = T_W, sh = A->loShift;
     const std::vector<int> &off = fwd ? A->h_loOff : A->h_upOff;
     const std::vector<int> &ent = fwd ? A->h_loEnt : A->h_upNbr;
     std::vector<int> nbr((size_t)W * nOwn, -1), src((size_t)W * nOwn, -1);
@@ -141,11 +141,11 @@ static int build_dir(ffm_ldu *A, bool fwd, const std::vector<int> &lvl, const st
             for (int s = 0; s < wdt; s++) {
                 const int q = off[sl] + s * 64 + lane, e = ent[q];
                 if (e < 0) continue;
-                const int nb = fwd ? (e >> 4) : e;
+                const int nb = fwd ? (e >> sh) : e;
                 if (nb >= nOwn) continue;
                 if (k >= W) { tooMany = 1; break; }
                 nbr[(size_t)W * c + k] = nb;
-                src[(size_t)W * c + k] = fwd ? (A->h_upOff[(e >> 4) >> 6] + (e & 15) * 64 + ((e >> 4) & 63)) : q;
+                src[(size_t)W * c + k] = fwd ? (A->h_upOff[nb >> 6] + (e & ((1 << sh) - 1)) * 64 + (nb & 63)) : q;
                 if (isExt((int)c, nb)) exposed[nb] = 1;          // (several threads may store the same 1)
                 else far = std::max(far, std::abs((int)c - nb));
                 k++;
@@ -289,7 +289,7 @@ static int build_amul(ffm_ldu *A, const std::vector<int> &grpOfCell, const std::
             for (int s = 0; s < lw; s++) {
                 const int q = A->h_loEnt[A->h_loOff[sl] + s * 64 + lane];
                 if (q < 0) continue;
-                const int o = q >> 4, os = q & 15;
+                const int o = q >> A->loShift, os = q & ((1 << A->loShift) - 1);
                 if (k >= 3) { AMUL_GIVE_UP("more than 3 lower neighbours"); }
                 if (inRing(c, o) && os < 3 && c - o < 2048) code[(size_t)8 * c + k] = (unsigned short)((c - o) | (os << 12));
                 else {

@@ -132,6 +132,13 @@ int ffm_ldu_create_ext(ffm_ctx *ctx, int nOwned, int nGhost, int nFaces, const i
                        const int *upperAddr, ffm_ldu **out);
 int ffm_renumber_levels_ext(int nOwned, int nGhost, int nFaces, const int *lowerAddr,
                             const int *upperAddr, int *newToOldCell, int *newToOldFace);
+/* Would ffm_ldu_create_ext accept this addressing?  Host code only, no device and no
+ * context: FFM_OK, or the code ffm_ldu_create_ext would return, with its message in
+ * ffm_last_error.  The limits of the row layout: at most 32 upper and 32 lower faces
+ * per cell; fewer than 2^27 cells, and fewer than 2^26 where some cell owns more than
+ * 16 faces towards owned cells (wide coarse GAMG levels).                            */
+int ffm_ldu_check_layout(int nOwned, int nGhost, int nFaces, const int *lowerAddr,
+                         const int *upperAddr);
 /* Same with a grouping hint for the sweeps: groupHint[c] = any label shared by owned cells that should be swept by one
  * workgroup (e.g. a 2-D tile of cell columns, from the cell centres).  Used when the label classes form an acyclic
  * dependency graph, ignored otherwise (NULL: the library chunks the caller's cell order).                         */

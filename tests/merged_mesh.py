@@ -24,12 +24,13 @@ CASES = {
     "w16u10": ((6, 5, 4), [(2, 2, 2, 2)], True, 119, 10, 4, 16),
     "w16u14": ((6, 5, 4), [(1, 2, 2, 3)], True, 118, 14, 4, 16),
     "w32l18": ((7, 5, 4), [(1, 2, 2, 4)], False, 137, 4, 18, 32),
+    "w32u18": ((7, 5, 4), [(1, 2, 2, 4)], True, 137, 18, 4, 32),                # owner slots 16 and 17: five-bit slot field of the lower entries
     "w32l30": ((9, 5, 4), [(1, 2, 2, 7)], False, 174, 4, 30, 32),
     "w32multi": ((9, 5, 5), [(1, 2, 2, 7), (1, 2, 3, 7), (1, 1, 1, 3)], False, 211, 4, 24, 32),      # bars adjacent to bars
 }
-# meshes the library refuses: more than 16 owned faces towards owned cells; more than 32 faces on one side
+# meshes the library refuses: more than 32 faces on one side, upper or lower
 REFUSED = {
-    "u18": ((7, 5, 4), [(1, 2, 2, 4)], True, 137, 18, 4, None),
+    "u34": ((10, 5, 4), [(1, 2, 2, 8)], True, 193, 34, 4, None),
     "l34": ((10, 5, 4), [(1, 2, 2, 8)], False, 193, 4, 34, None),
 }
 

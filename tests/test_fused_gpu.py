@@ -8,8 +8,8 @@ ffm_fvc_flux_rho, ffm_fvm_HbyA3, ffm_fvm_pressure_eqn, ffm_pc_phig / _phiHbyA / 
 each against the `_ops` chain of csrc/ffm_plume_step.hip it replaced, bitwise, and against oracle/fv.py.
 
 Row-width buckets (FFM_DISPATCH_W of csrc/ffm_device.hpp): the tests that take `setup` run on the hex box (W = 3) and, through
-TestMergedMeshes, on the merged meshes `w4`, `w8`, `w16u14`, `w32l30`, `w32multi` of tests/merged_mesh.py (W = 4, 8, 16, 32, 32); the ray
-assembly on hex, `w8`, `w16u14`, `w32l30`.  The entry points that pick their bucket by hand must refuse the rows they were not built for
+TestMergedMeshes, on the merged meshes `w4`, `w8`, `w16u14`, `w32l30`, `w32multi`, `w32u18` of tests/merged_mesh.py (W = 4, 8, 16, 32, 32, 32); the ray
+assembly on hex, `w8`, `w16u14`, `w32l30`, `w32u18`.  The entry points that pick their bucket by hand must refuse the rows they were not built for
 (div_phiK: W > 8; rho_eqn: W > 16; the tiled multivariate weights: W > 3) with FFM_ERR_UNSUPPORTED and leave their outputs untouched.
 The time-step and tiled-weights tests build their own box meshes (W = 3; the decomposed plume elsewhere reaches W = 8)."""
 import os
@@ -24,8 +24,8 @@ from common import rel_l2
 pytestmark = pytest.mark.gpu
 
 
-MESHES = ["hex", "w4", "w8", "w16u14", "w32l30", "w32multi"]
-BUCKET = {"hex": 3, "w4": 4, "w8": 8, "w16u14": 16, "w32l30": 32, "w32multi": 32}
+MESHES = ["hex", "w4", "w8", "w16u14", "w32l30", "w32multi", "w32u18"]
+BUCKET = {"hex": 3, "w4": 4, "w8": 8, "w16u14": 16, "w32l30": 32, "w32multi": 32, "w32u18": 32}
 
 
 def _bucket(s):
@@ -506,7 +506,7 @@ def test_pressure_corrector_face_passes_equal_the_operator_chain(setup, O, ctx):
     assert rel_l2(_faces_o(s, tt), (flx + _faces_o(s, phig)) / _faces_o(s, rhorAUf)) < 1e-14
 
 
-RAY_MESHES = ["hex", "w8", "w16u14", "w32l30"]
+RAY_MESHES = ["hex", "w8", "w16u14", "w32l30", "w32u18"]
 
 
 @pytest.mark.parametrize("which", RAY_MESHES)

@@ -5,7 +5,7 @@ reference's face order with FMA contraction off -> compared at 1e-14 relative (b
 expression order is identical); reconstruct inverts the cell tensor analytically (oracle: LAPACK) -> 1e-13.
 
 Row-width buckets (FFM_DISPATCH_W of csrc/ffm_device.hpp): the tests that take `setup` run on the hex box (W = 3) and, through
-TestMergedMeshes, once more on each of the merged meshes `w4`, `w8`, `w16u14`, `w32l30`, `w32multi` of tests/merged_mesh.py
+TestMergedMeshes, once more on each of the merged meshes `w4`, `w8`, `w16u14`, `w32l30`, `w32multi`, `w32u18` of tests/merged_mesh.py
 (W = 4, 8, 16, 32, 32: one wide row among rows of 3 or 4, nearly all slots padding), with the same assertions; every fixture asserts
 its bucket from the addressing the library is given.  The oracle runs on the mesh in that numbering (merged_mesh.renumbered), so a
 row's terms come in the same face order on both sides.  On the merged meshes the bar of `reconstruct` is 1e-13 times the largest
@@ -19,8 +19,8 @@ from common import rel_l2
 pytestmark = pytest.mark.gpu
 
 
-MESHES = ["hex", "w4", "w8", "w16u14", "w32l30", "w32multi"]
-BUCKET = {"hex": 3, "w4": 4, "w8": 8, "w16u14": 16, "w32l30": 32, "w32multi": 32}
+MESHES = ["hex", "w4", "w8", "w16u14", "w32l30", "w32multi", "w32u18"]
+BUCKET = {"hex": 3, "w4": 4, "w8": 8, "w16u14": 16, "w32l30": 32, "w32multi": 32, "w32u18": 32}
 
 
 def _host_mesh(name):

@@ -8,7 +8,7 @@ GPU, serial sums on the CPU), so residual histories agree to ~1e-12 relative; it
 must be identical and converged fields agree to 1e-8 rel-L2 (north_star tolerance).
 
 Row-width buckets (FFM_DISPATCH_W of csrc/ffm_device.hpp): the boxes, the chain and the plane run W = 3, the relabelled DAG mesh
-W = 8 with non-uniform slices; the merged meshes `w4`, `w16u14`, `w32l30` and `w32multi` (tests/merged_mesh.py) run W = 4, 16 and 32
+W = 8 with non-uniform slices; the merged meshes `w4`, `w16u14`, `w32l30`, `w32multi` and `w32u18` (tests/merged_mesh.py) run W = 4, 16 and 32
 of every row kernel and sweep against the serial face loop, bit for bit."""
 import numpy as np
 import pytest
@@ -33,10 +33,12 @@ def meshes(O):
                                         "hex_levelmajor_t41", "hex_natural_t29", "plane_t17",
                                         "hex_natural_t37", "dag_random_t23", "chain_t64", "plane_t50", "hex_natural_t500", "hex_tiles_t0",
                                         "hex_natural_lv", "hex_levelmajor_lv", "chain_lv", "plane_lv", "hex_big", "hex_big_lv", "hex_baffled_t0",
-                                        "w4", "w16u14", "w32l30", "w32multi", "w16u14_lv", "w32l30_lv", "w16u14_t0"])
+                                        "w4", "w16u14", "w32l30", "w32multi", "w16u14_lv", "w32l30_lv", "w16u14_t0",
+                                        "w32u18", "w32u18_lv"])
 def case(request, O, ffm, ctx):
-    """`w*`: the merged meshes of tests/merged_mesh.py in their own numbering (one row of 4, 14, 30 or 24 faces among rows of 3 or 4:
-    the W = 4, 16 and 32 instantiations of the row kernels and sweeps, non-uniform slice widths).  `_tNN`: tiled wavefront sweep on chunks of NN cells, so that the cross-workgroup hand-off (mailboxes, LDS ring
+    """`w*`: the merged meshes of tests/merged_mesh.py in their own numbering (one row of 4, 14, 30, 24 or 18 faces among rows of 3 or 4:
+    the W = 4, 16 and 32 instantiations of the row kernels and sweeps, non-uniform slice widths; `w32u18` has the wide row on the owner's
+    side, so that its neighbours read owner slots 16 and 17 through the five-bit slot field of their lower entries).  `_tNN`: tiled wavefront sweep on chunks of NN cells, so that the cross-workgroup hand-off (mailboxes, LDS ring
     wrap-around) is exercised on small meshes too (t0: a 2-D tile hint).  `_lv`: level-scheduled sweeps.  No suffix: the
     default (tiled sweeps on detected boxes and hinted meshes, level-scheduled otherwise)."""
     import os
@@ -250,12 +252,15 @@ def test_dataflow_sweeps_bit_exact(O, ffm, ctx, monkeypatch):
     launch in which every cell waits for the values it needs (csrc/ffm_solve.hip: k_flow_sweep; chunks of 256 cells by ticket,
     values published in sentinel-filled arrays).  They must be the serial face loops bit for bit: DIC and DILU (calcReciprocalD,
     precondition, transposed), GaussSeidel and symGaussSeidel, on a randomly relabelled DAG mesh (non-contiguous backward levels),
-    a hex box, and larger ones of both (hundreds of chunks)."""
+    a hex box, larger ones of both (hundreds of chunks), and the merged mesh with 18 owned upper faces in one row."""
     monkeypatch.setenv("FFM_SWEEP", "levels")
     H = ffm.hexmesh
-    for name in ("dag", "hex", "dag-large", "hex-large"):
+    for name in ("dag", "hex", "dag-large", "hex-large", "w32u18"):
         if name == "dag":
             N, l, u = random_dag_mesh(O, 14, seed=5)
+        elif name == "w32u18":                  # owner slots 16 and 17 read through the lower entries
+            m = MM.case(name); N, l, u = m.nCells, m.l.astype(np.int32), m.u.astype(np.int32)
+            assert MM.widths(l, u) == (18, 4)
         elif name == "dag-large":
             N, l, u = random_dag_mesh(O, 36, seed=9)
         elif name == "hex-large":
@@ -285,12 +290,11 @@ def test_dataflow_sweeps_bit_exact(O, ffm, ctx, monkeypatch):
         A.close()
 
 
-@pytest.mark.parametrize("name,message", [("u18", "a cell owns more than 16 faces towards owned cells"),
+@pytest.mark.parametrize("name,message", [("u34", r"a cell has 34 upper / \d+ lower faces \(> 32\): not supported by the sliced layout"),
                                           ("l34", r"a cell has \d+ upper / 34 lower faces \(> 32\): not supported by the sliced layout")])
 def test_too_wide_rows_are_refused(O, ffm, ctx, name, message):
-    """a cell with more than 16 owned upper faces (the packed lower entry has 4 bits for the owner's slot) or more than 32 faces on one
-    side (the widest instantiation) is refused by ffm_ldu_create with FFM_ERR_UNSUPPORTED before anything is launched, and the
-    context goes on working"""
+    """a cell with more than 32 faces on one side, the owner's or the neighbour's (the widest instantiation of the row kernels), is
+    refused by ffm_ldu_create with FFM_ERR_UNSUPPORTED before anything is launched, and the context goes on working"""
     m = MM.case(name)
     assert MM.widths(m.l, m.u) == MM.REFUSED[name][4:6]
     with pytest.raises(ffm.FfmError, match=r"failed \(-5\): " + message):

@@ -1,6 +1,6 @@
 """The kEqn kernels of the compiled time step on their own (csrc/ffm_fused.hip: ffm_les_keqn_terms, ffm_les_face_diffusivity,
 ffm_les_keqn_update) against numpy, on one mesh per row-width bucket of FFM_DISPATCH_W: the 7 x 8 x 6 hex box (W = 3) and the merged
-meshes w4, w8, w16u14, w32l30, w32multi of tests/merged_mesh.py.  The inputs hold a patch with nut_b = 0 (the floor), a cell with
+meshes w4, w8, w16u14, w32l30, w32multi, w32u18 of tests/merged_mesh.py.  The inputs hold a patch with nut_b = 0 (the floor), a cell with
 k = SMALL and cells below it; ffm_les_keqn_update is also launched on one cell.
 
 Agreement.  The numpy side states each expression in the kernels' operation order on the mesh in the device's numbering, where the
@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 SENTINEL = -7.25
 SMALL = 1.0e-15
-MESHES = {"hex": 3, "w4": 4, "w8": 8, "w16u14": 16, "w32l30": 32, "w32multi": 32}
+MESHES = {"hex": 3, "w4": 4, "w8": 8, "w16u14": 16, "w32l30": 32, "w32multi": 32, "w32u18": 32}
 MU, CE, CK, PRT = 1.8e-5, 1.048, 0.094, 0.85
 
 

@@ -96,9 +96,12 @@ def test_every_smoother_sweep_sees_the_neighbour_ranks_current_values(O, ffm, ct
     assert rel_l2(b, a) < 1e-13, rel_l2(b, a)
 
 
-@pytest.mark.parametrize("meshName,world,precond,asym", [("steckler", 2, "GS", 0.0), ("steckler", 4, "GS", 0.0), ("dag_random", 2, "DILU", 0.3),
-                                                         ("steckler", 4, "SYMGS", 0.0), ("dag_random", 4, "DIC", 0.0)])
-def test_gamg_on_a_decomposed_mesh(O, ffm, ctx, meshName, world, precond, asym):
+@pytest.mark.parametrize("meshName,world,precond,asym,part", [
+    pytest.param("steckler", 2, "GS", 0.0, "rcb", id="steckler-2-GS-0.0"), pytest.param("steckler", 4, "GS", 0.0, "rcb", id="steckler-4-GS-0.0"),
+    pytest.param("dag_random", 2, "DILU", 0.3, "rcb", id="dag_random-2-DILU-0.3"), pytest.param("steckler", 4, "SYMGS", 0.0, "rcb", id="steckler-4-SYMGS-0.0"),
+    pytest.param("dag_random", 4, "DIC", 0.0, "rcb", id="dag_random-4-DIC-0.0"),
+    pytest.param("dag_random", 2, "DILU", 0.3, "graph", id="dag_random-2-DILU-0.3-graph"), pytest.param("dag_random", 4, "DIC", 0.0, "graph", id="dag_random-4-DIC-0.0-graph")])
+def test_gamg_on_a_decomposed_mesh(O, ffm, ctx, meshName, world, precond, asym, part):
     """GAMG over 2 and 4 ranks the way OpenFOAM runs it without a processorAgglomerator (BASELINE config 5: p_rgh by GAMG + GaussSeidel on
     four ranks, cases/wallFireSpread2D/system/fvSolution:36-60): every rank agglomerates its own cells, the processor interfaces are
     agglomerated with them, smoothers refresh the interfaces before every sweep, the coarsest level is solved over all ranks, the
@@ -106,7 +109,7 @@ def test_gamg_on_a_decomposed_mesh(O, ffm, ctx, meshName, world, precond, asym):
     sharing cuda:0 through the host transport) against the oracle in OpenFOAM's processor-patch form (oracle/gamg_multi.py) on the same
     decomposition: the same hierarchy (cells per level on every rank), the same number of V-cycles, the same residuals and solution
     (the two forms add a row's interface terms at different places of its sum: rounding level)."""
-    args = [meshName, "rcb", "GAMG", precond, str(asym)]          # (coordinate bisection: box-like sub-domains; a coarse cell may have at most 16 lower / upper neighbours in this library)
+    args = [meshName, part, "GAMG", precond, str(asym)]           # (rcb: coordinate bisection, box-like sub-domains; graph: sub-domains of any shape, wider coarse rows)
     port = free_port()
     with tempfile.TemporaryDirectory() as t1, tempfile.TemporaryDirectory() as t2:
         ref = _run_ranks("oracle", world, port, args, t1, env=dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES=""))

@@ -20,7 +20,7 @@ from common import laplacian_like
 
 pytestmark = pytest.mark.gpu
 
-CASES = ["box", "box_random", "w8", "w16u14", "w32l30", "w32multi", "steckler"]
+CASES = ["box", "box_random", "w8", "w16u14", "w32l30", "w32multi", "w32u18", "steckler"]
 _cache = {}
 
 
