@@ -170,6 +170,8 @@ def lib():
         "ffm_thermo_he_d": ([vp, C.c_long, C.POINTER(vp), dp, dp], C.c_int),
         "ffm_thermo_properties_d": ([vp, C.c_long, C.POINTER(vp), dp, dp, dp, dp], C.c_int),
         "ffm_thermo_Cp_d": ([vp, C.c_long, C.POINTER(vp), dp, dp], C.c_int),
+        "ffm_thermo_step_d": ([vp, C.c_long, C.POINTER(vp), dp, dp, dp, dp, dp, dp, dp], C.c_int),
+        "ffm_thermo_species": ([vp, C.POINTER(C.c_int), hp], C.c_int),
         "ffm_thermo_destroy": ([vp], C.c_int),
         "ffm_edc_correct_d": ([vp, C.c_long] + [dp] * 6 + [C.c_double] * 7 + [dp, dp], C.c_int),
         "ffm_les_keqn_nut_d": ([vp, C.c_long, C.c_double, C.c_double, dp, dp, dp, dp, dp], C.c_int),
@@ -270,6 +272,9 @@ def lib():
         "ffm_plume_set_turbulence": ([vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, hp], C.c_int),
         "ffm_les_keqn_terms": ([vp, C.POINTER(vp), dp, dp, dp, dp, dp, dp, dp, C.c_double, dp, dp, dp], C.c_int),
         "ffm_les_face_diffusivity": ([vp, C.c_int, C.c_double, dp, dp, dp, dp, dp, dp], C.c_int),
+        "ffm_les_face_diffusivity_v": ([vp, C.c_int, dp, dp, dp, dp, dp, dp, dp], C.c_int),
+        "ffm_plume_set_thermo": ([vp, vp], C.c_int),
+        "ffm_plume_set_combustion": ([vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double], C.c_int),
         "ffm_les_keqn_update": ([vp, C.c_long, C.c_double, C.c_double, C.c_double, dp, dp, dp, dp, dp], C.c_int),
         "ffm_plume_set_radiation": ([vp, C.c_int, C.c_int, C.c_int, vp, vp], C.c_int),
         "ffm_plume_set_radiation_model": ([vp, C.c_double, C.c_double, C.c_double], C.c_int),
@@ -909,6 +914,22 @@ class Plume:
                 raise ValueError("set_turbulence: k0 holds one value per cell")
         _check(lib().ffm_plume_set_turbulence(self.h, names[model], float(Ck), float(Ce), float(Prt), float(kInlet), None if k0 is None else _hp(k0)),
                "ffm_plume_set_turbulence")
+
+    def set_thermo(self, thermo):
+        """the step's thermo model (ffm_plume_set_thermo): a Thermo holding the plume's five species in its order -- janaf / sutherland /
+        perfectGas -- or None for the stand-in.  Borrowed: keep it open while the plume uses it.  Only before the first step or after
+        set_initial_state; redoes the hydrostatic start-up"""
+        _check(lib().ffm_plume_set_thermo(self.h, None if thermo is None else thermo.h), "ffm_plume_set_thermo")
+        self._thermo = thermo
+
+    def set_combustion(self, model="EDC", C_EDC=4.0, C_Diff=0.0, C_Stiff=1.0, s=3.6282945, qFuel=46357151.0):
+        """the step's combustion model (ffm_plume_set_combustion): "EDC" -- the reference's eddyDissipationModel, needs set_turbulence --
+        or None / "none" for the stand-in; s, qFuel: singleStepReactingMixture's (defaults: the plume's constants)"""
+        names = {None: 0, "none": 0, "EDC": 1}
+        if model not in names:
+            raise ValueError("set_combustion: model %r (None, 'none' or 'EDC')" % (model,))
+        _check(lib().ffm_plume_set_combustion(self.h, names[model], float(C_EDC), float(C_Diff), float(C_Stiff), float(s), float(qFuel)),
+               "ffm_plume_set_combustion")
 
     def set_radiation(self, solverFreq=100, nPhi=2, nTheta=4, rays=None):
         """fvDOM stand-in: 4*nPhi*nTheta upwind ray solves every solverFreq steps; rays = [(dAve[3], omega)] or None"""

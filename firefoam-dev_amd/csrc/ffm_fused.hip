@@ -1391,7 +1391,7 @@ extern "C" int ffm_les_keqn_G(ffm_mesh *m, const double *const *g, const double 
     return FFM_OK;
 }
 
-// ---- kEqn in the compiled time step (ffm_plume_step.hip: k_eqn, u_eqn, standin_combustion) -----------------------------------------
+// ---- kEqn in the compiled time step (ffm_plume_step.hip: k_eqn, u_eqn, combustion_correct) -----------------------------------------
 // The explicit terms of kEqn::correct (LESModels/kEqn/kEqn.C) in one owner-row pass: divU = fvc::surfaceIntegrate(phi/interpolate(rho))
 // from the row's faces and patch faces in k_face_sum's order (lower faces -, upper faces +, patch faces +, then /V), G from the nine
 // cell gradients, and from them the three arrays a scalar transport assembly takes:
@@ -1487,6 +1487,47 @@ extern "C" int ffm_les_face_diffusivity(ffm_mesh *m, int mode, double c0, const 
     LesFaceDiff a = {rho, rho_b, x, x_b, c0, out_f, out_b};
     if (mode == 0) FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_les_face_diffusivity<W, 0>), mview(m), a));
     else FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_les_face_diffusivity<W, 1>), mview(m), a));
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// The same pass with the laminar part c taken from a cell field (sutherland mu, modified-Eucken alpha: ffm_plume_set_thermo) in place
+// of the constant c0; its patch value is the zero-gradient copy c[owner cell]:
+//   mode 0: rho*(x + c/rho)      mode 1: c + x      x == NULL (then x_b too, LAMINAR): c itself in both modes -- plain interpolation of
+//   c and its zero-gradient patch values
+// Equal, bit for bit, to the cell expression followed by ffm_fvc_interpolate(NULL, .) and the same expression on the patch faces.
+template <int MODE, bool LAMINAR> __device__ __forceinline__ double les_diff_v_of(double c, double rho, double x)
+{ return LAMINAR ? c : (MODE == 0 ? rho * (x + c / rho) : c + x); }
+template <int W, int MODE, bool LAMINAR>
+__global__ __launch_bounds__(256) void k_les_face_diffusivity_v(MeshView q, const double *__restrict__ cf, LesFaceDiff a)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci;
+        RowEnt<W> U; load_upper<W>(q.v, c, U);
+        const double cP = cf[c];
+        const double P = les_diff_v_of<MODE, LAMINAR>(cP, (MODE == 0 && !LAMINAR) ? a.rho[c] : 0.0, LAMINAR ? 0.0 : a.x[c]);
+#pragma unroll
+        for (int s = 0; s < W; s++) if (U.on[s]) {
+            const int e = U.f[s], n = U.nb[s]; const double w = q.w[e];
+            a.outf[e] = w * P + (1.0 - w) * les_diff_v_of<MODE, LAMINAR>(cf[n], (MODE == 0 && !LAMINAR) ? a.rho[n] : 0.0, LAMINAR ? 0.0 : a.x[n]);
+        }
+        const int j = q.cellB[c];
+        if (j >= 0) for (int t = q.bcStart[j]; t < q.bcStart[j + 1]; t++) {
+            const int k = q.bcItem[t];
+            a.outb[k] = les_diff_v_of<MODE, LAMINAR>(cP, (MODE == 0 && !LAMINAR) ? a.rhob[k] : 0.0, LAMINAR ? 0.0 : a.xb[k]);
+        }
+    }
+}
+extern "C" int ffm_les_face_diffusivity_v(ffm_mesh *m, int mode, const double *c, const double *rho, const double *rho_b, const double *x,
+                                          const double *x_b, double *out_f, double *out_b)
+{
+    CHECK_M(m);
+    if ((mode != 0 && mode != 1) || !c || !out_f || (m->B && !out_b)) return FFM_ERR_ARG;
+    if (x && ((mode == 0 && !rho) || (m->B && (!x_b || (mode == 0 && !rho_b))))) return FFM_ERR_ARG;
+    LesFaceDiff a = {rho, rho_b, x, x_b, 0.0, out_f, out_b};
+    if (!x) FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_les_face_diffusivity_v<W, 1, true>), mview(m), c, a));
+    else if (mode == 0) FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_les_face_diffusivity_v<W, 0, false>), mview(m), c, a));
+    else FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_les_face_diffusivity_v<W, 1, false>), mview(m), c, a));
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }

@@ -13,7 +13,7 @@ static int hydrostatic_init(ffm_plume *P)
     const double *kind = P->kind_d;
     forN(P, B, [=] __device__(long k) { fTop[k] = (kind[k] > 1.5 && kind[k] < 2.5) ? 1.0 : 0.0; });
     forN(P, N, [=] __device__(long i) { p[i] = ph[i] + rho[i] * gh[i] + PREF; });
-    standin_thermo(P); mul(P, rho, psi, p, N);
+    FFM_TRY(thermo_correct(P)); mul(P, rho, psi, p, N);
     const long nNat = P->nNat;
     for (int corr = 0; corr < 5; corr++) {
         FFM_TRY(ffm_fvc_interpolate(m, nullptr, rho, rhof));
@@ -31,7 +31,7 @@ static int hydrostatic_init(ffm_plume *P)
         FFM_TRY(solve_named(P, "ph_rgh", FFM_PCG, FFM_DIC, 1e-6, 0.01, P->dWork, P->upper, nullptr, ph, P->sWork));
         FFM_TRY(HX(P, ph));
         forN(P, N, [=] __device__(long i) { p[i] = ph[i] + rho[i] * gh[i] + PREF; });
-        standin_thermo(P); mul(P, rho, psi, p, N);
+        FFM_TRY(thermo_correct(P)); mul(P, rho, psi, p, N);
     }
     FFM_TRY(ffm_bc_values(m, fTop, P->zeroB, P->zeroB, ph, P->ph_rgh_b));
     dcopy(P, P->p_rgh, ph, N);
@@ -274,9 +274,40 @@ extern "C" int ffm_plume_destroy(ffm_plume *P)
     for (double *p : P->pool) hipFree(p);
     for (int a = 0; a < 3; a++) { hipFree(P->radCm[a]); hipFree(P->radFm[a]); }
     hipFree(P->radHaloCells);
+    hipFree(P->thermoFail); if (P->thermoFailH) hipHostFree(P->thermoFailH);
     ffm_mesh_destroy(P->mesh); ffm_ldu_destroy(P->A);
     delete P;
     return FFM_OK;
+}
+
+// h's patch reference values: the inlet's enthalpy, hAmb on the inletOutlet patches, 0 on the floor.  Stand-in thermo: CP (T_IN - TREF);
+// janaf: Hs(inlet mixture, T_IN) from the inlet faces' species values (ffm_thermo_he_d over all patch faces: the others' are not kept)
+static int plume_inlet_enthalpy(ffm_plume *P)
+{
+    const int B = P->B; const double *kind = P->kind_d; double *rH = P->refH; const double hAmb = P->hAmb;
+    if (!P->thermo) { forN(P, B, [=] __device__(long k) { rH[k] = kind[k] < 0.5 ? CP * (T_IN - TREF) : kind[k] > 1.5 ? hAmb : 0.0; }); return FFM_OK; }
+    double *Tin = P->wB[0], *hin = P->wB[2];
+    forN(P, B, [=] __device__(long k) { Tin[k] = T_IN; });
+    FFM_TRY(ffm_thermo_he_d(P->thermo, B, P->refY, Tin, hin));
+    forN(P, B, [=] __device__(long k) { rH[k] = kind[k] < 0.5 ? hin[k] : kind[k] > 1.5 ? hAmb : 0.0; });
+    return FFM_OK;
+}
+// The start-up from the Y and h the handle holds: p = pRef, ph_rgh = 0, thermo.correct() (janaf: from T = TREF, the Newton start),
+// rho = psi p, the hydrostatic initialisation; reNut: correctNut() of the kEqn model again, with the new rho
+static int plume_startup(ffm_plume *P, bool reNut)
+{
+    const int N = P->N;
+    double *p = P->p, *ph = P->ph_rgh, *T = P->T;
+    forN(P, N, [=] __device__(long c) { p[c] = PREF; ph[c] = 0.0; });
+    if (P->thermo) forN(P, N, [=] __device__(long c) { T[c] = TREF; });
+    P->log.clear();
+    FFM_TRY(thermo_correct(P));
+    mul(P, P->rho, P->psi, P->p, N);
+    FFM_TRY(hydrostatic_init(P));
+    if (reNut && P->turbModel) FFM_TRY(plume_turbulence_init(P));
+    thermo_flag_fetch(P);
+    PL_HIP(hipStreamSynchronize(P->ctx->stream));
+    return thermo_flag_check(P);
 }
 
 extern "C" int ffm_plume_set_tight(ffm_plume *P, int on) { if (!P) return FFM_ERR_ARG; P->tight = on != 0; return FFM_OK; }
@@ -305,20 +336,13 @@ extern "C" int ffm_plume_set_initial_state(ffm_plume *P, const double *const *Y,
     for (int i = 0; i < NSP; i++) FFM_TRY(up(P->Y[i], Y[i]));
     FFM_TRY(up(P->hs, h));
     P->hAmb = hAmb;
-    const double *kind = P->kind_d; double *rH = P->refH;
+    const double *kind = P->kind_d;
     for (int i = 0; i < NSP; i++) {
         double *r = P->refY[i]; const double a = Yamb[i], b = Yin[i];
         forN(P, B, [=] __device__(long k) { r[k] = kind[k] < 0.5 ? b : kind[k] > 1.5 ? a : 0.0; });
     }
-    forN(P, B, [=] __device__(long k) { rH[k] = kind[k] < 0.5 ? CP * (T_IN - TREF) : kind[k] > 1.5 ? hAmb : 0.0; });
-    double *p = P->p, *ph = P->ph_rgh;
-    forN(P, N, [=] __device__(long c) { p[c] = PREF; ph[c] = 0.0; });
-    P->log.clear();
-    standin_thermo(P);
-    mul(P, P->rho, P->psi, P->p, N);
-    FFM_TRY(hydrostatic_init(P));
-    PL_HIP(hipStreamSynchronize(P->ctx->stream));
-    return FFM_OK;
+    FFM_TRY(plume_inlet_enthalpy(P));
+    return plume_startup(P, P->thermo != nullptr);
 }
 
 // Tests (the deciding test of the multi-step parity question): the NEXT ffm_plume_step convects the species and h with these face
@@ -358,6 +382,10 @@ extern "C" int ffm_plume_set_turbulence(ffm_plume *P, int model, double Ck, doub
             ffm_set_error("ffm_plume_set_turbulence: k0[%d] is not finite and positive", c); return FFM_ERR_ARG;
         }
     }
+    if (model == 0 && P->combModel == 1) {
+        ffm_set_error("ffm_plume_set_turbulence: the EDC of ffm_plume_set_combustion reads the kEqn model's Ce and delta; switch it off first");
+        return FFM_ERR_UNSUPPORTED;
+    }
     PL_HIP(hipSetDevice(P->ctx->device));
     PL_HIP(hipStreamSynchronize(P->ctx->stream));
     if (model == 0) {
@@ -393,6 +421,77 @@ extern "C" int ffm_plume_set_turbulence(ffm_plume *P, int model, double Ck, doub
     PL_HIP(hipStreamSynchronize(P->ctx->stream));
     return FFM_OK;
 }
+// buffers that live while a model wants them.  alphaStd: the alpha EDC reads with the stand-in thermo, a cell field of mu/Pr.  wFuel and
+// Qdot: with either model on they get arrays of their own and stay readable after the step ("wFuel", "Qdot"); otherwise they are the
+// scratch slots they always were, which later stages of the step reuse
+static int plume_model_buffers(ffm_plume *P)
+{
+    const bool wantA = P->combModel == 1 && !P->thermo, wantS = P->combModel == 1 || P->thermo;
+    if ((!wantA && P->alphaStd) || (!wantS && P->wFuelOwn)) PL_HIP(hipStreamSynchronize(P->ctx->stream));
+    if (wantA && !P->alphaStd) P->alphaStd = dfill(P, P->N, MU / PR);
+    if (!wantA) dfree(P, P->alphaStd);
+    if (wantS && !P->wFuelOwn) { P->wFuelOwn = dalloc(P, P->N); P->QdotOwn = dalloc(P, P->N); }
+    if (!wantS) { dfree(P, P->wFuelOwn); dfree(P, P->QdotOwn); }
+    if ((wantA && !P->alphaStd) || (wantS && (!P->wFuelOwn || !P->QdotOwn))) { ffm_set_error("plume: out of device memory"); return FFM_ERR_HIP; }
+    P->wFuel = wantS ? P->wFuelOwn : P->wN[8]; P->Qdot = wantS ? P->QdotOwn : P->wN[9];
+    return FFM_OK;
+}
+// the thermo model of the step: see include/ffm.h
+extern "C" int ffm_plume_set_thermo(ffm_plume *P, ffm_thermo *thermo)
+{
+    if (!P) return FFM_ERR_ARG;
+    if (P->stepNo != 0) { ffm_set_error("ffm_plume_set_thermo: steps have been taken; restart with ffm_plume_set_initial_state first"); return FFM_ERR_ARG; }
+    if (thermo) {
+        int n = 0; double W[8];
+        FFM_TRY(ffm_thermo_species(thermo, &n, nullptr));
+        if (n != NSP) { ffm_set_error("ffm_plume_set_thermo: the table holds %d species, the plume %d", n, NSP); return FFM_ERR_ARG; }
+        FFM_TRY(ffm_thermo_species(thermo, &n, W));
+        for (int i = 0; i < NSP; i++) if (!(std::fabs(W[i] - WMOL[i]) <= 1e-3 * WMOL[i])) {
+            ffm_set_error("ffm_plume_set_thermo: species %d has molecular weight %g, the plume's %s %g", i, W[i], SPN[i], WMOL[i]); return FFM_ERR_ARG;
+        }
+        if (P->radFreq > 0 || P->radCoupled || P->radOrdering != 0) {
+            ffm_set_error("ffm_plume_set_thermo: not with ffm_plume_set_radiation* on (radiation->Sh is written with the constant Cp)"); return FFM_ERR_UNSUPPORTED;
+        }
+    }
+    PL_HIP(hipSetDevice(P->ctx->device));
+    PL_HIP(hipStreamSynchronize(P->ctx->stream));
+    if (thermo && !P->mu) {
+        const size_t nPool = P->pool.size();
+        P->mu = dalloc(P, P->N); P->alpha = dalloc(P, P->N); P->Cp = dalloc(P, P->N);
+        if (P->pool.size() != nPool + 3) { ffm_set_error("plume: out of device memory"); return FFM_ERR_HIP; }
+        PL_HIP(hipMalloc((void **)&P->thermoFail, sizeof(int)));
+        PL_HIP(hipMemsetAsync(P->thermoFail, 0, sizeof(int), P->ctx->stream));
+        PL_HIP(hipHostMalloc((void **)&P->thermoFailH, sizeof(int), hipHostMallocDefault));
+        *P->thermoFailH = 0;
+    }
+    if (!thermo && P->mu) {
+        dfree(P, P->mu); dfree(P, P->alpha); dfree(P, P->Cp);
+        hipFree(P->thermoFail); P->thermoFail = nullptr; hipHostFree(P->thermoFailH); P->thermoFailH = nullptr;
+    }
+    P->thermo = thermo;
+    FFM_TRY(plume_model_buffers(P));
+    FFM_TRY(plume_inlet_enthalpy(P));
+    return plume_startup(P, true);
+}
+// the combustion model of the step: see include/ffm.h
+extern "C" int ffm_plume_set_combustion(ffm_plume *P, int model, double C_EDC, double C_Diff, double C_Stiff, double s, double qFuel)
+{
+    if (!P) return FFM_ERR_ARG;
+    if (model != 0 && model != 1) { ffm_set_error("ffm_plume_set_combustion: unknown model %d (0 stand-in, 1 EDC)", model); return FFM_ERR_ARG; }
+    if (model == 1) {
+        if (!std::isfinite(C_EDC) || !std::isfinite(C_Diff) || !std::isfinite(C_Stiff) || !std::isfinite(s) || !std::isfinite(qFuel) ||
+            !(s > 0) || !(C_Stiff > 0) || !(C_EDC >= 0) || !(C_Diff >= 0) || !(qFuel > 0)) {
+            ffm_set_error("ffm_plume_set_combustion: finite C_EDC >= 0, C_Diff >= 0, C_Stiff > 0, s > 0, qFuel > 0 wanted"); return FFM_ERR_ARG;
+        }
+        if (!P->turbModel) {
+            ffm_set_error("ffm_plume_set_combustion: the EDC reads the kEqn model's Ce and delta; ffm_plume_set_turbulence first"); return FFM_ERR_UNSUPPORTED;
+        }
+    }
+    PL_HIP(hipSetDevice(P->ctx->device));
+    P->combModel = model;
+    if (model == 1) { P->C_EDC = C_EDC; P->C_Diff = C_Diff; P->C_Stiff = C_Stiff; P->edcS = s; P->qFuel = qFuel; }
+    return plume_model_buffers(P);
+}
 extern "C" int ffm_plume_ncells(const ffm_plume *P) { return P ? P->nOwn : FFM_ERR_ARG; }
 extern "C" int ffm_plume_nfaces(const ffm_plume *P) { return P ? P->F : FFM_ERR_ARG; }
 
@@ -406,6 +505,8 @@ extern "C" int ffm_plume_get_field(ffm_plume *P, const char *name, double *out)
     if (n == "rho") src = P->rho; else if (n == "p") src = P->p; else if (n == "p_rgh") src = P->p_rgh; else if (n == "T") src = P->T;
     else if (n == "h") src = P->hs; else if (n == "K") src = P->K; else if (n == "Ux") src = P->U[0]; else if (n == "Uy") src = P->U[1];
     else if (n == "Uz") src = P->U[2]; else if (n == "psi") src = P->psi; else if (n == "ph_rgh") src = P->ph_rgh;
+    else if (n == "mu") src = P->mu; else if (n == "alpha") src = P->alpha; else if (n == "Cp") src = P->Cp;      // (null while the stand-in thermo is on)
+    else if (n == "wFuel") src = P->wFuelOwn; else if (n == "Qdot") src = P->QdotOwn;      // (null while both are scratch slots: no model of theirs on)
     else if (n == "k") src = P->kSgs; else if (n == "nut") src = P->nut; else if (n == "alphat") src = P->alphat;      // (null while the model is off)
     else if (n == "G") src = P->G; else if (n == "ShSu") src = P->radShSu; else if (n == "ShSp") src = P->radShSp; else if (n == "radE") src = P->radE;
     else if (n.size() > 1 && n[0] == 'I' && isdigit((unsigned char)n[1])) { const int i = atoi(n.c_str() + 1); if (i < (int)P->I.size()) src = P->I[i]; }

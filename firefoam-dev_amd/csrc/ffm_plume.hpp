@@ -2,6 +2,8 @@
 // setters, getters, hydrostatic initialisation), ffm_plume_step.hip (the time step), ffm_plume_rad.hip (the fvDOM stand-in).  The physics
 // plug-ins that the reference takes from other libraries are replaced by the stand-ins listed in oracle/plume.py (perfect gas / constant
 // Cp, constant mu, Pr, EDC-shaped single-step source, zero-gradient thermo boundary values); their constants are below.
+// Opt-in, the reference's own models take their place: LES kEqn (ffm_plume_set_turbulence), janaf / sutherland thermo (ffm_plume_set_thermo), EDC
+// (ffm_plume_set_combustion); the patch values of the thermo fields stay zero-gradient copies.
 #pragma once
 #include "ffm_internal.hpp"
 #include "ffm_device.hpp"
@@ -56,9 +58,9 @@ struct ffm_plume {
     //   wN[1-3]  u_source_ops, scalar_transport, mv_weights_ops, e_K_terms: a gradient | p_corrector: rhorAU, HbyA[0-1] ->
     //   wN[4]    u_source_ops: divc | e_eqn: divK -> (scalar_transport reads it before it writes its source sum here) | p_corrector: HbyA[2] ->
     //   wN[5-7]  u_eqn (ops), pc_flux_U (ops, blocks): reconstruct(...) -> | e_eqn: [5] -dpdt -> | pc_phig_flux_ops: rho*HbyA
-    //   wN[8-10] wFuel, Qdot, Yt: standin_combustion -> species_eqns, radiation_correct, e_eqn | pc_ddtCorr_ops: rho0*U0 | pc_p_rgh_eqn_ops: [8] div
+    //   wN[8-10] wFuel, Qdot, Yt: combustion_correct -> species_eqns, radiation_correct, e_eqn | pc_ddtCorr_ops: rho0*U0 | pc_p_rgh_eqn_ops: [8] div
     //   wN[11]   species_eqns_ops: nu_i*wFuel
-    //   wF[0]    hydrostatic_init: rhof | u_eqn: muf | alphaEff_f: standin_combustion -> species_eqns, e_eqn | p_corrector: rhorAUf ->
+    //   wF[0]    hydrostatic_init: rhof | u_eqn: muf | alphaEff_f: combustion_correct -> species_eqns, e_eqn | p_corrector: rhorAUf ->
     //   wF[1]    hydrostatic_init, u_buoyancy, pc_phig_flux_ops: snGrad(rho) | mv_weights_ops: limiter
     //   wF[2]    hydrostatic_init: phig | u_buoyancy: snGrad(p_rgh) | p_corrector: phig ->
     //   wF[3]    u_eqn (ops): LUST weights -> | scalar_transport, e_K_terms_ops: a field's own weights | p_corrector: phiHbyA ->
@@ -67,7 +69,7 @@ struct ffm_plume {
     //   wB[0]    hydrostatic_init: rhob | e_K_terms: Kb, then (after Kb's last reader) plume_rad_fraction: burner flux | p_corrector: rhorAUfb ->
     //   wB[1-3]  Ub: U_boundary -> the end of the stage that called it (u_eqn, e_K_terms, p_corrector); in between hydrostatic_init: [1] fTop |
     //            mv_weights: [1] inert specie's, [3] h's patch values | scalar_transport: [2] patch values
-    //   wB[4]    u_eqn: mub -> | alphaEff_b: standin_combustion -> species_eqns, e_eqn | p_corrector: rhob ->
+    //   wB[4]    u_eqn: mub -> | alphaEff_b: combustion_correct -> species_eqns, e_eqn | p_corrector: rhob ->
     //   wB[5]    u_buoyancy: reconstruct's argument -> u_eqn's source pass (after u_sources) | e_K_terms_ops: phib*Kb | p_corrector: phiHbyAb ->
     //   wB[6]    u_buoyancy: rhob | pc_p_rgh_eqn: constrainPressure gradient (until bc_p_rgh), then pc_flux_U: reconstruct's argument
     //   wB[7]    u_buoyancy: p_rgh patch values | p_corrector: p_rghEqn.flux() on the patches
@@ -120,9 +122,21 @@ struct ffm_plume {
     double *lesG[3][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};   // (ops) grad(U_c)[d]; the fused form has gM[c][d]
     // Scratch of the model's passes, beside the table above:
     //   u_eqn: wN[8] rho*nuEff, wN[9-11] div(rho nuEff dev2(T(grad U)))
-    //   standin_combustion (ops): wN[11] alpha + alphat
+    //   combustion_correct (ops): wN[11] alpha + alphat
     //   k_eqn: wN[5-7] su, su2, sp -> the assembly | wF[0], wB[4] rho*nuEff on faces / patch faces -> | wB[6] rhob | fused: gM[0-2] grad(U), gM[3] grad(k) |
     //          (ops) wN[8] G, wN[9] divU, wN[10] rho*nuEff, wF[1] rhof, wF[2] phi/rhof, wB[5] phib/rhob, then scalar_transport's own slots
+    // janaf / sutherland thermo (ffm_plume_set_thermo): the borrowed handle, or null = the stand-in; every pointer null with it
+    ffm_thermo *thermo = nullptr;
+    double *mu = nullptr, *alpha = nullptr, *Cp = nullptr;     // cells, ghosts included: thermo.correct()'s
+    int *thermoFail = nullptr, *thermoFailH = nullptr;         // thermo::T's iteration-limit flag on the device; its pinned host copy
+    // the reference's EDC (ffm_plume_set_combustion): 0 = the stand-in rate
+    int combModel = 0;
+    double C_EDC = 4.0, C_Diff = 0.0, C_Stiff = 1.0, edcS = S_O2, qFuel = HC;
+    double *alphaStd = nullptr;            // cells: mu/Pr, the alpha EDC reads while the stand-in thermo is on
+    double *wFuelOwn = nullptr, *QdotOwn = nullptr;      // wFuel and Qdot outside the scratch table while either model is on ("wFuel", "Qdot" stay readable)
+    // Scratch of the two models' passes, beside the tables above:
+    //   combustion_correct (ops, laminar thermo): nothing | (ops, kEqn) wN[11] alpha + alphat, as before
+    //   plume_inlet_enthalpy: wB[0] T_IN, wB[2] Hs(refY, T_IN) (between stages: set-up only)
 };
 
 constexpr double K_MIN = 1.0e-15;          // bound(k, kMin): kMin = SMALL
@@ -170,6 +184,27 @@ static inline void standin_thermo(ffm_plume *P)
         T[i] = t;
         psi[i] = 1.0 / (RR * t * ((((y0[i] / w0 + y1[i] / w1) + y2[i] / w2) + y3[i] / w3) + y4[i] / w4));
     });
+}
+// thermo.correct() with the selected model over all N cells.  The stand-in: standin_thermo, the launch it always was.  The janaf
+// model: fused, ONE pass without a read-back (ffm_thermo_step_d; the failure flag is read where the caller next synchronises:
+// thermo_flag_fetch / thermo_flag_check); per-operator, the two public passes it replaces (ffm_thermo_correct_d reads its own flag back)
+static inline int thermo_correct(ffm_plume *P)
+{
+    if (!P->thermo) { standin_thermo(P); return FFM_OK; }
+    if (P->fused) return ffm_thermo_step_d(P->thermo, P->N, P->Y, P->hs, P->T, P->psi, P->mu, P->alpha, P->Cp, P->thermoFail);
+    FFM_TRY(ffm_thermo_correct_d(P->thermo, P->N, P->Y, P->hs, P->p, P->T, P->psi, P->mu, P->alpha));
+    return ffm_thermo_Cp_d(P->thermo, P->N, P->Y, P->T, P->Cp);
+}
+// before / after a synchronisation the caller does anyway: copy the flag to its pinned host word; report and clear it
+static inline void thermo_flag_fetch(ffm_plume *P)
+{ if (P->thermo && P->fused) hipMemcpyAsync(P->thermoFailH, P->thermoFail, sizeof(int), hipMemcpyDeviceToHost, P->ctx->stream); }
+static inline int thermo_flag_check(ffm_plume *P)
+{
+    if (!P->thermo || !P->fused || !*P->thermoFailH) return FFM_OK;
+    *P->thermoFailH = 0;
+    hipMemsetAsync(P->thermoFail, 0, sizeof(int), P->ctx->stream);
+    ffm_set_error("thermo::T: maximum number of iterations exceeded");
+    return FFM_ERR_ARG;
 }
 static inline void mul(ffm_plume *P, double *o, const double *a, const double *b, long n) { forN(P, n, [=] __device__(long i) { o[i] = a[i] * b[i]; }); }
 

@@ -302,6 +302,7 @@ static int rad_prepare(ffm_plume *P)
 extern "C" int ffm_plume_set_radiation(ffm_plume *P, int solverFreq, int nPhi, int nTheta, const double *dAve, const double *omega)
 {
     if (!P || solverFreq < 0 || nPhi < 1 || nTheta < 1 || ((dAve == nullptr) != (omega == nullptr))) return FFM_ERR_ARG;
+    if (P->thermo) { ffm_set_error("ffm_plume_set_radiation: not with ffm_plume_set_thermo on (radiation->Sh is written with the constant Cp)"); return FFM_ERR_UNSUPPORTED; }
     PL_HIP(hipSetDevice(P->ctx->device));
     const int nRay = 4 * nPhi * nTheta;
     P->rayD.assign(3 * (size_t)nRay, 0.0); P->rayOmega.assign(nRay, 0.0);
@@ -334,6 +335,7 @@ extern "C" int ffm_plume_set_radiation(ffm_plume *P, int solverFreq, int nPhi, i
 extern "C" int ffm_plume_set_radiation_ordering(ffm_plume *P, int mode)
 {
     if (!P || (mode != 0 && mode != 1)) return FFM_ERR_ARG;
+    if (P->thermo) { ffm_set_error("ffm_plume_set_radiation_ordering: not with ffm_plume_set_thermo on (radiation->Sh is written with the constant Cp)"); return FFM_ERR_UNSUPPORTED; }
     PL_HIP(hipSetDevice(P->ctx->device));
     if (mode == 1 && !P->oneBlock) {
         const int *nb = P->nbrRank; const int rank = P->ctx->rank, world = P->ctx->nRanks;
@@ -367,6 +369,7 @@ extern "C" int ffm_plume_set_radiation_ordering(ffm_plume *P, int mode)
 extern "C" int ffm_plume_set_radiation_model(ffm_plume *P, double absorption, double Ehrr1, double Ehrr2)
 {
     if (!P || absorption < 0 || Ehrr1 < 0 || Ehrr2 < 0) return FFM_ERR_ARG;
+    if (P->thermo) { ffm_set_error("ffm_plume_set_radiation_model: not with ffm_plume_set_thermo on (radiation->Sh is written with the constant Cp)"); return FFM_ERR_UNSUPPORTED; }
     PL_HIP(hipSetDevice(P->ctx->device));
     if (!P->radE) { P->radE = dalloc(P, P->N); P->radShSu = dalloc(P, P->N); P->radShSp = dalloc(P, P->N); }
     if (!P->radE || !P->radShSu || !P->radShSp) return FFM_ERR_HIP;

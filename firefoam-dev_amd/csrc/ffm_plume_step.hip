@@ -3,6 +3,8 @@
 //   rhoEqn  solver/rhoEqn.H:33-43      UEqn  solver/UEqn.H:3-33      YEEqn   solver/YEEqn.H:37-118      pEqn  solver/pEqn.H:1-60 (x2)
 //   turbulence->correct()  solver/fireFoam.C:113-116: k_eqn, only with the LES kEqn model selected (ffm_plume_set_turbulence; oracle:
 //   tests/plume_keqn_ref.py); without it the step is the stand-in's constant mu and mu/Pr and launches nothing more than before
+//   thermo.correct(), mu, alpha: the janaf / sutherland package, and combustion->correct(): the reference's EDC, where selected
+//   (ffm_plume_set_thermo, ffm_plume_set_combustion; oracle: tests/plume_thermo_ref.py); with nothing selected, the stand-ins' launches
 // bench.py's workload and the subject of tests/test_plume_gpu.py (oracle: oracle/plume.py, same sequence in numpy).  A stage whose assembly has
 // a fused pass (ffm_fused.hip) reads P->fused once; its per-operator form, one launch per fvc:: / fvm:: operator (FFM_PLUME_UNFUSED, bitwise
 // equal), is the function <stage>_ops next to it, and what both forms run is in the stage.  Scratch slots: the table in ffm_plume.hpp.
@@ -146,6 +148,14 @@ static int les_rho_nuEff_faces(ffm_plume *P, double *gamCell, bool wantCell, dou
     ffm_mesh *m = P->mesh;
     const double *rho = P->rho, *nut = P->nut, *nutb = P->nutb;
     zg(P, rhob, rho);
+    if (P->thermo) {                // mu: thermo.correct()'s cell field, zero-gradient on the patches (ffm_les_face_diffusivity_v)
+        const double *mu = P->mu; const int *fc = ffm_mesh_bcells(m);
+        if (!P->fused || wantCell) forN(P, P->N, [=] __device__(long i) { gamCell[i] = rho[i] * (nut[i] + mu[i] / rho[i]); });
+        if (P->fused) return ffm_les_face_diffusivity_v(m, 0, mu, rho, rhob, nut, nutb, gf, gb);
+        FFM_TRY(ffm_fvc_interpolate(m, nullptr, gamCell, gf));
+        forN(P, P->B, [=] __device__(long k) { gb[k] = rhob[k] * (nutb[k] + mu[fc[k]] / rhob[k]); });
+        return FFM_OK;
+    }
     if (!P->fused || wantCell) forN(P, P->N, [=] __device__(long i) { gamCell[i] = rho[i] * (nut[i] + MU / rho[i]); });
     if (P->fused) return ffm_les_face_diffusivity(m, 0, MU, rho, rhob, nut, nutb, gf, gb);
     FFM_TRY(ffm_fvc_interpolate(m, nullptr, gamCell, gf));
@@ -166,11 +176,28 @@ static int u_stress_divergence(ffm_plume *P, const double *gam, const double *ga
     return FFM_OK;
 }
 
+// a laminar diffusivity of the janaf thermo on the faces: interpolate(c), zero-gradient patch values (c = mu: UEqn; c = alpha: YEEqn)
+static int thermo_laminar_faces(ffm_plume *P, const double *c, double *cf, double *cb)
+{
+    if (P->fused) return ffm_les_face_diffusivity_v(P->mesh, 1, c, nullptr, nullptr, nullptr, nullptr, cf, cb);
+    FFM_TRY(ffm_fvc_interpolate(P->mesh, nullptr, c, cf));
+    zg(P, cb, c);
+    return FFM_OK;
+}
+
 // turbulence->alphaEff() (solver/YEEqn.H:12): alpha + alphat with the alphat of the last correctNut(), one diffusivity for species and h
 static int les_alpha_eff(ffm_plume *P)
 {
     ffm_mesh *m = P->mesh;
     double *af = P->alphaEff_f, *afb = P->alphaEff_b, *a = P->wN[11]; const double *alphat = P->alphat, *alphatb = P->alphatb;
+    if (P->thermo) {                // alpha: thermo.correct()'s cell field, zero-gradient on the patches
+        const double *alpha = P->alpha; const int *fc = ffm_mesh_bcells(m);
+        if (P->fused) return ffm_les_face_diffusivity_v(m, 1, alpha, nullptr, nullptr, alphat, alphatb, af, afb);
+        forN(P, P->N, [=] __device__(long i) { a[i] = alpha[i] + alphat[i]; });
+        FFM_TRY(ffm_fvc_interpolate(m, nullptr, a, af));
+        forN(P, P->B, [=] __device__(long k) { afb[k] = alpha[fc[k]] + alphatb[k]; });
+        return FFM_OK;
+    }
     if (P->fused) return ffm_les_face_diffusivity(m, 1, MU / PR, nullptr, nullptr, alphat, alphatb, af, afb);
     forN(P, P->N, [=] __device__(long i) { a[i] = MU / PR + alphat[i]; });
     FFM_TRY(ffm_fvc_interpolate(m, nullptr, a, af));
@@ -189,6 +216,7 @@ static int u_eqn(ffm_plume *P)
     if (ops) FFM_TRY(ffm_fv_limited_weights(m, 4, 1.0, 0.0, 1.0, P->phi, nullptr, nullptr, nullptr, nullptr, wU));
     double *gam = P->wN[8];         // kEqn: rho*nuEff on the cells, for the stress divergence (wB[6] is u_buoyancy's rhob next)
     if (P->turbModel) FFM_TRY(les_rho_nuEff_faces(P, gam, true, P->wB[6], muf, mub));
+    else if (P->thermo) FFM_TRY(thermo_laminar_faces(P, P->mu, muf, mub));
     else {
         forN(P, P->nNat, [=] __device__(long e) { muf[e] = MU; });
         forN(P, P->B, [=] __device__(long k) { mub[k] = MU; });
@@ -214,18 +242,28 @@ static int u_eqn(ffm_plume *P)
 }
 
 // ---------------- YEEqn.H
-// stand-ins for turbulence->alphaEff() and combustion->R / Qdot(): constant alphaEff, EDC-shaped single-step fuel consumption rate
-static void standin_combustion(ffm_plume *P)
+// turbulence->alphaEff() without a sub-grid model and combustion->correct().  The stand-ins: constant alphaEff, EDC-shaped single-step
+// fuel consumption rate.  The selected models: interpolate(alpha) of the janaf thermo; the reference's eddyDissipationModel::correct
+// (ffm_plume_set_combustion: ffm_edc_correct_d, one cell pass in both forms, ghosts included) with the step's deltaT, kEqn's Ce and delta
+// and the thermo model's alpha
+static int combustion_correct(ffm_plume *P)
 {
     double *af = P->alphaEff_f, *afb = P->alphaEff_b, *wFuel = P->wFuel, *Qdot = P->Qdot, *Yt = P->Yt;
-    if (!P->turbModel) {            // (kEqn: les_alpha_eff, called next)
+    if (!P->turbModel && P->thermo) FFM_TRY(thermo_laminar_faces(P, P->alpha, af, afb));
+    else if (!P->turbModel) {       // (kEqn: les_alpha_eff, called next)
         forN(P, P->nNat, [=] __device__(long e) { af[e] = 0.5 * (MU / PR) + (1.0 - 0.5) * (MU / PR); });
         forN(P, P->B, [=] __device__(long k) { afb[k] = MU / PR; });
     }
     const double *rho = P->rho, *fuel = P->Y[2], *o2 = P->Y[0];
     // (the per-operator species loop sums Yt as it goes and wants it zero)
+    if (P->combModel == 1) {
+        if (!P->fused) forN(P, P->N, [=] __device__(long i) { Yt[i] = 0.0; });
+        return ffm_edc_correct_d(P->ctx, P->N, rho, P->kSgs, P->lesDelta, P->thermo ? P->alpha : P->alphaStd, fuel, o2, P->edcS, P->dt, P->Ce,
+                                 P->C_EDC, P->C_Diff, P->C_Stiff, P->qFuel, wFuel, Qdot);
+    }
     if (P->fused) forN(P, P->N, [=] __device__(long i) { const double w = rho[i] * fmin(fuel[i], o2[i] / S_O2) / TAU; wFuel[i] = w; Qdot[i] = w * HC; });
     else forN(P, P->N, [=] __device__(long i) { const double w = rho[i] * fmin(fuel[i], o2[i] / S_O2) / TAU; wFuel[i] = w; Qdot[i] = w * HC; Yt[i] = 0.0; });
+    return FFM_OK;
 }
 
 // the six fields under the common limiter and their patch values: h first, then the transported species, then the inert one
@@ -344,7 +382,7 @@ static int e_radiation_source(ffm_plume *P, const double **shSu, const double **
 
 // withH (the common limiter, PBiCGStab + DILU, one block, no radiation->correct() in this step): h is the fifth field of the assembly
 // pass and the fifth lane of the lock-step solve.  Nothing the enthalpy matrix reads is written by the species solves -- Qdot is
-// standin_combustion's, the K terms come from U, wMv is formed before, T, hs and G are old values -- so its explicit terms are formed
+// combustion_correct's, the K terms come from U, wMv is formed before, T, hs and G are old values -- so its explicit terms are formed
 // first; the solve log keeps the reference's order, every lane the numbers of a solve of its own.
 static int species_eqns(ffm_plume *P, bool *offDiagBound, bool withH)
 {
@@ -792,7 +830,7 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     store_old_time(P);
     FFM_TRY(rho_eqn(P));
     FFM_TRY(u_eqn(P));
-    standin_combustion(P);
+    FFM_TRY(combustion_correct(P));
     if (P->turbModel) FFM_TRY(les_alpha_eff(P));
     FFM_TRY(mv_weights(P));
     bool spOffDiagBound;
@@ -801,12 +839,13 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     FFM_TRY(species_eqns(P, &spOffDiagBound, jointYh));
     if (radNow) { FFM_TRY(radiation_correct(P)); spOffDiagBound = false; }     // radiation->correct(), solver/YEEqn.H:80: its ray solves bind other coefficients
     if (!jointYh) FFM_TRY(e_eqn(P, spOffDiagBound));
-    standin_thermo(P);
+    FFM_TRY(thermo_correct(P));
     FFM_TRY(p_corrector(P, false));
     FFM_TRY(p_corrector(P, true));
     if (P->turbModel) FFM_TRY(k_eqn(P));
     mul(P, P->rho, P->psi, P->p, P->N);
     P->time += P->dt; P->stepNo++;
+    thermo_flag_fetch(P);           // thermo::T's iteration-limit flag travels with the synchronisation that closes the step
     PL_HIP(hipStreamSynchronize(P->ctx->stream));
-    return FFM_OK;
+    return thermo_flag_check(P);
 }

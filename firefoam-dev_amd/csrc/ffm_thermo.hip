@@ -111,6 +111,33 @@ __global__ void k_thermo_cp(long n, ThermoTable t, ThermoPtrs y, const double *_
         cp[i] = th_Cp(m, T[i]);
     }
 }
+// thermo.correct() of the compiled time step (ffm_plume_step.hip): k_thermo_correct and k_thermo_cp in one pass -- the mixture is formed
+// once, Cp at the new temperature is evaluated once and serves alpha and the Cp field.  Every expression is the pair's, in the pair's
+// order: the five outputs are theirs bit for bit.  The failure flag is only ever raised; the caller reads it when it next synchronises.
+__global__ __launch_bounds__(256) void k_thermo_step(long n, ThermoTable t, ThermoPtrs y, const double *__restrict__ he, double *__restrict__ T,
+                                                     double *__restrict__ psi, double *__restrict__ mu, double *__restrict__ alpha,
+                                                     double *__restrict__ cp, int *fail)
+{
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        Mix m; cell_mixture(t, y, i, m);
+        const double h = he[i], T0 = T[i], Ttol = T0 * 1.0e-4;
+        double Tnew = T0, Test;
+        int it = 0;
+        do {
+            Test = Tnew;
+            Tnew = th_limit(m, Test - (th_Hs(m, Test) - h) / th_Cp(m, Test));
+            if (it++ > 100) { *fail = 1; break; }
+        } while (fabs(Tnew - Test) > Ttol);
+        const double R = t.RR / m.W;
+        const double muv = m.As * sqrt(Tnew) / (1.0 + m.Ts / Tnew);
+        const double Cp = th_Cp(m, Tnew), Cv = Cp - R;
+        T[i] = Tnew;
+        psi[i] = 1.0 / (R * Tnew);
+        mu[i] = muv;
+        alpha[i] = muv * Cv * (1.32 + 1.77 * R / Cv) / Cp;
+        cp[i] = Cp;
+    }
+}
 // eddyDissipationModel::correct: rtTurb = C_EDC*epsilon/max(k, SMALL), rtDiff = C_Diff*alpha/rho/delta^2, rt = max of the two;
 // wFuel = rho*min(Y_fuel, Y_O2/s)/deltaT/C_Stiff*(1 - exp(-C_Stiff*deltaT*rt)); Qdot = qFuel*wFuel; epsilon = Ce*k*sqrt(k)/delta
 __global__ void k_edc(long n, const double *__restrict__ rho, const double *__restrict__ k, const double *__restrict__ delta,
@@ -211,6 +238,26 @@ extern "C" int ffm_thermo_Cp_d(ffm_thermo *th, long n, const double *const *Y_d,
     FFM_HIP(hipSetDevice(th->ctx->device));
     if (n) hipLaunchKernelGGL(k_thermo_cp, dim3(tgrid(n)), dim3(256), 0, th->ctx->stream, n, th->t, y, T_d, Cp_d);
     FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+// ffm_thermo_correct_d + ffm_thermo_Cp_d as one launch without a read-back: fail_d (device int, never cleared here) is set to 1 where
+// thermo::T exceeds its iteration limit
+extern "C" int ffm_thermo_step_d(ffm_thermo *th, long n, const double *const *Y_d, const double *he_d, double *T_d, double *psi_d, double *mu_d,
+                                 double *alpha_d, double *Cp_d, int *fail_d)
+{
+    if (!th || n < 0 || !Y_d || !he_d || !T_d || !psi_d || !mu_d || !alpha_d || !Cp_d || !fail_d) return FFM_ERR_ARG;
+    ThermoPtrs y; FFM_TRY(ptrs_of(th, Y_d, y));
+    FFM_HIP(hipSetDevice(th->ctx->device));
+    if (n) hipLaunchKernelGGL(k_thermo_step, dim3(tgrid(n)), dim3(256), 0, th->ctx->stream, n, th->t, y, he_d, T_d, psi_d, mu_d, alpha_d, Cp_d, fail_d);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+// the table's species count and (W: nullable, [nSpecies]) molecular weights
+extern "C" int ffm_thermo_species(const ffm_thermo *th, int *nSpecies, double *W)
+{
+    if (!th || !nSpecies) return FFM_ERR_ARG;
+    *nSpecies = th->t.n;
+    if (W) for (int i = 0; i < th->t.n; i++) W[i] = th->t.W[i];
     return FFM_OK;
 }
 extern "C" int ffm_edc_correct_d(ffm_ctx *ctx, long n, const double *rho_d, const double *k_d, const double *delta_d, const double *alpha_d,

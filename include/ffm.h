@@ -663,6 +663,7 @@ int ffm_solve_ordered_staged_d(ffm_ldu *ldu, const ffm_flow_order *o, double *ps
  * the synthetic buoyant-plume box of SURVEY 8(d): rhoEqn, UEqn, YEEqn, 2 x pEqn in
  * the order of solver/fireFoam.C:97-119.  bench.py's workload.                */
 typedef struct ffm_plume ffm_plume;
+typedef struct ffm_thermo ffm_thermo;      /* the thermo package below (ffm_thermo_create): ffm_plume_set_thermo borrows one */
 int ffm_plume_create(ffm_ctx *ctx, int nx, int ny, int nz, double h, double deltaT, ffm_plume **out);
 /* one rank's block [lo,hi) of the global box; nbrRank[6] = rank across the -x,+x,-y,+y,-z,+z side or -1
  * (physical boundary).  Needs ffm_comm_init / ffm_comm_init_host when any neighbour exists.            */
@@ -694,6 +695,44 @@ int ffm_plume_set_solvers(ffm_plume *plume, int stecklerSelection);
  * data, as the plume itself is: the check is oracle/steckler_case.py's kEqn restated on the plume box (tests/plume_keqn_ref.py).  */
 int ffm_plume_set_turbulence(ffm_plume *plume, int model /* 0 none (default), 1 kEqn */, double Ck, double Ce, double Prt, double kInlet,
                              const double *k0);
+/* The thermo model of the step: NULL (default) the stand-in -- perfect gas with one constant Cp, T = Tref + h/Cp, constant mu and mu/Pr
+ * -- or a handle of ffm_thermo_create: hePsiThermo<reactingMixture<sutherland<janaf<perfectGas<specie>>>>, sensibleEnthalpy>
+ * (cases/steckler/constant/thermophysicalProperties:18-27).  With a handle
+ *   thermo.correct() (solver/YEEqn.H:114 after the enthalpy solve; solver/phrghEqn.H inside the five hydrostatic correctors; at set-up):
+ *          cell mixture by progressive mass-fraction sum, T by thermo::T's Newton iteration from the old T, psi, sutherland mu,
+ *          modified-Eucken alpha and Cp at the new T, ghost cells included -- one pass (ffm_thermo_step_d).  "maximum number of
+ *          iterations exceeded" is accumulated on the device and read at the synchronisation that closes the step (or the set-up):
+ *          ffm_plume_step then returns FFM_ERR_ARG; the step has no further host synchronisation;
+ *   UEqn   (solver/UEqn.H:7): laminar - fvm::laplacian(interpolate(mu), U); with kEqn rho nuEff = rho (nut + mu/rho), mu the cell field;
+ *   YEEqn  (solver/YEEqn.H:12): alphaEff = alpha (+ alphat), one diffusivity for the species and h;
+ *   inlet  h = Hs(inlet mixture, T_IN) by ffm_thermo_he_d's arithmetic on the inlet faces' species values, in place of Cp (T_IN - Tref);
+ *          the inletOutlet value hAmb stays the caller's.
+ * Patches: rho, psi, mu, alpha keep the plume's stand-in convention, zero-gradient copies of the cell values; the patch types of
+ * heThermo (fixed T, mixedEnergy) stay with the class layer (include/fireFoamHandles.H).
+ * The handle is BORROWED (created on the plume's context): it outlives the plume or is unset (NULL) first.  It must hold exactly the plume's five species in the
+ * plume's order (O2, H2O, C3H8, CO2, N2; checked by count and molecular weight): anything else is FFM_ERR_ARG.  Allowed only while no
+ * step has been taken since creation or ffm_plume_set_initial_state -- the hydrostatic start depends on psi -- otherwise FFM_ERR_ARG.
+ * The call redoes the start-up from the Y and h the handle holds: T = Tref (the Newton start: thermo::T's result depends on it, a
+ * restart must not inherit an old run's T), thermo.correct(), rho = psi p, the hydrostatic initialisation with the selected thermo in
+ * its correctors; with kEqn on, correctNut() again with the new rho.  ffm_plume_set_initial_state on a handle with the model on does
+ * the same: the two call orders give the same bytes.  Excludes ffm_plume_set_radiation* (radiation->Sh is written with the constant
+ * Cp): FFM_ERR_UNSUPPORTED in whichever order they are called.  A refused call leaves the handle unchanged.  Fields "mu", "alpha",
+ * "Cp" become readable with ffm_plume_get_field while the model is on, and with them "wFuel", "Qdot" (the last step's, whichever
+ * combustion model formed them; with neither model on they are scratch of the step and refused).  Unpinned by reference data, as the plume itself is: the check
+ * is oracle/thermo.py's package restated on the plume box (tests/plume_thermo_ref.py). */
+int ffm_plume_set_thermo(ffm_plume *plume, ffm_thermo *thermo /* NULL: the stand-in (default) */);
+/* The combustion model of the step: 0 (default) the stand-in rate rho min(Yf, YO2/s)/tau, 1 the reference's eddyDissipationModel
+ * (lib/thermophysicalModels/combustionModels/eddyDissipationModel/eddyDissipationModel.C:93-149; cases/steckler/constant/
+ * combustionProperties: C_EDC 4, C_Diff 0, C_Stiff 1) at combustion->correct() of solver/YEEqn.H: ffm_edc_correct_d's expressions with the
+ * step's deltaT, kEqn's Ce and delta (epsilon = Ce k sqrt(k)/delta) and the thermo model's alpha (mu/Pr with the stand-in thermo);
+ * wFuel and Qdot = qFuel wFuel, readable as fields "wFuel", "Qdot".  s, qFuel: singleStepReactingMixture's; the species'
+ * stoichiometric factors stay the plume's.  No patch values: the rate is a cell field.  Callable between steps.  Model 1 needs the
+ * kEqn model (ffm_plume_set_turbulence) to be on: FFM_ERR_UNSUPPORTED without it, and ffm_plume_set_turbulence(.., 0, ..) is
+ * refused the same way while model 1 is on.  FFM_ERR_ARG with the handle unchanged: an unknown model, a non-finite value, s <= 0,
+ * C_Stiff <= 0, C_EDC < 0, C_Diff < 0, qFuel <= 0.  EDC with radiation on is as untested as kEqn with radiation is.  Unpinned by
+ * reference data, as the plume itself is (tests/plume_thermo_ref.py restates oracle/steckler_case.py's edc_correct). */
+int ffm_plume_set_combustion(ffm_plume *plume, int model /* 0 stand-in (default), 1 the reference's EDC */,
+                             double C_EDC, double C_Diff, double C_Stiff, double s, double qFuel);
 /* SURVEY 8(f) N1 stand-in: the reference's radiation->correct() (solver/YEEqn.H:80; fvDOM with nPhi 2, nTheta 4, solverFreq 100,
  * cases/steckler/constant/radiationProperties:32-40) as 4*nPhi*nTheta upwind ray-transport solves every `solverFreq` steps
  * (0 = off, the default).  dAve[3*nRay], omega[nRay]: the rays' mean directions and solid angles as fvDOM.C:55-90 builds
@@ -841,7 +880,6 @@ int ffm_pyro_destroy(ffm_pyro *p);
  * ffm_edc_correct_d: the reference's eddyDissipationModel::correct (lib/thermophysicalModels/combustionModels/
  *   eddyDissipationModel/eddyDissipationModel.C:93-149) with kEqn::epsilon = Ce k sqrt(k)/delta: wFuel and Qdot = qFuel wFuel.
  * ffm_les_keqn_nut_d: kEqn::correctNut (nut = Ck sqrt(k) delta) and alphat = rho nut/Prt (alphat_d null: nut only). */
-typedef struct ffm_thermo ffm_thermo;
 int ffm_thermo_create(ffm_ctx *ctx, int nSpecies, const double *W, const double *Tlow, const double *Thigh, const double *Tcommon,
                       const double *highCpCoeffs, const double *lowCpCoeffs, const double *As, const double *Ts, double RR,
                       ffm_thermo **out);
@@ -854,6 +892,13 @@ int ffm_thermo_properties_d(ffm_thermo *th, long n, const double *const *Y_d, co
 /* Cp of the mixture at T (heThermo::Cp(p, T, patchi): kappaEff of compressible::thermalBaffle1D -- cases/steckler/0/T:51-82 --
  * and the gradient term of mixedEnergy::updateCoeffs) */
 int ffm_thermo_Cp_d(ffm_thermo *th, long n, const double *const *Y_d, const double *T_d, double *Cp_d);
+/* thermo.correct() of the compiled time step: ffm_thermo_correct_d + ffm_thermo_Cp_d as ONE streaming pass that forms the cell
+ * mixture once and writes T (in: the Newton start), psi, mu, alpha and Cp at the new T -- bitwise the pair's values.  No read-back
+ * and no synchronisation: *fail_d (a device int the caller owns and clears) is set to 1 where thermo::T exceeds its iteration limit. */
+int ffm_thermo_step_d(ffm_thermo *th, long n, const double *const *Y_d, const double *he_d, double *T_d, double *psi_d, double *mu_d,
+                      double *alpha_d, double *Cp_d, int *fail_d);
+/* the table's species count and, W non-NULL, its molecular weights W[nSpecies] */
+int ffm_thermo_species(const ffm_thermo *th, int *nSpecies, double *W);
 int ffm_thermo_destroy(ffm_thermo *th);
 int ffm_edc_correct_d(ffm_ctx *ctx, long n, const double *rho_d, const double *k_d, const double *delta_d, const double *alpha_d,
                       const double *Yfuel_d, const double *YO2_d, double s, double deltaT, double Ce, double C_EDC, double C_Diff,
@@ -883,6 +928,13 @@ int ffm_les_keqn_terms(ffm_mesh *m, const double *const *g, const double *nut, c
                        const double *delta, const double *phi_f, const double *phi_b, double Ce, double *su, double *su2, double *sp);
 int ffm_les_face_diffusivity(ffm_mesh *m, int mode, double c0, const double *rho, const double *rho_b, const double *x, const double *x_b,
                              double *out_f, double *out_b);
+/* ffm_les_face_diffusivity with the laminar part taken from a cell field c (sutherland mu, modified-Eucken alpha of
+ *   ffm_plume_set_thermo) in place of the constant c0; the patch value of c is its zero-gradient copy c[owner cell]:
+ *   mode 0  rho*(x + c/rho)   mode 1  c + x   x == NULL (x_b, rho, rho_b then unread; either mode): c itself, i.e. plain linear
+ *   interpolation of c and its zero-gradient patch values (the laminar case).  Every row-width bucket.  Bitwise equal to the cell
+ *   expression + ffm_fvc_interpolate(NULL, .). */
+int ffm_les_face_diffusivity_v(ffm_mesh *m, int mode, const double *c, const double *rho, const double *rho_b, const double *x,
+                               const double *x_b, double *out_f, double *out_b);
 int ffm_les_keqn_update(ffm_mesh *m, long n, double kMin, double Ck, double Prt, double *k, const double *delta, const double *rho,
                         double *nut, double *alphat);
 
