@@ -242,6 +242,8 @@ def lib():
         "ffm_fvdom_ray_assemble_d": ([vp, hp] + [C.c_double] * 3 + [dp] * 9, C.c_int),
         "ffm_fvdom_wall_coeffs_d": ([vp, C.c_int, C.c_int, hp, hp, C.c_double] + [dp] * 8, C.c_int),
         "ffm_fvdom_sum_rays_d": ([vp, C.c_int, dp, dp], C.c_int),
+        "ffm_radiation_sh_d": ([vp, C.c_long] + [C.c_double] * 3 + [dp] * 5 + [C.c_double, dp, dp], C.c_int),
+        "ffm_fvdom_G_d": ([vp, C.c_long, C.c_int, dp, dp, dp], C.c_int),
         "ffm_mesh_nboundary": ([vp], C.c_int),
         "ffm_mesh_nnative": ([vp], C.c_int),
         "ffm_faces_to_native": ([vp, hp, dp], C.c_int),
@@ -279,6 +281,7 @@ def lib():
         "ffm_plume_set_radiation": ([vp, C.c_int, C.c_int, C.c_int, vp, vp], C.c_int),
         "ffm_plume_set_radiation_model": ([vp, C.c_double, C.c_double, C.c_double], C.c_int),
         "ffm_plume_set_radiation_ordering": ([vp, C.c_int], C.c_int),
+        "ffm_plume_set_radiation_thermo": ([vp, C.c_int], C.c_int),
         "ffm_plume_ray_system": ([vp, C.c_int, C.c_int, hp, hp, hp, hp], C.c_int),
         "ffm_ray_schedule": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, hp, ip, C.c_int], C.c_int),
         "ffm_ray_octant": ([hp], C.c_int),
@@ -951,6 +954,11 @@ class Plume:
         """0: every ray a PBiCGStab solve over all ranks; 1: the staged direction-ordered sweep over the blocks of a decomposed box
         (ffm_plume_set_radiation_ordering)"""
         _check(lib().ffm_plume_set_radiation_ordering(self.h, int(mode)), "ffm_plume_set_radiation_ordering")
+
+    def set_radiation_thermo(self, on=True):
+        """opt-in: set_thermo and set_radiation / set_radiation_model / set_radiation_ordering accept each other, radiation->Sh then divides
+        by the thermo package's Cp field (ffm_plume_set_radiation_thermo).  Off is refused while both are on"""
+        _check(lib().ffm_plume_set_radiation_thermo(self.h, 1 if on else 0), "ffm_plume_set_radiation_thermo")
 
     def ray_system(self, ray, fused):
         """(diag, upper, lower, source) of one ray's system by the operator chain or by the one-pass kernel (ffm_plume_ray_system; tests)"""

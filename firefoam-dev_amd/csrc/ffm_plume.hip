@@ -449,8 +449,8 @@ extern "C" int ffm_plume_set_thermo(ffm_plume *P, ffm_thermo *thermo)
         for (int i = 0; i < NSP; i++) if (!(std::fabs(W[i] - WMOL[i]) <= 1e-3 * WMOL[i])) {
             ffm_set_error("ffm_plume_set_thermo: species %d has molecular weight %g, the plume's %s %g", i, W[i], SPN[i], WMOL[i]); return FFM_ERR_ARG;
         }
-        if (P->radFreq > 0 || P->radCoupled || P->radOrdering != 0) {
-            ffm_set_error("ffm_plume_set_thermo: not with ffm_plume_set_radiation* on (radiation->Sh is written with the constant Cp)"); return FFM_ERR_UNSUPPORTED;
+        if (!P->radThermo && (P->radFreq > 0 || P->radCoupled || P->radOrdering != 0)) {
+            ffm_set_error("ffm_plume_set_thermo: not with ffm_plume_set_radiation* on (ffm_plume_set_radiation_thermo is off)"); return FFM_ERR_UNSUPPORTED;
         }
     }
     PL_HIP(hipSetDevice(P->ctx->device));
@@ -472,6 +472,17 @@ extern "C" int ffm_plume_set_thermo(ffm_plume *P, ffm_thermo *thermo)
     FFM_TRY(plume_model_buffers(P));
     FFM_TRY(plume_inlet_enthalpy(P));
     return plume_startup(P, true);
+}
+// the rays and radiation->Sh together with the thermo package: see include/ffm.h
+extern "C" int ffm_plume_set_radiation_thermo(ffm_plume *P, int on)
+{
+    if (!P) return FFM_ERR_ARG;
+    if (!on && P->thermo && (P->radFreq > 0 || P->radCoupled || P->radOrdering != 0)) {
+        ffm_set_error("ffm_plume_set_radiation_thermo: the thermo package and ffm_plume_set_radiation* are both on; unset one of them first");
+        return FFM_ERR_UNSUPPORTED;
+    }
+    P->radThermo = on != 0;
+    return FFM_OK;
 }
 // the combustion model of the step: see include/ffm.h
 extern "C" int ffm_plume_set_combustion(ffm_plume *P, int model, double C_EDC, double C_Diff, double C_Stiff, double s, double qFuel)
@@ -508,7 +519,7 @@ extern "C" int ffm_plume_get_field(ffm_plume *P, const char *name, double *out)
     else if (n == "mu") src = P->mu; else if (n == "alpha") src = P->alpha; else if (n == "Cp") src = P->Cp;      // (null while the stand-in thermo is on)
     else if (n == "wFuel") src = P->wFuelOwn; else if (n == "Qdot") src = P->QdotOwn;      // (null while both are scratch slots: no model of theirs on)
     else if (n == "k") src = P->kSgs; else if (n == "nut") src = P->nut; else if (n == "alphat") src = P->alphat;      // (null while the model is off)
-    else if (n == "G") src = P->G; else if (n == "ShSu") src = P->radShSu; else if (n == "ShSp") src = P->radShSp; else if (n == "radE") src = P->radE;
+    else if (n == "G") src = P->G; else if (n == "ShSu") src = P->radHaveSh ? P->radShSu : nullptr; else if (n == "ShSp") src = P->radHaveSh ? P->radShSp : nullptr; else if (n == "radE") src = P->radE;      // (ShSu, ShSp: null before the first radiation->Sh pass)
     else if (n.size() > 1 && n[0] == 'I' && isdigit((unsigned char)n[1])) { const int i = atoi(n.c_str() + 1); if (i < (int)P->I.size()) src = P->I[i]; }
     else for (int i = 0; i < NSP; i++) if (n == SPN[i]) src = P->Y[i];
     if (!src) { ffm_set_error("unknown field %s", name); return FFM_ERR_ARG; }

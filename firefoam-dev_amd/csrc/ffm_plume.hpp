@@ -112,6 +112,11 @@ struct ffm_plume {
     // coefficient, emission E = RadFraction*Qdot with the radScaling of constRadFractionEmission::ECont
     bool radCoupled = false; double radA = 0.1, Ehrr1 = 0.0, Ehrr2 = 0.0;
     double *radE = nullptr, *radShSu = nullptr, *radShSp = nullptr; bool radHaveG = false;
+    bool radHaveSh = false;                // radShSu / radShSp hold a source pass ("ShSu", "ShSp" are readable)
+    // fvDOM::updateG as one pass (ffm_fvdom_G_d): the rays' pointers and solid angles on the device, for radTabRays rays
+    double **radIdd = nullptr, *radOmegaD = nullptr; int radTabRays = 0;
+    // ffm_plume_set_radiation_thermo: the rays and radiation->Sh accepted together with the thermo package (Sh then reads the Cp field)
+    bool radThermo = false;
     bool stecklerSolvers = false;          // transport equations with smoothSolver + symGaussSeidel, maxIter 10
                                            // (cases/steckler/system/fvSolution:49-62) instead of PBiCGStab + DILU
     // LES kEqn sub-grid model (ffm_plume_set_turbulence; cases/steckler/constant/turbulenceProperties:18-30): 0 = none, every pointer null

@@ -45,6 +45,12 @@ static int ray_assemble_ops(ffm_plume *P, int i, const double *Ee)
     return ffm_fvm_add_boundary(m, P->ic[0], P->bc[0], P->diag, su, nullptr, P->dWork, P->sWork);
 }
 
+// fvDOM::updateG over the cells (ghost cells included: every rank holds its neighbours' rays there) in one pass
+static int rad_update_G(ffm_plume *P)
+{
+    return ffm_fvdom_G_d(P->ctx, P->N, (int)P->rayOmega.size(), P->radIdd, P->radOmegaD, P->G);
+}
+
 // the axis whose direction component has the minority sign; none (-1) when all three agree (the cell order is then already
 // an upwind or a downwind order of the ray and DILU is exact)
 static int ray_flip_axis(const ffm_plume *P, int i)
@@ -65,7 +71,7 @@ static int ray_flip_axis(const ffm_plume *P, int i)
 // waits for another outside that exchange.
 static int radiation_correct_staged(ffm_plume *P, const double *Ee)
 {
-    ffm_mesh *m = P->mesh; const int N = P->N, nOwn = P->nOwn; const long nNat = P->nNat;
+    ffm_mesh *m = P->mesh; const int nOwn = P->nOwn; const long nNat = P->nNat;
     const int nTicks = (int)P->radTick.size();
     const bool timing = getenv("FFM_TIMING") != nullptr;          // wall time of the ticks' exchanges (ghost exchange + the copies into the rays' ghost layers)
     double tExch = 0.0;
@@ -111,21 +117,19 @@ static int radiation_correct_staged(ffm_plume *P, const double *Ee)
         if (timing) { PL_HIP(hipStreamSynchronize(P->ctx->stream)); tExch += FfmStageTimer::now() - tx0; }
     }
     if (timing) fprintf(stderr, "ffm timing: staged ray sweep rank %d: %d ticks, exchanges %.4f s in all (%.3f ms per tick)\n", P->ctx->rank, nTicks, tExch, nTicks ? 1e3 * tExch / nTicks : 0.0);
-    // G = sum Ii omega in ray-index order, as the unstaged sweep adds it
-    double *G = P->G;
-    for (int i = 0; i < (int)P->rayOmega.size(); i++) {
-        const double *Ii = P->I[i]; const double omega = P->rayOmega[i];
-        forN(P, N, [=] __device__(long c) { G[c] = G[c] + Ii[c] * omega; });
-    }
-    return FFM_OK;
+    // G = sum Ii omega in ray-index order from zero, as the unstaged sweep adds it: one pass over the rays
+    return rad_update_G(P);
 }
 
 int radiation_correct(ffm_plume *P)
 {
     const int N = P->N, B = P->B; const long nNat = P->nNat;
     const double Ib = SIGMA_SB * ((TREF * TREF) * (TREF * TREF)) / M_PI;
+    // the fused step on one block: every ray assembled in one pass, G formed once after the last ray.  The per-operator step, and
+    // the block-Jacobi solves of a decomposed box, keep the operator chain and add each ray to G as it is solved -- the same bytes
+    const bool onePass = P->fused && P->oneBlock;
     double *G = P->G, *ref = P->radRef;
-    forN(P, N, [=] __device__(long c) { G[c] = 0.0; });
+    if (!onePass && !P->radStaged) forN(P, N, [=] __device__(long c) { G[c] = 0.0; });
     forN(P, B, [=] __device__(long k) { ref[k] = Ib; });
     const double *Ee = nullptr;
     if (P->radCoupled) {      // absorptionEmission->ECont(): E = RadFraction*Qdot (constRadFractionEmission.C, radScaling)
@@ -139,7 +143,9 @@ int radiation_correct(ffm_plume *P)
     const int nRay = (int)P->rayOmega.size();
     for (int i = 0; i < nRay; i++) {
         const double omega = P->rayOmega[i];
-        FFM_TRY(ray_assemble_ops(P, i, Ee));
+        if (onePass) FFM_TRY(ffm_fvdom_ray_assemble_d(P->mesh, &P->rayD[3 * i], omega, P->radA, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr, P->upper, P->lower,
+                                                      P->dWork, P->sWork));
+        else FFM_TRY(ray_assemble_ops(P, i, Ee));
         char nm[16]; snprintf(nm, sizeof(nm), "I%d", i);
         const int flip = P->radOrdered ? ray_flip_axis(P, i) : -1;
         if (flip < 0) {
@@ -159,8 +165,9 @@ int radiation_correct(ffm_plume *P)
         }
         FFM_TRY(HX(P, P->I[i]));
         const double *Ii = P->I[i];
-        forN(P, N, [=] __device__(long c) { G[c] = G[c] + Ii[c] * omega; });
+        if (!onePass) forN(P, N, [=] __device__(long c) { G[c] = G[c] + Ii[c] * omega; });
     }
+    if (onePass) FFM_TRY(rad_update_G(P));
     P->radHaveG = true;
     return FFM_OK;
 }
@@ -302,7 +309,7 @@ static int rad_prepare(ffm_plume *P)
 extern "C" int ffm_plume_set_radiation(ffm_plume *P, int solverFreq, int nPhi, int nTheta, const double *dAve, const double *omega)
 {
     if (!P || solverFreq < 0 || nPhi < 1 || nTheta < 1 || ((dAve == nullptr) != (omega == nullptr))) return FFM_ERR_ARG;
-    if (P->thermo) { ffm_set_error("ffm_plume_set_radiation: not with ffm_plume_set_thermo on (radiation->Sh is written with the constant Cp)"); return FFM_ERR_UNSUPPORTED; }
+    if (P->thermo && !P->radThermo) { ffm_set_error("ffm_plume_set_radiation: not with ffm_plume_set_thermo on (ffm_plume_set_radiation_thermo is off)"); return FFM_ERR_UNSUPPORTED; }
     PL_HIP(hipSetDevice(P->ctx->device));
     const int nRay = 4 * nPhi * nTheta;
     P->rayD.assign(3 * (size_t)nRay, 0.0); P->rayOmega.assign(nRay, 0.0);
@@ -324,6 +331,15 @@ extern "C" int ffm_plume_set_radiation(ffm_plume *P, int solverFreq, int nPhi, i
         P->radJb = dalloc(P, P->B); P->radF = dalloc(P, P->B); P->radRef = dalloc(P, P->B);
         if (!P->G || !P->radSrc || !P->radJ || !P->radW || !P->radJb || !P->radF || !P->radRef) return FFM_ERR_HIP;
     }
+    // the rays' pointers and solid angles for ffm_fvdom_G_d
+    static_assert(sizeof(double *) == sizeof(double), "the pointer table is taken from the pool of doubles");
+    if (P->radTabRays < nRay) {
+        P->radIdd = (double **)dalloc(P, nRay); P->radOmegaD = dalloc(P, nRay);
+        if (!P->radIdd || !P->radOmegaD) return FFM_ERR_HIP;
+        P->radTabRays = nRay;
+    }
+    FFM_TRY(ffm_h2d(P->ctx, P->radIdd, P->I.data(), sizeof(double *) * nRay));
+    FFM_TRY(ffm_h2d(P->ctx, P->radOmegaD, P->rayOmega.data(), sizeof(double) * nRay));
     FFM_TRY(rad_prepare(P));
     P->radFreq = solverFreq;
     return FFM_OK;
@@ -335,7 +351,7 @@ extern "C" int ffm_plume_set_radiation(ffm_plume *P, int solverFreq, int nPhi, i
 extern "C" int ffm_plume_set_radiation_ordering(ffm_plume *P, int mode)
 {
     if (!P || (mode != 0 && mode != 1)) return FFM_ERR_ARG;
-    if (P->thermo) { ffm_set_error("ffm_plume_set_radiation_ordering: not with ffm_plume_set_thermo on (radiation->Sh is written with the constant Cp)"); return FFM_ERR_UNSUPPORTED; }
+    if (P->thermo && !P->radThermo) { ffm_set_error("ffm_plume_set_radiation_ordering: not with ffm_plume_set_thermo on (ffm_plume_set_radiation_thermo is off)"); return FFM_ERR_UNSUPPORTED; }
     PL_HIP(hipSetDevice(P->ctx->device));
     if (mode == 1 && !P->oneBlock) {
         const int *nb = P->nbrRank; const int rank = P->ctx->rank, world = P->ctx->nRanks;
@@ -369,7 +385,7 @@ extern "C" int ffm_plume_set_radiation_ordering(ffm_plume *P, int mode)
 extern "C" int ffm_plume_set_radiation_model(ffm_plume *P, double absorption, double Ehrr1, double Ehrr2)
 {
     if (!P || absorption < 0 || Ehrr1 < 0 || Ehrr2 < 0) return FFM_ERR_ARG;
-    if (P->thermo) { ffm_set_error("ffm_plume_set_radiation_model: not with ffm_plume_set_thermo on (radiation->Sh is written with the constant Cp)"); return FFM_ERR_UNSUPPORTED; }
+    if (P->thermo && !P->radThermo) { ffm_set_error("ffm_plume_set_radiation_model: not with ffm_plume_set_thermo on (ffm_plume_set_radiation_thermo is off)"); return FFM_ERR_UNSUPPORTED; }
     PL_HIP(hipSetDevice(P->ctx->device));
     if (!P->radE) { P->radE = dalloc(P, P->N); P->radShSu = dalloc(P, P->N); P->radShSp = dalloc(P, P->N); }
     if (!P->radE || !P->radShSu || !P->radShSp) return FFM_ERR_HIP;

@@ -503,13 +503,16 @@ static int e_radiation_source(ffm_plume *P, const double **shSu, const double **
     double frac = 0.0;
     FFM_TRY(plume_rad_fraction(P, &frac));
     const double Rp = 4.0 * P->radA * SIGMA_SB, KA = P->radA;
-    double *su2 = P->radShSu, *sp2 = P->radShSp; const double *G = P->G, *T = P->T, *hh = P->hs, *Qd = P->Qdot;
-    forN(P, P->N, [=] __device__(long c) {
-        const double t = T[c], T3 = t * t * t;
+    // Cpv: the thermo package's cell field (thermo.correct() of the step before wrote it at the T read here), else the stand-in's constant
+    double *su2 = P->radShSu, *sp2 = P->radShSp; const double *G = P->G, *T = P->T, *hh = P->hs, *Qd = P->Qdot, *Cpf = P->thermo ? P->Cp : nullptr;
+    if (P->fused) FFM_TRY(ffm_radiation_sh_d(P->ctx, P->N, KA, SIGMA_SB, frac, G, T, hh, Qd, Cpf, CP, su2, sp2));
+    else forN(P, P->N, [=] __device__(long c) {
+        const double t = T[c], T3 = t * t * t, cp = Cpf ? Cpf[c] : CP;
         const double Ru = KA * G[c] - frac * Qd[c];
-        sp2[c] = 4.0 * Rp * T3 / CP;
-        su2[c] = Ru - Rp * T3 * (t - 4.0 * hh[c] / CP);
+        sp2[c] = 4.0 * Rp * T3 / cp;
+        su2[c] = Ru - Rp * T3 * (t - 4.0 * hh[c] / cp);
     });
+    P->radHaveSh = true;
     *shSu = su2; *shSp = sp2;
     return FFM_OK;
 }

@@ -154,3 +154,53 @@ extern "C" int ffm_fvdom_fold_ghost_inflow_d(ffm_mesh *m, int nCells, const int 
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
+
+// ------------------------------------------------------------------ radiation->Sh and fvDOM::updateG as cell passes ---
+// radiation->Sh(thermo, he) of solver/YEEqn.H:101 (radiationModel.C:229-244 with fvDOM's Rp = 4 a sigma, Ru = a G - E,
+// E = radFraction*Qdot of constRadFractionEmission::ECont): the two arrays the enthalpy assembly takes as su2 / sp.  One
+// streaming pass, 4 (5 with a Cp field) doubles read and 2 written per cell; the operation order is that of oracle/plume.py:464-468.
+__global__ void k_radiation_sh(long n, double KA, double Rp, double frac, const double *__restrict__ G, const double *__restrict__ T,
+                               const double *__restrict__ he, const double *__restrict__ Qdot, const double *__restrict__ Cp, double CpConst,
+                               double *__restrict__ su, double *__restrict__ sp)
+{
+    GRID_STRIDE(c, n) {
+        const double t = T[c], T3 = t * t * t, cp = Cp ? Cp[c] : CpConst;
+        const double Ru = KA * G[c] - frac * Qdot[c];
+        sp[c] = 4.0 * Rp * T3 / cp;
+        su[c] = Ru - Rp * T3 * (t - 4.0 * he[c] / cp);
+    }
+}
+extern "C" int ffm_radiation_sh_d(ffm_ctx *ctx, long n, double absorption, double sigma, double radFraction, const double *G_d, const double *T_d,
+                                  const double *he_d, const double *Qdot_d, const double *Cp_d, double CpConst, double *su_d, double *sp_d)
+{
+    if (!ctx || n < 0 || !G_d || !T_d || !he_d || !Qdot_d || !su_d || !sp_d) return FFM_ERR_ARG;
+    if (n == 0) return FFM_OK;
+    FFM_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_radiation_sh, dim3(sgrid(n)), dim3(256), 0, ctx->stream, n, absorption, 4.0 * absorption * sigma, radFraction, G_d, T_d, he_d,
+                       Qdot_d, Cp_d, CpConst, su_d, sp_d);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// fvDOM::updateG, cell part (fvDOM.C:697-718): G = sum Ii omega_i.  The sum of a cell is kept in a register and formed in ray-index
+// order from zero, ((0 + I_0 w_0) + I_1 w_1) + ..., which is what nRay passes G = G + I_i*omega_i over a zeroed G leave: every ray is
+// read once, G written once.  The ray pointers and omega are the same for all lanes (scalar loads); a lane's loads of a ray are
+// adjacent to its neighbours'.  The unroll keeps four rays' loads in flight, the additions stay in order.
+__global__ void k_fvdom_G(long n, int nRay, const double *const *__restrict__ I, const double *__restrict__ omega, double *__restrict__ G)
+{
+    GRID_STRIDE(c, n) {
+        double g = 0.0;
+#pragma unroll 4
+        for (int i = 0; i < nRay; i++) g = g + I[i][c] * omega[i];
+        G[c] = g;
+    }
+}
+extern "C" int ffm_fvdom_G_d(ffm_ctx *ctx, long n, int nRay, const double *const *I_dd, const double *omega_d, double *G_d)
+{
+    if (!ctx || n < 0 || nRay < 1 || !I_dd || !omega_d || !G_d) return FFM_ERR_ARG;
+    if (n == 0) return FFM_OK;
+    FFM_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_fvdom_G, dim3(sgrid(n)), dim3(256), 0, ctx->stream, n, nRay, I_dd, omega_d, G_d);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}

@@ -560,6 +560,21 @@ int ffm_fvdom_sum_rays_d(ffm_mesh *mesh, int nRay, const double *all, double *ou
 int ffm_fvdom_ray_assemble_d(ffm_mesh *mesh, const double *dAve3, double omega, double absorption, double sigma, const double *T,
                              const double *E, const double *ref_b, double *J_f, double *w_f, double *upper, double *lower,
                              double *diag, double *source);
+/* radiation->Sh(thermo, he) of solver/YEEqn.H:101 as one streaming pass over n cells (radiationModel.C:229-244; fvDOM/fvDOM.C:588 Rp, :612 Ru;
+ * E = radFraction*Qdot of constRadFractionEmission::ECont): with Rp = 4 absorption sigma, Ru = absorption G - radFraction*Qdot,
+ * T3 = T*T*T and Cp = Cp_d[c] where Cp_d is given, CpConst where it is NULL,
+ *   sp = 4.0*Rp*T3/Cp          (the coefficient of fvm::Sp(., he))
+ *   su = Ru - Rp*T3*(T - 4.0*he/Cp)
+ * in exactly this operation order (oracle/plume.py:464-468), no FMA contraction.  Reads and writes the first n entries of every
+ * array and nothing else; n == 0 is a no-op.  FFM_ERR_ARG: a NULL context or array (Cp_d excepted), n < 0. */
+int ffm_radiation_sh_d(ffm_ctx *ctx, long n, double absorption, double sigma, double radFraction, const double *G_d, const double *T_d,
+                       const double *he_d, const double *Qdot_d, const double *Cp_d /* nullable */, double CpConst, double *su_d,
+                       double *sp_d);
+/* fvDOM::updateG, cell part (fvDOM/fvDOM.C:697-718): G[c] = ((0 + I_0[c] omega_0) + I_1[c] omega_1) + ... in ray-index order,
+ * accumulated in a register: every ray is read once and G written once -- bitwise what nRay passes G = G + I_i*omega_i over a zeroed
+ * G leave.  I_dd: DEVICE array of nRay device pointers, omega_d: device [nRay].  Any nRay >= 1; n == 0 is a no-op.  FFM_ERR_ARG: a
+ * NULL argument, n < 0, nRay < 1. */
+int ffm_fvdom_G_d(ffm_ctx *ctx, long n, int nRay, const double *const *I_dd, const double *omega_d, double *G_d);
 /* One block of a decomposed mesh, a ray whose upstream neighbour blocks are done: for the owned cells cells[nCells] that have a
  * face towards a ghost cell g, source -= upper[face] I[g] in the row's face order, then both coefficients of the face are set to
  * 0 -- the inflow from the neighbour ranks becomes a known term and the rows couple owned cells only.                         */
@@ -715,8 +730,8 @@ int ffm_plume_set_turbulence(ffm_plume *plume, int model /* 0 none (default), 1 
  * The call redoes the start-up from the Y and h the handle holds: T = Tref (the Newton start: thermo::T's result depends on it, a
  * restart must not inherit an old run's T), thermo.correct(), rho = psi p, the hydrostatic initialisation with the selected thermo in
  * its correctors; with kEqn on, correctNut() again with the new rho.  ffm_plume_set_initial_state on a handle with the model on does
- * the same: the two call orders give the same bytes.  Excludes ffm_plume_set_radiation* (radiation->Sh is written with the constant
- * Cp): FFM_ERR_UNSUPPORTED in whichever order they are called.  A refused call leaves the handle unchanged.  Fields "mu", "alpha",
+ * the same: the two call orders give the same bytes.  Excludes ffm_plume_set_radiation* unless ffm_plume_set_radiation_thermo is on:
+ * FFM_ERR_UNSUPPORTED in whichever order they are called.  A refused call leaves the handle unchanged.  Fields "mu", "alpha",
  * "Cp" become readable with ffm_plume_get_field while the model is on, and with them "wFuel", "Qdot" (the last step's, whichever
  * combustion model formed them; with neither model on they are scratch of the step and refused).  Unpinned by reference data, as the plume itself is: the check
  * is oracle/thermo.py's package restated on the plume box (tests/plume_thermo_ref.py). */
@@ -747,6 +762,20 @@ int ffm_plume_set_radiation(ffm_plume *plume, int solverFreq, int nPhi, int nThe
  * EEqn gets radiation->Sh(thermo, he) = Ru - fvm::Sp(4 Rp T^3/Cpv, he) - Rp T^3 (T - 4 he/Cpv), Rp = 4 a sigma, Ru = a G - E
  * (radiationModel.C:229-244; solver/YEEqn.H:101).  Without this call the rays keep the round-1 stand-in (a = 0.1, no E, no Sh). */
 int ffm_plume_set_radiation_model(ffm_plume *plume, double absorption, double Ehrr1, double Ehrr2);
+/* Opt-in (default 0): the fvDOM rays and radiation->Sh together with the thermo package of ffm_plume_set_thermo.  On, ffm_plume_set_thermo
+ * and ffm_plume_set_radiation / _model / _ordering accept each other in either call order (ffm_plume_set_thermo keeps its own rules), and
+ *   radiation->Sh(thermo, he) (solver/YEEqn.H:101) divides by thermo.Cpv(): the Cp field thermo.correct() wrote (ffm_radiation_sh_d with
+ *          Cp_d), in the separate EEqn and where h is the fifth lock-step system;
+ *   the rays (radiativeIntensityRay.C:267-322) read the package's T; E = RadFraction*Qdot with Qdot of the selected combustion model;
+ *   RadFraction, the ambient black-body inflow and the zero-gradient outflow of the stand-in are unchanged; both orderings of a
+ *          decomposed box run.
+ * Off, the setters refuse each other as before.  With the switch on and the thermo package off the step is that of a handle that never
+ * saw the switch.  Turning it off while the thermo package and any of ffm_plume_set_radiation* are on: FFM_ERR_UNSUPPORTED, the handle
+ * unchanged.  "ShSu" / "ShSp" (ffm_plume_get_field) are the last radiation->Sh pass, an error before the first.  Unpinned by reference
+ * data, as the plume itself is: the check is tests/plume_radiation_ref.py.
+ * Not here: greyDiffusiveRadiation walls (they stay with the fvDOM handle of include/fireFoamHandles.H), a device-resident RadFraction,
+ * wide-band models, rays pipelined against each other. */
+int ffm_plume_set_radiation_thermo(ffm_plume *plume, int on);
 /* How the rays are solved on a block of a decomposed box.  0 (default): every ray is a block-Jacobi PBiCGStab + DILU solve over
  * all ranks.  1: the staged, direction-ordered sweep -- the ranks walk the ticks of ffm_ray_schedule; in a tick a rank assembles
  * at most one ray (ffm_fvdom_ray_assemble_d), moves the inflow from its upstream neighbours' ghost values into the source
