@@ -155,8 +155,18 @@ int ffm_allreduce_minmax(ffm_ctx *c, int slot, int isMax, int n)
 extern "C" int ffm_ldu_set_interfaces(ffm_ldu *A, int nPatches, const int *patchSizes, const int *const *faceCells,
                                       const double *const *bouCoeffs, const double *const *intCoeffs, const int *neighbRank)
 {
-    if (!A || nPatches < 0 || (nPatches && (!patchSizes || !faceCells || !bouCoeffs || !neighbRank))) return FFM_ERR_ARG;
+    if (!A) return FFM_ERR_ARG;
     ffm_ctx *c = A->ctx;
+    // every check comes before anything is stored: a refused call leaves the matrix with no interfaces at all, never with
+    // the patches that preceded the bad one (an Amul would then exchange their sizes through buffers that are gone)
+    int bad = FFM_OK;
+    if (nPatches < 0 || (nPatches && (!patchSizes || !faceCells || !bouCoeffs || !neighbRank))) { ffm_set_error("ffm_ldu_set_interfaces: %d patches or a null argument", nPatches); bad = FFM_ERR_ARG; }
+    for (int p = 0; !bad && p < nPatches; p++) {
+        if (patchSizes[p] < 0 || neighbRank[p] < 0 || neighbRank[p] >= std::max(c->nRanks, 1)) { ffm_set_error("interface %d: bad size or rank", p); bad = FFM_ERR_ARG; }
+        else if (patchSizes[p] && (!faceCells[p] || !bouCoeffs[p])) { ffm_set_error("interface %d: null array", p); bad = FFM_ERR_ARG; }
+        for (int i = 0; !bad && i < patchSizes[p]; i++)
+            if (faceCells[p][i] < 0 || faceCells[p][i] >= A->nCells) { ffm_set_error("interface %d: faceCell out of range", p); bad = FFM_ERR_ARG; }
+    }
     hipStreamSynchronize(c->stream);
     hipFree(A->ifFaceCells); hipFree(A->ifBou); hipFree(A->ifInt); hipFree(A->haloSend); hipFree(A->haloRecv);
     hipFree(A->ifCell); hipFree(A->ifCellStart); hipFree(A->ifItem);
@@ -165,23 +175,21 @@ extern "C" int ffm_ldu_set_interfaces(ffm_ldu *A, int nPatches, const int *patch
     A->ifFaceCells = nullptr; A->ifBou = A->ifInt = A->haloSend = A->haloRecv = nullptr;
     A->ifCell = A->ifCellStart = A->ifItem = nullptr;
     A->ifaces.clear(); A->ifaceTags.clear(); A->haloTotal = 0; A->nIfCells = 0;
+    if (bad) return bad;
     if (!nPatches) return FFM_OK;
     // old -> new cell map
     std::vector<int> oldToNew(A->nCells);
     for (int i = 0; i < A->nCells; i++) oldToNew[A->h_newToOldCell[i]] = i;
     int total = 0;
     for (int p = 0; p < nPatches; p++) {
-        if (patchSizes[p] < 0 || neighbRank[p] < 0 || neighbRank[p] >= std::max(c->nRanks, 1)) { ffm_set_error("interface %d: bad size or rank", p); return FFM_ERR_ARG; }
         ffm_iface f; f.size = patchSizes[p]; f.nbrRank = neighbRank[p]; f.offset = total; total += f.size;
         A->ifaces.push_back(f);
     }
     A->haloTotal = total;
     std::vector<int> fc(total); std::vector<double> bou(total), in(total);
     for (int p = 0; p < nPatches; p++) for (int i = 0; i < patchSizes[p]; i++) {
-        const int oc = faceCells[p][i];
-        if (oc < 0 || oc >= A->nCells) { ffm_set_error("interface %d: faceCell out of range", p); A->ifaces.clear(); A->haloTotal = 0; return FFM_ERR_ARG; }
         const int k = A->ifaces[p].offset + i;
-        fc[k] = oldToNew[oc]; bou[k] = bouCoeffs[p][i];
+        fc[k] = oldToNew[faceCells[p][i]]; bou[k] = bouCoeffs[p][i];
         in[k] = (intCoeffs && intCoeffs[p]) ? intCoeffs[p][i] : bouCoeffs[p][i];
     }
     // group packed items by cell, keeping (patch, face) order inside a cell

@@ -283,6 +283,16 @@ extern "C" int ffm_gamg_face_area_pair_weights(int nFaces, const double *Sf, dou
 }
 
 // Build the level hierarchy for the matrix `finest` (created from the same lowerAddr / upperAddr) and one ffm_ldu per coarse level.
+// the hierarchy couples the ranks through ghost cells on every level; processor interfaces would be left behind on the finest one.
+// Asked at creation and again wherever the finest matrix is used: interfaces may have been set on it since
+static int refuse_interfaces(const ffm_ldu *finest)
+{
+    if (finest->ifaces.empty()) return FFM_OK;
+    ffm_set_error("GAMG: the matrix carries processor interfaces (ffm_ldu_set_interfaces), which the coarse levels do not agglomerate; "
+                  "give the rank in the ghost-cell form (ffm_ldu_create_ext + ffm_ldu_set_ghost_exchange)");
+    return FFM_ERR_UNSUPPORTED;
+}
+
 extern "C" int ffm_gamg_create(ffm_ctx *ctx, ffm_ldu *finest, int nCells, int nFaces, const int *lowerAddr, const int *upperAddr,
                                const double *faceWeights, int nCellsInCoarsestLevel, int mergeLevels, ffm_gamg **out)
 {
@@ -291,6 +301,7 @@ extern "C" int ffm_gamg_create(ffm_ctx *ctx, ffm_ldu *finest, int nCells, int nF
     }
     if (mergeLevels != 1) { ffm_set_error("GAMG: mergeLevels %d not offered (the reference's dictionaries use 1)", mergeLevels); return FFM_ERR_UNSUPPORTED; }
     if (finest->nCells != nCells) { ffm_set_error("GAMG: the matrix has %d cells (owned + ghost), the addressing %d", finest->nCells, nCells); return FFM_ERR_ARG; }
+    FFM_TRY(refuse_interfaces(finest));
     const bool decomposed = finest->nCells > finest->nOwned;
     if (decomposed && finest->ghNbrRank.empty()) { ffm_set_error("GAMG: ghost cells without a ghost exchange (ffm_ldu_set_ghost_exchange first)"); return FFM_ERR_ARG; }
     FFM_HIP(hipSetDevice(ctx->device));
@@ -516,6 +527,7 @@ static int agglomerate_levels(ffm_gamg *G)
 extern "C" int ffm_gamg_set_matrix_d(ffm_gamg *G, const double *diag_d, const double *upper_d, const double *lower_d)
 {
     if (!G || !diag_d || !upper_d) return FFM_ERR_ARG;
+    FFM_TRY(refuse_interfaces(G->lev[0].A));
     FFM_HIP(hipSetDevice(G->ctx->device));
     G->symmetric = lower_d == nullptr;
     Level &L0 = G->lev[0];
@@ -532,6 +544,7 @@ extern "C" int ffm_gamg_set_matrix_native_d(ffm_gamg *G, const double *diag_d, c
 {
     if (!G || !diag_d || !upperNative_d) return FFM_ERR_ARG;
     Level &L0 = G->lev[0];
+    FFM_TRY(refuse_interfaces(L0.A));
     if (!L0.A->identity) { ffm_set_error("GAMG: native coefficient layout needs the library's cell order (ffm_renumber_levels)"); return FFM_ERR_UNSUPPORTED; }
     FFM_HIP(hipSetDevice(G->ctx->device));
     hipStream_t s = G->ctx->stream;
@@ -640,6 +653,7 @@ extern "C" int ffm_gamg_solve_d(ffm_gamg *G, int smoother, double tol, double re
 {
     if (!G || !psi_d || !source_d || !out) { ffm_set_error("ffm_gamg_solve_d: null argument"); return FFM_ERR_ARG; }
     if (!G->haveMatrix) { ffm_set_error("ffm_gamg_solve_d: no coefficients (ffm_gamg_set_matrix_d)"); return FFM_ERR_ARG; }
+    FFM_TRY(refuse_interfaces(G->lev[0].A));
     if (!(smoother == FFM_GS || smoother == FFM_SYMGS || smoother == FFM_DIC || smoother == FFM_DILU)) { ffm_set_error("GAMG: smoother %d not offered", smoother); return FFM_ERR_UNSUPPORTED; }
     if (smoother == FFM_DIC && !G->symmetric) { ffm_set_error("GAMG: the DIC smoother needs a symmetric matrix"); return FFM_ERR_UNSUPPORTED; }
     ffm_ctx *c = G->ctx; hipStream_t s = c->stream;

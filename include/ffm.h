@@ -212,7 +212,18 @@ long ffm_ldu_tile_gathers(const ffm_ldu *ldu);
  * of the matching patch on rank neighbRank[p]; as in OpenFOAM there is one
  * patch per neighbour rank (or both sides list their common patches in the
  * same order).  Amul: y[faceCells] -= bouCoeffs*psi_neighbour.  DIC/DILU ignore
- * the interfaces (block-Jacobi).  Needs ffm_comm_init / ffm_comm_init_host.   */
+ * the interfaces (block-Jacobi).  Needs ffm_comm_init / ffm_comm_init_host.
+ * A call replaces the interfaces of an earlier one; nPatches == 0 removes them.  A refused call (FFM_ERR_ARG: a negative
+ * size, a neighbour rank outside the context's ranks, a faceCell outside the matrix, a null array) leaves the matrix with
+ * no interfaces at all.
+ * Entry points that take such a matrix: ffm_spmv, ffm_tmul (interfaceIntCoeffs), ffm_residual, ffm_sumA, ffm_gs_smooth,
+ * ffm_precond_* (block-Jacobi), ffm_solve / ffm_solve_d with every solver they offer (FFM_GAMG is not one, see above), and
+ * ffm_solve_multi_d, which solves several such systems one after the other (one system is the matrix's own lane as ever).
+ * Entry points that refuse it with FFM_ERR_UNSUPPORTED: ffm_gamg_create -- and ffm_gamg_set_matrix_d / _native_d and
+ * ffm_gamg_solve_d where the interfaces were set after the hierarchy was made -- (the coarse levels couple the ranks
+ * through ghost cells: give the rank as ffm_ldu_create_ext + ffm_ldu_set_ghost_exchange), ffm_flow_order_create,
+ * ffm_flow_order_create_staged, ffm_solve_ordered_d, ffm_solve_ordered_staged_d and ffm_solve_triangular_rows_d.  The FV
+ * operators, the fused assembly and the plume driver work on the ghost-cell form only.                                      */
 int ffm_ldu_set_interfaces(ffm_ldu *ldu, int nPatches, const int *patchSizes,
                            const int *const *faceCells,
                            const double *const *bouCoeffs,

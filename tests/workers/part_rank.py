@@ -1,6 +1,7 @@
 """One rank of a decomposed solve on a mesh partitioned by the product's partitioner (firefoam-dev_amd/decompose.py ->
 csrc/ffm_partition.cpp), over gloo.  mode "oracle": the rank-local C solver of the oracle with OpenFOAM-style processor patches
-(CPU only).  mode "gpu": the HIP library on cuda:0 (all ranks share it) in the ghost-cell form, host transport.
+(CPU only).  mode "gpu": the HIP library on cuda:0 (all ranks share it) in the ghost-cell form, host transport.  mode "gpu_if": the HIP
+library in the oracle's own form, the LDU of the owned cells + ffm_ldu_set_interfaces (tests/test_ldu_interfaces_gpu.py).
 usage: part_rank.py mode rank world port mesh partitioner solver precond asym outdir"""
 import os
 import sys
@@ -73,6 +74,33 @@ if mode == "oracle":
         perf = dict(nIterations=2, initialResidual=0.0)
     else:
         psi, perf = A.solve(getattr(O, solver), getattr(O, precond), np.zeros(sub.nOwned), source[sub.gcell[:sub.nOwned]], tolerance=1e-12)
+elif mode == "gpu_if":
+    # the matrix of mode "oracle" on the device: the LDU of the owned cells + ffm_ldu_set_interfaces (interfaceIntCoeffs = interfaceBouCoeffs, as there)
+    nO = sub.nOwned
+    ctx = ffm.Context(0)
+    ctx.comm_init_host(rank, world, gloo.allreduce, gloo.exchange, gloo.exchange_var)
+    keep, pat = sub.interface_form(up, lo)
+    d, upl, lol = sub.coeffs(diag, up, lo)
+    A = ffm.lduMatrix(ctx, nO, sub.l[keep], sub.u[keep])
+    A.set_interfaces([p[0] for p in pat], [p[1] for p in pat], neighbRank=sub.nbrRank, globalCells=N)
+    A.set_coeffs(d[:nO], upl[keep], None if lol is None else lol[keep])
+    if solver == "GS2":
+        out = A.smooth(ctx.to_device(O.hash_u(0xF5, np.arange(N))[sub.gcell[:nO]]), ctx.to_device(source[sub.gcell[:nO]]), nSweeps=2,
+                       smoother="symGaussSeidel" if precond == "SYMGS" else "GaussSeidel")
+        np.savez(os.path.join(outdir, "rank%d.npz" % rank), psi=out.cpu().numpy(), gcell=sub.gcell[:nO], nIter=2, initialResidual=0.0,
+                 nGhost=sub.nGhost, nNbr=len(sub.nbrRank), sweepMode=A.sweep_mode, nPatches=len(pat))
+        A.close(); ctx.close()
+        sys.exit(0)
+    names = {"PCG": "PCG", "PBICGSTAB": "PBiCGStab", "PBICG": "PBiCG", "SMOOTH": "smoothSolver"}
+    pre = {"DIC": "DIC", "DILU": "DILU", "SYMGS": "symGaussSeidel"}
+    kw = dict(solver=names[solver], preconditioner=pre[precond], tolerance=1e-12, maxIter=1000)
+    psi_d = ctx.zeros(nO)
+    perf = A.solve(psi_d, ctx.to_device(source[sub.gcell[:nO]]), **kw)
+    psi = psi_d.cpu().numpy()
+    np.savez(os.path.join(outdir, "rank%d.npz" % rank), psi=psi, gcell=sub.gcell[:nO], nIter=perf["nIterations"], initialResidual=perf["initialResidual"],
+             finalResidual=perf["finalResidual"], converged=perf["converged"], nGhost=sub.nGhost, nNbr=len(sub.nbrRank), nPatches=len(pat))
+    A.close(); ctx.close()
+    sys.exit(0)
 else:
     ctx = ffm.Context(0)
     ctx.comm_init_host(rank, world, gloo.allreduce, gloo.exchange, gloo.exchange_var)
@@ -111,4 +139,5 @@ else:
     np.save(os.path.join(outdir, "amul%d.npy" % rank), y)
     A.close(); ctx.close()
 np.savez(os.path.join(outdir, "rank%d.npz" % rank), psi=psi, gcell=sub.gcell[:sub.nOwned], nIter=perf["nIterations"],
-         initialResidual=perf["initialResidual"], nGhost=sub.nGhost, nNbr=len(sub.nbrRank))
+         initialResidual=perf["initialResidual"], nGhost=sub.nGhost, nNbr=len(sub.nbrRank),
+         **({"finalResidual": perf["finalResidual"]} if "finalResidual" in perf else {}))       # (a solve's; the smoother call has none)
