@@ -115,6 +115,11 @@ def test_limited_weights(setup, O, ctx, scheme, code):
     got = back_face(s, w)
     assert np.abs(got - ref).max() < 1e-13
     assert got.min() >= 0.0 and got.max() <= 1.0
+    # bitwise against the restatement whose dot product is written in the kernel's order, (d0 g0 + d1 g1) + d2 g2 (the oracle's
+    # np.einsum fixes no order, hence its 1e-13 above); upwind and linear weights involve no arithmetic
+    import fv_edge_inputs as E
+    exact = E.restate(m, scheme, phi, vf, grad, 1.0, (0.0, 1.0))[1] if scheme in E.SCHEME_NAME.values() else ref
+    assert np.array_equal(got.view(np.uint64), exact.view(np.uint64))
 
 
 def test_limiter_unit_vectors(O):
