@@ -635,6 +635,49 @@ extern "C" int b1_fvdom_ordered(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, int e
                         qinOut, qemOut, qrOut, iters, nSolves, maxSolveIterations);
 }
 
+// ---- the P1 handle (include/fireFoamHandles.H) on any mesh: nCalls calls of radiation->correct() (solverFreq 1) with a given temperature
+// field (cells + boundary faces), constant a, e, scatter constants sigma_s, C, wall emissivities and -- where E is given -- the emission as
+// a cell field through the handle's emission provider (NULL: E = 0); G by PCG + DIC to GTol, relTol 0, from G = 0.  Out: G [N], G_b, qr [B],
+// iters[nCalls] = PCG iterations of every call.  sysClass / sysFused (both or neither; [nNative + 2 N]: upper, diag, source): the system
+// as the class layer's operators leave it for the solver, and as ffm_p1_assemble_d does from the same fields.  Returns the number of
+// solves logged.  tests/test_p1_foam_gpu.py compares with tests/p1_ref.py.
+extern "C" int b1_p1(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, double a, double e, double sigmaS, double Cscatter, const double* T, const double* Tb,
+                     const double* E, const double* emissivity, double GTol, int nCalls, double* GOut, double* GbOut, double* qrOut, int* iters,
+                     double* sysClass, double* sysFused)
+{
+    const double sigma = 5.670367e-8;
+    fvMesh mesh(ctx, ldu, msh, 1.0);
+    mesh.solvers["G"] = mesh.solvers["GFinal"] = {FFM_PCG, FFM_DIC, GTol, 0, 0, 1000, 1};
+    const label N = mesh.nCells, B = mesh.nBoundary, nNat = mesh.nInternalNative;
+    volScalarField Tf("T", mesh); Tf.v.assignHost(T); Tf.b.assignHost(Tb);
+    volScalarField Ef("E", mesh); if (E) Ef.v.assignHost(E);
+    P1 p1(mesh, Tf, 1, a, e, 0.0, sigmaS, Cscatter, sigma);
+    if (E) p1.emission = [&Ef]() { return Ef; };
+    p1.emissivity().assignHost(emissivity);
+    int nSolves = 0;
+    for (int c = 0; c < nCalls; c++) {
+        mesh.log.clear();
+        p1.correct();
+        iters[c] = mesh.log.empty() ? -1 : mesh.log.back().nIterations;
+        nSolves += (int)mesh.log.size();
+    }
+    p1.G_.v.toHost(GOut); p1.G_.b.toHost(GbOut); p1.qr_.toHost(qrOut);
+    if (sysClass && sysFused) {
+        fvScalarMatrix M(p1.GEqn());
+        M.ensure();
+        dField d(ctx, N), s(ctx, N);
+        FFM_FOAM_CHK(ffm_fvm_add_boundary(msh, M.internalCoeffs[0].data(), M.boundaryCoeffs[0].data(), M.diag.data(), M.source[0].data(), nullptr,
+                                          d.dataOverwrite(), s.dataOverwrite()));
+        M.upper.toHost(sysClass); d.toHost(sysClass + nNat); s.toHost(sysClass + nNat + N);
+        dField u2(ctx, nNat, 0.0), d2(ctx, N), s2(ctx, N), gb(ctx, B), fb(ctx, B), rb(ctx, B);
+        FFM_FOAM_CHK(ffm_p1_assemble_d(msh, sigmaS*(3.0 - Cscatter), sigma, nullptr, a, nullptr, nullptr, e, E ? Ef.v.data() : nullptr, Tf.v.data(), Tf.b.data(),
+                                       p1.emissivity().data(), u2.data(), d2.dataOverwrite(), s2.dataOverwrite(), gb.dataOverwrite(), fb.dataOverwrite(), rb.dataOverwrite()));
+        u2.toHost(sysFused); d2.toHost(sysFused + nNat); s2.toHost(sysFused + nNat + N);
+    }
+    FFM_FOAM_CHK(ffm_ctx_sync(ctx));
+    return nSolves;
+}
+
 // ---- Time::setDeltaT / operator++ of include/ffmFoam.H (Time::adjustDeltaT with writeControl adjustableRunTime) stepped n times with the
 // wished deltaT of every step: the adjusted deltaT, the time and the write index after every step (tests/test_abi_cpu.py)
 extern "C" int b1_time_sequence(double deltaT0, double writeInterval, int n, const double* wish, double* dtOut, double* tOut, int* writeIndexOut)

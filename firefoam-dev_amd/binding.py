@@ -244,6 +244,10 @@ def lib():
         "ffm_fvdom_sum_rays_d": ([vp, C.c_int, dp, dp], C.c_int),
         "ffm_radiation_sh_d": ([vp, C.c_long] + [C.c_double] * 3 + [dp] * 5 + [C.c_double, dp, dp], C.c_int),
         "ffm_fvdom_G_d": ([vp, C.c_long, C.c_int, dp, dp, dp], C.c_int),
+        "ffm_p1_gamma_d": ([vp, C.c_long, dp, C.c_double, C.c_double, dp], C.c_int),
+        "ffm_p1_marshak_coeffs_d": ([vp, C.c_double] + [dp] * 5, C.c_int),
+        "ffm_p1_assemble_d": ([vp, C.c_double, C.c_double, dp, C.c_double, dp, dp, C.c_double] + [dp] * 10, C.c_int),
+        "ffm_p1_wall_flux_d": ([vp] + [dp] * 6, C.c_int),
         "ffm_mesh_nboundary": ([vp], C.c_int),
         "ffm_mesh_nnative": ([vp], C.c_int),
         "ffm_faces_to_native": ([vp, hp, dp], C.c_int),
@@ -282,6 +286,7 @@ def lib():
         "ffm_plume_set_radiation_model": ([vp, C.c_double, C.c_double, C.c_double], C.c_int),
         "ffm_plume_set_radiation_ordering": ([vp, C.c_int], C.c_int),
         "ffm_plume_set_radiation_thermo": ([vp, C.c_int], C.c_int),
+        "ffm_plume_set_radiation_p1": ([vp, C.c_int] + [C.c_double] * 4, C.c_int),
         "ffm_plume_ray_system": ([vp, C.c_int, C.c_int, hp, hp, hp, hp], C.c_int),
         "ffm_ray_schedule": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, hp, ip, C.c_int], C.c_int),
         "ffm_ray_octant": ([hp], C.c_int),
@@ -960,6 +965,14 @@ class Plume:
         by the thermo package's Cp field (ffm_plume_set_radiation_thermo).  Off is refused while both are on"""
         _check(lib().ffm_plume_set_radiation_thermo(self.h, 1 if on else 0), "ffm_plume_set_radiation_thermo")
 
+    def set_radiation_p1(self, solverFreq=1, absorption=0.1, Ehrr1=0.0, Ehrr2=0.0, wallEmissivity=1.0):
+        """the P1 model in place of the rays (ffm_plume_set_radiation_p1): every solverFreq-th step one PCG + DIC solve for G with
+        MarshakRadiation walls of the one emissivity, E = RadFraction*Qdot and radiation->Sh as set_radiation_model has them;
+        solverFreq 0: off.  Refused (FfmError) while set_radiation is on and on a block of a decomposed box.  Fields G, qr (per
+        boundary face), ShSu, ShSp become readable"""
+        _check(lib().ffm_plume_set_radiation_p1(self.h, int(solverFreq), float(absorption), float(Ehrr1), float(Ehrr2), float(wallEmissivity)),
+               "ffm_plume_set_radiation_p1")
+
     def ray_system(self, ray, fused):
         """(diag, upper, lower, source) of one ray's system by the operator chain or by the one-pass kernel (ffm_plume_ray_system; tests)"""
         d, s_ = np.empty(self.nCells), np.empty(self.nCells)
@@ -991,7 +1004,8 @@ class Plume:
         _check(lib().ffm_plume_step(self.h), "ffm_plume_step")
 
     def field(self, name):
-        out = np.empty(self.nCells)
+        # (qr: P1's wall flux, one value per boundary face in patch-face order; everything else one value per cell, natural order)
+        out = np.empty(lib().ffm_mesh_nboundary(C.c_void_p(lib().ffm_plume_mesh(self.h))) if name == "qr" else self.nCells)
         _check(lib().ffm_plume_get_field(self.h, name.encode(), _hp(out)), "ffm_plume_get_field")
         return out
 

@@ -327,6 +327,7 @@ extern "C" int ffm_plume_set_initial_state(ffm_plume *P, const double *const *Y,
         FFM_TRY(ffm_dzero(P->ctx, P->K, sizeof(double) * N)); FFM_TRY(ffm_dzero(P->ctx, P->dpdt, sizeof(double) * N));
         FFM_TRY(ffm_dzero(P->ctx, P->phi, sizeof(double) * std::max<long>(P->nNat, 1))); FFM_TRY(ffm_dzero(P->ctx, P->phib, sizeof(double) * std::max(B, 1)));
         P->stepNo = 0; P->time = 0.0; P->radHaveG = false; P->mvOverride = false; P->ddtCorrValid = false;
+        if (P->p1G) { FFM_TRY(ffm_dzero(P->ctx, P->p1G, sizeof(double) * N)); P->p1HaveQr = false; }      // P1 starts again from G = 0
     }
     std::vector<double> v(N);
     auto up = [&](double *dst, const double *nat) -> int {
@@ -513,13 +514,18 @@ extern "C" int ffm_plume_get_field(ffm_plume *P, const char *name, double *out)
     if (!P || !name || !out) return FFM_ERR_ARG;
     const std::string n(name);
     const double *src = nullptr;
+    if (n == "qr") {        // P1's wall flux: [nBoundary] in patch-face order, an error before the first correct()
+        if (!(P->p1Freq > 0 && P->p1HaveQr)) { ffm_set_error("unknown field %s", name); return FFM_ERR_ARG; }
+        PL_HIP(hipStreamSynchronize(P->ctx->stream));
+        return ffm_d2h(P->ctx, out, P->p1Qr, sizeof(double) * P->B);
+    }
     if (n == "rho") src = P->rho; else if (n == "p") src = P->p; else if (n == "p_rgh") src = P->p_rgh; else if (n == "T") src = P->T;
     else if (n == "h") src = P->hs; else if (n == "K") src = P->K; else if (n == "Ux") src = P->U[0]; else if (n == "Uy") src = P->U[1];
     else if (n == "Uz") src = P->U[2]; else if (n == "psi") src = P->psi; else if (n == "ph_rgh") src = P->ph_rgh;
     else if (n == "mu") src = P->mu; else if (n == "alpha") src = P->alpha; else if (n == "Cp") src = P->Cp;      // (null while the stand-in thermo is on)
     else if (n == "wFuel") src = P->wFuelOwn; else if (n == "Qdot") src = P->QdotOwn;      // (null while both are scratch slots: no model of theirs on)
     else if (n == "k") src = P->kSgs; else if (n == "nut") src = P->nut; else if (n == "alphat") src = P->alphat;      // (null while the model is off)
-    else if (n == "G") src = P->G; else if (n == "ShSu") src = P->radHaveSh ? P->radShSu : nullptr; else if (n == "ShSp") src = P->radHaveSh ? P->radShSp : nullptr; else if (n == "radE") src = P->radE;      // (ShSu, ShSp: null before the first radiation->Sh pass)
+    else if (n == "G") src = P->radG(); else if (n == "ShSu") src = P->radHaveSh ? P->radShSu : nullptr; else if (n == "ShSp") src = P->radHaveSh ? P->radShSp : nullptr; else if (n == "radE") src = P->radE;      // (ShSu, ShSp: null before the first radiation->Sh pass)
     else if (n.size() > 1 && n[0] == 'I' && isdigit((unsigned char)n[1])) { const int i = atoi(n.c_str() + 1); if (i < (int)P->I.size()) src = P->I[i]; }
     else for (int i = 0; i < NSP; i++) if (n == SPN[i]) src = P->Y[i];
     if (!src) { ffm_set_error("unknown field %s", name); return FFM_ERR_ARG; }

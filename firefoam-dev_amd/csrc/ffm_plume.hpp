@@ -1,5 +1,5 @@
 // ffm_plume.hpp -- the handle of the synthetic buoyant-plume case and what its translation units share: ffm_plume.hip (create / destroy,
-// setters, getters, hydrostatic initialisation), ffm_plume_step.hip (the time step), ffm_plume_rad.hip (the fvDOM stand-in).  The physics
+// setters, getters, hydrostatic initialisation), ffm_plume_step.hip (the time step), ffm_plume_rad.hip (the fvDOM stand-in and P1).  The physics
 // plug-ins that the reference takes from other libraries are replaced by the stand-ins listed in oracle/plume.py (perfect gas / constant
 // Cp, constant mu, Pr, EDC-shaped single-step source, zero-gradient thermo boundary values); their constants are below.
 // Opt-in, the reference's own models take their place: LES kEqn (ffm_plume_set_turbulence), janaf / sutherland thermo (ffm_plume_set_thermo), EDC
@@ -117,7 +117,14 @@ struct ffm_plume {
     double **radIdd = nullptr, *radOmegaD = nullptr; int radTabRays = 0;
     // ffm_plume_set_radiation_thermo: the rays and radiation->Sh accepted together with the thermo package (Sh then reads the Cp field)
     bool radThermo = false;
-    bool stecklerSolvers = false;          // transport equations with smoothSolver + symGaussSeidel, maxIter 10
+    // P1 in place of the rays (ffm_plume_set_radiation_p1; off: p1Freq 0, every pointer null): its G (the rays keep theirs), the patch
+    // arrays gamma_b, valueFraction, refValue, G_b, qr, T_b [B], and -- the per-operator form only -- gamma on cells and faces, su
+    int p1Freq = 0; double p1Emis = 1.0;
+    double *p1G = nullptr, *p1GammaB = nullptr, *p1F = nullptr, *p1Ref = nullptr, *p1Gb = nullptr, *p1Qr = nullptr, *p1Tb = nullptr, *p1EmisB = nullptr;
+    double *p1GammaC = nullptr, *p1GammaF = nullptr, *p1Su = nullptr, *p1Sn = nullptr;
+    bool p1HaveQr = false;
+    const double *radG() const { return p1Freq > 0 ? p1G : G; }      // the G radiation->Sh reads
+    bool stecklerSolvers = false;         // transport equations with smoothSolver + symGaussSeidel, maxIter 10
                                            // (cases/steckler/system/fvSolution:49-62) instead of PBiCGStab + DILU
     // LES kEqn sub-grid model (ffm_plume_set_turbulence; cases/steckler/constant/turbulenceProperties:18-30): 0 = none, every pointer null
     int turbModel = 0;

@@ -1,4 +1,4 @@
-// ffm_plume_rad.hip -- the fvDOM stand-in of the plume case: the rays' set-up, radiation->correct() and the radiation setters.
+// ffm_plume_rad.hip -- the radiation models of the plume case: the fvDOM stand-in (the rays' set-up), P1, radiation->correct() and the radiation setters.
 #include "ffm_plume.hpp"
 
 // ---- fvDOM stand-in: radiation->correct() of solver/YEEqn.H:80 -------------------------------------------------------
@@ -121,8 +121,80 @@ static int radiation_correct_staged(ffm_plume *P, const double *Ee)
     return rad_update_G(P);
 }
 
+// ---- P1 in place of the rays (ffm_plume_set_radiation_p1): P1::calculate() of P1.C:213-258 -------------------------------------
+// gamma = 1/(3 a + a0) (no scattering), fvm::laplacian(gamma, G) - fvm::Sp(a, G) == -4 a sigma T^4 - E with E = RadFraction*Qdot,
+// MarshakRadiation with the one wall emissivity on every patch at the zero-gradient patch values of T, PCG + DIC at the `G` entry's
+// controls (cases/steckler/system/fvSolution:75-81) from the previous G, then qr.  The fused step: ffm_p1_assemble_d and
+// ffm_p1_wall_flux_d; the per-operator step: the chain of entry points they restate, the same bytes.
+static int p1_correct(ffm_plume *P)
+{
+    ffm_mesh *m = P->mesh; const int N = P->N;
+    double frac = 0.0;
+    FFM_TRY(plume_rad_fraction(P, &frac));
+    double *E = P->radE; const double *Qd = P->Qdot;
+    forN(P, N, [=] __device__(long c) { E[c] = frac * Qd[c]; });
+    zg(P, P->p1Tb, P->T);
+    const double a = P->radA;
+    if (P->fused) {
+        FFM_TRY(ffm_p1_assemble_d(m, 0.0, SIGMA_SB, nullptr, a, nullptr, nullptr, a, E, P->T, P->p1Tb, P->p1EmisB, P->upper, P->dWork, P->sWork,
+                                  P->p1GammaB, P->p1F, P->p1Ref));
+    } else {
+        FFM_TRY(ffm_p1_gamma_d(P->ctx, N, nullptr, a, 0.0, P->p1GammaC));
+        FFM_TRY(ffm_p1_gamma_d(P->ctx, P->B, nullptr, a, 0.0, P->p1GammaB));
+        FFM_TRY(ffm_fvc_interpolate(m, nullptr, P->p1GammaC, P->p1GammaF));
+        FFM_TRY(ffm_fvm_transport(m, 0.0, nullptr, nullptr, nullptr, P->p1GammaF, +1, P->diag, P->upper, nullptr));
+        FFM_TRY(ffm_p1_marshak_coeffs_d(m, SIGMA_SB, P->p1GammaB, P->p1Tb, P->p1EmisB, P->p1F, P->p1Ref));
+        FFM_TRY(ffm_fvm_boundary_coeffs(m, nullptr, P->p1GammaB, +1, P->p1F, P->p1Ref, P->zeroB, P->ic[0], P->bc[0]));
+        const double *V = ffm_mesh_geom(m, 0), *T = P->T; double *dg = P->diag, *su = P->p1Su;
+        forN(P, N, [=] __device__(long c) {
+            dg[c] = dg[c] - V[c] * a;
+            const double t = T[c];
+            su[c] = 0.0 + V[c] * ((-(4.0 * ((a * SIGMA_SB) * ((t * t) * (t * t))))) - E[c]);
+        });
+        FFM_TRY(ffm_fvm_add_boundary(m, P->ic[0], P->bc[0], P->diag, su, nullptr, P->dWork, P->sWork));
+    }
+    FFM_TRY(solve_named(P, "G", FFM_PCG, FFM_DIC, 1e-6, 0.0, P->dWork, P->upper, nullptr, P->p1G, P->sWork));
+    if (P->fused) FFM_TRY(ffm_p1_wall_flux_d(m, P->p1GammaB, P->p1F, P->p1Ref, P->p1G, P->p1Gb, P->p1Qr));
+    else {
+        FFM_TRY(ffm_bc_values(m, P->p1F, P->p1Ref, P->zeroB, P->p1G, P->p1Gb));
+        FFM_TRY(ffm_fvc_snGrad_b(m, P->p1G, P->p1Gb, P->p1Sn));
+        const double *gb = P->p1GammaB, *sn = P->p1Sn; double *qr = P->p1Qr;
+        forN(P, P->B, [=] __device__(long k) { qr[k] = -gb[k] * sn[k]; });
+    }
+    P->radHaveG = true; P->p1HaveQr = true;
+    return FFM_OK;
+}
+
+extern "C" int ffm_plume_set_radiation_p1(ffm_plume *P, int solverFreq, double absorption, double Ehrr1, double Ehrr2, double wallEmissivity)
+{
+    if (!P || solverFreq < 0 || !(absorption >= 0) || !(Ehrr1 >= 0) || !(Ehrr2 >= 0) || !(wallEmissivity >= 0 && wallEmissivity <= 1)) return FFM_ERR_ARG;
+    if (solverFreq == 0) {          // off: the step of a handle that never saw P1
+        if (P->p1Freq > 0) { P->p1Freq = 0; P->radCoupled = false; P->radHaveG = false; P->radHaveSh = false; P->p1HaveQr = false; }
+        return FFM_OK;
+    }
+    if (!P->oneBlock) { ffm_set_error("ffm_plume_set_radiation_p1: a block of a decomposed box (P1 runs on a single block only)"); return FFM_ERR_UNSUPPORTED; }
+    if (P->radFreq > 0) { ffm_set_error("ffm_plume_set_radiation_p1: the fvDOM rays are on (ffm_plume_set_radiation); one radiation model at a time"); return FFM_ERR_UNSUPPORTED; }
+    if (P->thermo && !P->radThermo) { ffm_set_error("ffm_plume_set_radiation_p1: not with ffm_plume_set_thermo on (ffm_plume_set_radiation_thermo is off)"); return FFM_ERR_UNSUPPORTED; }
+    PL_HIP(hipSetDevice(P->ctx->device));
+    if (!P->p1G) {
+        const size_t nPool = P->pool.size(); const int N = P->N, B = P->B;
+        P->p1G = dalloc(P, N); P->p1GammaB = dalloc(P, B); P->p1F = dalloc(P, B); P->p1Ref = dalloc(P, B); P->p1Gb = dalloc(P, B); P->p1Qr = dalloc(P, B);
+        P->p1Tb = dalloc(P, B); P->p1EmisB = dalloc(P, B);
+        if (!P->fused) { P->p1GammaC = dalloc(P, N); P->p1GammaF = dalloc(P, P->nNat); P->p1Su = dalloc(P, N); P->p1Sn = dalloc(P, B); }
+        if (P->pool.size() != nPool + (P->fused ? 8 : 12)) { ffm_set_error("plume: out of device memory"); return FFM_ERR_HIP; }
+    }
+    if (!P->radE) { P->radE = dalloc(P, P->N); P->radShSu = dalloc(P, P->N); P->radShSp = dalloc(P, P->N); }
+    if (!P->radE || !P->radShSu || !P->radShSp) return FFM_ERR_HIP;
+    double *eb = P->p1EmisB; const double eps = wallEmissivity;
+    forN(P, P->B, [=] __device__(long k) { eb[k] = eps; });
+    P->radA = absorption; P->Ehrr1 = Ehrr1; P->Ehrr2 = Ehrr2; P->radCoupled = true; P->p1Emis = wallEmissivity;
+    P->p1Freq = solverFreq;
+    return FFM_OK;
+}
+
 int radiation_correct(ffm_plume *P)
 {
+    if (P->p1Freq > 0) return p1_correct(P);
     const int N = P->N, B = P->B; const long nNat = P->nNat;
     const double Ib = SIGMA_SB * ((TREF * TREF) * (TREF * TREF)) / M_PI;
     // the fused step on one block: every ray assembled in one pass, G formed once after the last ray.  The per-operator step, and
@@ -310,6 +382,7 @@ extern "C" int ffm_plume_set_radiation(ffm_plume *P, int solverFreq, int nPhi, i
 {
     if (!P || solverFreq < 0 || nPhi < 1 || nTheta < 1 || ((dAve == nullptr) != (omega == nullptr))) return FFM_ERR_ARG;
     if (P->thermo && !P->radThermo) { ffm_set_error("ffm_plume_set_radiation: not with ffm_plume_set_thermo on (ffm_plume_set_radiation_thermo is off)"); return FFM_ERR_UNSUPPORTED; }
+    if (P->p1Freq > 0) { ffm_set_error("ffm_plume_set_radiation: the P1 model is on (ffm_plume_set_radiation_p1); one radiation model at a time"); return FFM_ERR_UNSUPPORTED; }
     PL_HIP(hipSetDevice(P->ctx->device));
     const int nRay = 4 * nPhi * nTheta;
     P->rayD.assign(3 * (size_t)nRay, 0.0); P->rayOmega.assign(nRay, 0.0);
@@ -386,6 +459,7 @@ extern "C" int ffm_plume_set_radiation_model(ffm_plume *P, double absorption, do
 {
     if (!P || absorption < 0 || Ehrr1 < 0 || Ehrr2 < 0) return FFM_ERR_ARG;
     if (P->thermo && !P->radThermo) { ffm_set_error("ffm_plume_set_radiation_model: not with ffm_plume_set_thermo on (ffm_plume_set_radiation_thermo is off)"); return FFM_ERR_UNSUPPORTED; }
+    if (P->p1Freq > 0) { ffm_set_error("ffm_plume_set_radiation_model: the P1 model is on and has its own constants (ffm_plume_set_radiation_p1)"); return FFM_ERR_UNSUPPORTED; }
     PL_HIP(hipSetDevice(P->ctx->device));
     if (!P->radE) { P->radE = dalloc(P, P->N); P->radShSu = dalloc(P, P->N); P->radShSp = dalloc(P, P->N); }
     if (!P->radE || !P->radShSu || !P->radShSp) return FFM_ERR_HIP;

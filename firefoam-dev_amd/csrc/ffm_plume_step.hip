@@ -504,7 +504,7 @@ static int e_radiation_source(ffm_plume *P, const double **shSu, const double **
     FFM_TRY(plume_rad_fraction(P, &frac));
     const double Rp = 4.0 * P->radA * SIGMA_SB, KA = P->radA;
     // Cpv: the thermo package's cell field (thermo.correct() of the step before wrote it at the T read here), else the stand-in's constant
-    double *su2 = P->radShSu, *sp2 = P->radShSp; const double *G = P->G, *T = P->T, *hh = P->hs, *Qd = P->Qdot, *Cpf = P->thermo ? P->Cp : nullptr;
+    double *su2 = P->radShSu, *sp2 = P->radShSp; const double *G = P->radG(), *T = P->T, *hh = P->hs, *Qd = P->Qdot, *Cpf = P->thermo ? P->Cp : nullptr;
     if (P->fused) FFM_TRY(ffm_radiation_sh_d(P->ctx, P->N, KA, SIGMA_SB, frac, G, T, hh, Qd, Cpf, CP, su2, sp2));
     else forN(P, P->N, [=] __device__(long c) {
         const double t = T[c], T3 = t * t * t, cp = Cpf ? Cpf[c] : CP;
@@ -837,7 +837,7 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     if (P->turbModel) FFM_TRY(les_alpha_eff(P));
     FFM_TRY(mv_weights(P));
     bool spOffDiagBound;
-    const bool radNow = P->radFreq > 0 && P->stepNo % P->radFreq == 0;
+    const bool radNow = (P->radFreq > 0 && P->stepNo % P->radFreq == 0) || (P->p1Freq > 0 && P->stepNo % P->p1Freq == 0);
     const bool jointYh = P->fused && P->mvSelection && !P->stecklerSolvers && P->oneBlock && !radNow && !P->separateH;
     FFM_TRY(species_eqns(P, &spOffDiagBound, jointYh));
     if (radNow) { FFM_TRY(radiation_correct(P)); spOffDiagBound = false; }     // radiation->correct(), solver/YEEqn.H:80: its ray solves bind other coefficients

@@ -591,6 +591,41 @@ int ffm_fvdom_G_d(ffm_ctx *ctx, long n, int nRay, const double *const *I_dd, con
  * 0 -- the inflow from the neighbour ranks becomes a known term and the rows couple owned cells only.                         */
 int ffm_fvdom_fold_ghost_inflow_d(ffm_mesh *mesh, int nCells, const int *cells_d, const double *I, double *upper, double *lower,
                                   double *source);
+/* ------------------------------------------------------- P1 radiation model */
+/* P1::calculate() (reference packages/thermophysicalModels/radiation/radiationModels/P1/P1.C:213-258; selected by
+ * cases/pyrolysis1D/constant/radiationProperties:21, solved with the `G` entry of cases/steckler/system/fvSolution:75-81):
+ *   gamma = 1.0/(3.0*a + 3.0*sigmaEff + a0);  solve(fvm::laplacian(gamma, G) - fvm::Sp(a, G) == -4.0*(e*sigma*pow4(T)) - E)
+ * with sigmaEff = sigma_s*(3 - C) of constantScatter.C:87 and a0 = ROOTVSMALL = 1e-150 (upstream OpenFOAM's, restated from knowledge),
+ * every patch MarshakRadiation (cases/pyrolysis1D/0/G; MarshakRadiationFvPatchScalarField.C:156-190), and qr_b = -gamma_b*snGrad(G)_b.
+ * Operation order everywhere: pow4(x) = (x*x)*(x*x); the denominator (3.0*a + 3.0*sigmaEff) + a0; no FMA contraction.
+ * All pointers are device pointers; `_b` arrays hold ffm_mesh_nboundary entries, face arrays are in the native layout.
+ *
+ * gamma_d[i] = 1.0/((3.0*a + 3.0*sigmaEff) + a0), a = a_d[i] or aConst where a_d is NULL: cells (P1.C:219-226) and patch values alike.
+ * FFM_ERR_ARG: NULL ctx or gamma_d, n < 0; n == 0 is a no-op. */
+int ffm_p1_gamma_d(ffm_ctx *ctx, long n, const double *a_d /* nullable */, double aConst, double sigmaEff, double *gamma_d);
+/* MarshakRadiationFvPatchScalarField::updateCoeffs on every boundary face: refValue = (4.0*sigma)*pow4(T_b), refGrad = 0 (not written),
+ * Ep = emissivity/(2.0*(2.0 - emissivity)), valueFraction = 1.0/(1.0 + (gamma_b*deltaCoeffs)/Ep).  emissivity 0 gives Ep = 0, the quotient
+ * +inf and the fraction exactly 0 (a reflecting, zero-gradient wall): IEEE arithmetic, not guarded.  emissivity_b NULL = 1 everywhere.
+ * A mesh without boundary faces: no-op.  FFM_ERR_ARG (nothing written): NULL mesh or any other array. */
+int ffm_p1_marshak_coeffs_d(ffm_mesh *mesh, double sigma, const double *gamma_b, const double *T_b, const double *emissivity_b /* nullable */,
+                            double *valueFraction_b, double *refValue_b);
+/* The whole system of P1::calculate() as the solver takes it (symmetric: upper [native faces], diag / source [cells], boundary
+ * coefficients added) in one walk over the rows, with the Marshak coefficients and gamma_b it formed on the way.  Bit for bit the chain
+ *   ffm_p1_gamma_d (cells; patches -> gamma_b) | ffm_fvc_interpolate (NULL weights) | ffm_fvm_transport (gamma_f alone, laplacianSign +1) |
+ *   ffm_p1_marshak_coeffs_d | ffm_fvm_boundary_coeffs(NULL, gamma_b, +1, f, ref, 0) | diag -= V*a |
+ *   source = 0 + V*((-(4.0*((e*sigma)*pow4(T)))) - E) (fvMatrix == volField: source += V*su) | ffm_fvm_add_boundary.
+ * a_d / e_d NULL: the constants; a_b NULL: aConst on the patches; E_d NULL: no emission term.
+ * FFM_ERR_ARG (nothing written): NULL mesh, T_d, upper, diag or source, or -- on a mesh with boundary faces -- T_b or an output _b array. */
+int ffm_p1_assemble_d(ffm_mesh *mesh, double sigmaEff, double sigma, const double *a_d /* nullable */, double aConst,
+                      const double *a_b /* nullable */, const double *e_d /* nullable */, double eConst, const double *E_d /* nullable */,
+                      const double *T_d, const double *T_b, const double *emissivity_b /* nullable */, double *upper, double *diag, double *source,
+                      double *gamma_b, double *valueFraction_b, double *refValue_b);
+/* After the solve: the mixed evaluate of G on the patches and the wall flux of P1.C:251-257,
+ *   G_b = f*ref + (1 - f)*(G[faceCell] + 0/delta);  qr_b = -gamma_b*(delta*(G_b - G[faceCell])),
+ * bit for bit ffm_bc_values (refGrad 0) + ffm_fvc_snGrad_b + one multiply.  A mesh without boundary faces: no-op.
+ * FFM_ERR_ARG (nothing written): any NULL argument. */
+int ffm_p1_wall_flux_d(ffm_mesh *mesh, const double *gamma_b, const double *valueFraction_b, const double *refValue_b, const double *G_d,
+                       double *G_b, double *qr_b);
 /* The tick schedule of the direction-ordered ray solves on a px x py x pz box of blocks, for the block (bx,by,bz); pure host
  * code, no GPU.  Rays are grouped by octant (ffm_ray_octant); a block's stage in an octant is its Manhattan distance from the
  * octant's upstream corner block; at tick t of an octant the block at stage s solves the octant's ray number t - s (rays of an
@@ -787,6 +822,17 @@ int ffm_plume_set_radiation_model(ffm_plume *plume, double absorption, double Eh
  * Not here: greyDiffusiveRadiation walls (they stay with the fvDOM handle of include/fireFoamHandles.H), a device-resident RadFraction,
  * wide-band models, rays pipelined against each other. */
 int ffm_plume_set_radiation_thermo(ffm_plume *plume, int on);
+/* Opt-in (solverFreq 0 = off, the default): the P1 model as the plume's radiation->correct() (solver/YEEqn.H:80) in place of the rays.
+ * Every solverFreq-th step assembles the system of P1::calculate() (ffm_p1_assemble_d; the chain it restates under FFM_PLUME_UNFUSED, the
+ * same bytes), solves G with PCG + DIC at the `G` entry's controls (tolerance 1e-6, relTol 0) from the previous G -- logged as "G" -- and
+ * forms qr (ffm_p1_wall_flux_d).  One constant `absorption` for a and e, no scattering, E = RadFraction*Qdot and radiation->Sh exactly as
+ * ffm_plume_set_radiation_model has them (Ehrr1, Ehrr2), every patch MarshakRadiation with the one `wallEmissivity` and the zero-gradient
+ * patch values of T.  "G", "qr" ([nBoundary], patch-face order), "ShSu", "ShSp" are readable with ffm_plume_get_field.  Towards
+ * ffm_plume_set_thermo the rules of ffm_plume_set_radiation_thermo hold.  FFM_ERR_UNSUPPORTED, the handle unchanged: the rays are on
+ * (ffm_plume_set_radiation refuses likewise while P1 is on), or the handle is a block of a decomposed box.  FFM_ERR_ARG: negative arguments
+ * or wallEmissivity outside [0, 1].  Unpinned by reference data: the reference ships no output of a P1 run; the check is tests/plume_p1_ref.py.
+ * Not here: decomposed boxes, per-patch emissivities, MarshakRadiationFixedTemperature, coefficient models other than the constant. */
+int ffm_plume_set_radiation_p1(ffm_plume *plume, int solverFreq, double absorption, double Ehrr1, double Ehrr2, double wallEmissivity);
 /* How the rays are solved on a block of a decomposed box.  0 (default): every ray is a block-Jacobi PBiCGStab + DILU solve over
  * all ranks.  1: the staged, direction-ordered sweep -- the ranks walk the ticks of ffm_ray_schedule; in a tick a rank assembles
  * at most one ray (ffm_fvdom_ray_assemble_d), moves the inflow from its upstream neighbours' ghost values into the source
