@@ -311,6 +311,11 @@ def lib():
         "ffm_plume_ldu": ([vp], vp),
         "ffm_plume_mesh": ([vp], vp),
         "ffm_fv_multivariate_weights_tiled": ([vp, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double, dp] + [C.POINTER(C.c_void_p)] * 2 + [dp], C.c_int),
+        "ffm_fv_multivariate_weights_phiK_tiled": ([vp, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, C.c_double, dp] + [C.POINTER(C.c_void_p)] * 2
+                                                   + [dp, C.c_int, C.c_double, C.c_double, C.c_double, dp, dp, dp], C.c_int),
+        "ffm_fvc_div_phiK_sum": ([vp, C.c_double] + [dp] * 11, C.c_int),
+        "ffm_fv_lust_phi_correction3_tiled": ([vp, dp] + [C.POINTER(C.c_void_p)] * 3, C.c_int),
+        "ffm_fvm_lust_source3_sum": ([vp, C.c_double, dp] + [C.POINTER(C.c_void_p)] * 3, C.c_int),
         "ffm_comm_unique_id": ([vp], C.c_int),
         "ffm_comm_init": ([vp, C.c_int, C.c_int, vp], C.c_int),
         "ffm_comm_init_host": ([vp, C.c_int, C.c_int, vp, HOST_ALLREDUCE_FN, HOST_EXCHANGE_FN], C.c_int),

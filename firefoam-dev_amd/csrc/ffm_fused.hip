@@ -12,7 +12,9 @@
 //                       coefficients of the mixed patch condition, source with the explicit terms, addBoundaryDiag/Source
 //   k_lust_source       the explicit part of `div(phi,U) Gauss LUST grad(U)` (cases/steckler/system/fvSchemes:32) for the
 //                       three components + the ddt source:  source_c = rDeltaT*rho0*U0_c*V - V*surfaceIntegrate(phi*corr_c)
-// tests/test_fused_gpu.py checks each of them bitwise against the chain of per-operator entry points.
+//   k_mv_tile           gradients in registers on the tile walk, every face by its upwind cell: the common limiter's weights, with K as a
+//                       seventh field phi*Kf of fvc::div(phi,K), or phi*LUST::correction of U's components; k_phiK_sum / k_lust_sum sum those
+// tests/test_fused_gpu.py checks each of them bitwise against the chain of per-operator entry points (the last: tests/test_tile_face_chains_gpu.py).
 #include "ffm_mesh.hpp"
 
 constexpr int FUSE_MAX = 5;          // fields of one pass: the four species and h under the common weights (k_scalar_eqns<W,5,true,true>)
@@ -305,24 +307,38 @@ __global__ __launch_bounds__(256) void k_mv_weights(MeshView q, MvWeights a)
 // Measured at 400^3 (profiles/r03*): 11.8-12.7 ms against 17.3 ms for the three passes it replaces (k_grad_multi<3,2> + <3,4> + k_mv_weights);
 // the pass is then bound by its ~5 000 instructions per cell (54 fp64 divisions of the gradients and of NVDTVD::r), not by traffic: holding the
 // centres in LDS as well (217 VGPRs, 2 waves / SIMD) or forcing 3 waves / SIMD (168 VGPRs, 140 B of scratch) changes it by < 4 %.
-constexpr int MVT_ENT = 256, MVT_FLD = 6, MVT_RUN = 32;
+//
+// The same walk serves two more face quantities that need the upwind cell's gradient and the other cell's value and nothing else (MODE):
+//   MVT_WK    the weights, and K as one more staged field (index nf, not in the minimum): the upwind cell forms grad(K), K's own limiter,
+//             the limitedLinear weight, Kf and phi_f*Kf as k_div_phiK forms them, and stores the product per face (-> k_phiK_sum)
+//   MVT_LUST  three fields (the components of U), no limiter: the upwind cell forms phi_f*0.25*(d . grad U_i), d = Cf - C[c], as
+//             k_lust_source forms it, and stores the three products per face (-> k_lust_sum)
+// so neither grad(K) nor the nine gradients of U are written or read.  Measured at 400^3 (profiles/r09*): MVT_WK 13.7 ms + k_phiK_sum 1.8
+// against k_mv_tile 11.8 + k_grad<3> 2.9 + k_div_phiK<3> 4.9; MVT_LUST 7.8 ms + k_lust_sum 2.3 against k_grad_multi<3,3> 4.5 + k_lust_source<3> 6.4
+// (the LUST pass is bound by its face data -- flux, weight, Sf, Cf of six faces per cell -- not by instructions; 254 / 190 VGPRs, no scratch).
+constexpr int MVT_ENT = 256, MVT_FLD = 7, MVT_RUN = 32;
+enum { MVT_W = 0, MVT_WK = 1, MVT_LUST = 2 };
 struct MvTile {
     const double *vf[MVT_FLD], *vb[MVT_FLD];
-    int scheme[MVT_FLD], nf;
+    int scheme[MVT_FLD], nf;                // nf: the fields under the common limiter (MVT_WK: K is field nf; MVT_LUST: 3 fields, no limiter)
     const double *phi, *Cx, *Cy, *Cz;
     double twoByk, lo, hi;
     double *out;
     const int4 *seg, *rec;
+    double kTwoByk, kLo, kHi;               // MVT_WK: K's own limiter (scheme[nf])
+    const double *Cfx, *Cfy, *Cfz;          // MVT_LUST: face centres
+    double *q[3];                           // MVT_WK: q[0] = phi_f*Kf; MVT_LUST: q[i] = phi_f*correction(U_i)
 };
-template <int W>
+template <int W, int MODE>
 __global__ __launch_bounds__(256) void k_mv_tile(MeshView q, MvTile a)
 {
-    __shared__ double ring[MVT_FLD][3 * MVT_ENT];
+    constexpr int NRING = MODE == MVT_LUST ? 3 : MODE == MVT_WK ? MVT_FLD : MVT_FLD - 1;
+    __shared__ double ring[NRING][3 * MVT_ENT];
     __shared__ int4 shRec[3];
     const int4 sg = a.seg[blockIdx.x];
     const int gBeg = sg.x, ea = sg.y, eb = sg.z, gEnd = sg.w;
     const int t = threadIdx.x;
-    const int nf = a.nf;
+    const int nf = MODE == MVT_LUST ? 3 : MODE == MVT_WK ? a.nf + 1 : a.nf;          // staged fields
     auto stage = [&](int ee) {          // cell values + centres of entry ee -> buffer ee % 3
         if (ee < gBeg || ee >= gEnd) { if (t == 0) shRec[(ee + 3) % 3] = make_int4(0, 0, 0, 0); return; }
         const int4 R = a.rec[ee];
@@ -374,9 +390,14 @@ __global__ __launch_bounds__(256) void k_mv_tile(MeshView q, MvTile a)
                 sx[W + s] = q.Sfx[U.f[s]]; sy[W + s] = q.Sfy[U.f[s]]; sz[W + s] = q.Sfz[U.f[s]];
             }
 #pragma unroll
-            for (int s = 0; s < W; s++) {       // d = C[neighbour] - C[owner]; the cell centres of the neighbours are gathered (cache hits inside a tile)
-                dx[s] = cx - a.Cx[L.nb[s]]; dy[s] = cy - a.Cy[L.nb[s]]; dz[s] = cz - a.Cz[L.nb[s]];
-                dx[W + s] = a.Cx[U.nb[s]] - cx; dy[W + s] = a.Cy[U.nb[s]] - cy; dz[W + s] = a.Cz[U.nb[s]] - cz;
+            for (int s = 0; s < W; s++) {
+                if (MODE == MVT_LUST) {         // d = Cf - C[upwind cell] (k_lust_source): wanted on the faces whose upwind cell is c
+                    dx[s] = a.Cfx[L.f[s]] - cx; dy[s] = a.Cfy[L.f[s]] - cy; dz[s] = a.Cfz[L.f[s]] - cz;
+                    dx[W + s] = a.Cfx[U.f[s]] - cx; dy[W + s] = a.Cfy[U.f[s]] - cy; dz[W + s] = a.Cfz[U.f[s]] - cz;
+                } else {                        // d = C[neighbour] - C[owner]; the cell centres of the neighbours are gathered (cache hits inside a tile)
+                    dx[s] = cx - a.Cx[L.nb[s]]; dy[s] = cy - a.Cy[L.nb[s]]; dz[s] = cz - a.Cz[L.nb[s]];
+                    dx[W + s] = a.Cx[U.nb[s]] - cx; dy[W + s] = a.Cy[U.nb[s]] - cy; dz[W + s] = a.Cz[U.nb[s]] - cz;
+                }
             }
             const double V = q.V[c];
             const int j = q.cellB[c];
@@ -410,26 +431,55 @@ __global__ __launch_bounds__(256) void k_mv_tile(MeshView q, MvTile a)
                     ax += q.bSfx[k] * b; ay += q.bSfy[k] * b; az += q.bSfz[k] * b;
                 }
                 const double gxc = ax / V, gyc = ay / V, gzc = az / V;
-                // ---- the limiter of field i on the faces whose upwind cell is c (k_mv_weights)
                 const int sch = a.scheme[i];
+                if (MODE == MVT_LUST) {
+                    // ---- phi_f * LUST::correction(U_i) on the faces whose upwind cell is c (k_lust_source)
+                    double *__restrict__ qi = a.q[i];
 #pragma unroll
-                for (int s = 0; s < W; s++) {
-                    if (mine[s]) {          // P = owner's value (the other cell), N = c's
-                        const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[s], vl[s], P, dx[s] * gxc + dy[s] * gyc + dz[s] * gzc);
-                        lim[s] = i == 0 ? l : fmin(lim[s], l);
+                    for (int s = 0; s < 2 * W; s++) if (mine[s]) {
+                        const double corr = 0.25 * ((dx[s] * gxc + dy[s] * gyc) + dz[s] * gzc);
+                        qi[s < W ? L.f[s] : U.f[s - W]] = fl[s] * corr;
                     }
-                    if (mine[W + s]) {      // P = c's value, N = the other cell's
-                        const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[W + s], P, vu[s], dx[W + s] * gxc + dy[W + s] * gyc + dz[W + s] * gzc);
-                        lim[W + s] = i == 0 ? l : fmin(lim[W + s], l);
+                } else if (MODE == MVT_WK && i == nf - 1) {
+                    // ---- K: limitedLinear weight, Kf and phi_f*Kf on the faces whose upwind cell is c (k_div_phiK)
+#pragma unroll
+                    for (int s = 0; s < W; s++) {
+                        if (mine[s]) {          // owner = the other cell, neighbour = c
+                            const double l = mv_limiter(sch, a.kTwoByk, a.kLo, a.kHi, fl[s], vl[s], P, dx[s] * gxc + dy[s] * gyc + dz[s] * gzc);
+                            const double p0 = fl[s] >= 0 ? 1.0 : 0.0, w = l * wl[s] + (1.0 - l) * p0;
+                            const double Kf = w * vl[s] + (1.0 - w) * P;
+                            a.q[0][L.f[s]] = fl[s] * Kf;
+                        }
+                        if (mine[W + s]) {      // owner = c
+                            const double l = mv_limiter(sch, a.kTwoByk, a.kLo, a.kHi, fl[W + s], P, vu[s], dx[W + s] * gxc + dy[W + s] * gyc + dz[W + s] * gzc);
+                            const double p0 = fl[W + s] >= 0 ? 1.0 : 0.0, w = l * wu[s] + (1.0 - l) * p0;
+                            const double Kf = w * P + (1.0 - w) * vu[s];
+                            a.q[0][U.f[s]] = fl[W + s] * Kf;
+                        }
+                    }
+                } else {
+                    // ---- the limiter of field i on the faces whose upwind cell is c (k_mv_weights)
+#pragma unroll
+                    for (int s = 0; s < W; s++) {
+                        if (mine[s]) {          // P = owner's value (the other cell), N = c's
+                            const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[s], vl[s], P, dx[s] * gxc + dy[s] * gyc + dz[s] * gzc);
+                            lim[s] = i == 0 ? l : fmin(lim[s], l);
+                        }
+                        if (mine[W + s]) {      // P = c's value, N = the other cell's
+                            const double l = mv_limiter(sch, a.twoByk, a.lo, a.hi, fl[W + s], P, vu[s], dx[W + s] * gxc + dy[W + s] * gyc + dz[W + s] * gzc);
+                            lim[W + s] = i == 0 ? l : fmin(lim[W + s], l);
+                        }
                     }
                 }
 #pragma unroll
                 for (int s = 0; s < 2 * W; s++) gcur[s] = gnext[s];
             }
+            if (MODE != MVT_LUST) {
 #pragma unroll
-            for (int s = 0; s < W; s++) {
-                if (mine[s]) { const int e = L.f[s]; const double p0 = fl[s] >= 0 ? 1.0 : 0.0; a.out[e] = lim[s] * q.w[e] + (1.0 - lim[s]) * p0; }
-                if (mine[W + s]) { const int e = U.f[s]; const double p0 = fl[W + s] >= 0 ? 1.0 : 0.0; a.out[e] = lim[W + s] * q.w[e] + (1.0 - lim[W + s]) * p0; }
+                for (int s = 0; s < W; s++) {
+                    if (mine[s]) { const int e = L.f[s]; const double p0 = fl[s] >= 0 ? 1.0 : 0.0; a.out[e] = lim[s] * q.w[e] + (1.0 - lim[s]) * p0; }
+                    if (mine[W + s]) { const int e = U.f[s]; const double p0 = fl[W + s] >= 0 ? 1.0 : 0.0; a.out[e] = lim[W + s] * q.w[e] + (1.0 - lim[W + s]) * p0; }
+                }
             }
         }
         __syncthreads();            // entry ee is done: its e-1 buffer may be overwritten by the next stage()
@@ -444,8 +494,8 @@ extern "C" int ffm_fv_multivariate_weights_tiled(ffm_mesh *m, int nf, const int 
     CHECK_M(m);
     if (nf < 1 || !schemes || !phi_f || !vf || !vb || !out_w) return FFM_ERR_ARG;
     FfmFvSegs sg;
-    if (nf > MVT_FLD || m->A->maxW > 3 || !ffm_tile_fv_segments(m->A, MVT_RUN, &sg)) return FFM_ERR_UNSUPPORTED;
-    MvTile a;
+    if (nf > MVT_FLD - 1 || m->A->maxW > 3 || !ffm_tile_fv_segments(m->A, MVT_RUN, &sg)) return FFM_ERR_UNSUPPORTED;
+    MvTile a = {};
     for (int i = 0; i < MVT_FLD; i++) {
         const int qq = i < nf ? i : 0;
         if (i < nf && ((schemes[qq] != 2 && schemes[qq] != 3) || !vf[qq] || (m->B && !vb[qq]))) return FFM_ERR_ARG;
@@ -453,7 +503,54 @@ extern "C" int ffm_fv_multivariate_weights_tiled(ffm_mesh *m, int nf, const int 
     }
     a.nf = nf; a.phi = phi_f; a.Cx = m->C[0]; a.Cy = m->C[1]; a.Cz = m->C[2]; a.twoByk = 2.0 / std::max(k, 1e-15); a.lo = lo; a.hi = hi; a.out = out_w;
     a.seg = sg.seg; a.rec = sg.rec;
-    hipLaunchKernelGGL(k_mv_tile<3>, dim3(sg.nSeg), dim3(256), 0, m->ctx->stream, mview(m), a);
+    hipLaunchKernelGGL((k_mv_tile<3, MVT_W>), dim3(sg.nSeg), dim3(256), 0, m->ctx->stream, mview(m), a);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// the same pass with K as the seventh staged field: out_w as above (K is not in the minimum), out_phiK[e] = phi_f*Kf of every internal face
+// with Kf from K's own limitedLinear / limitedLinear01 weight (schemeK, kK, loK, hiK) -- what k_div_phiK forms per face, stored once by the
+// face's upwind cell for ffm_fvc_div_phiK_sum.  Refusals as above, with nothing written.
+extern "C" int ffm_fv_multivariate_weights_phiK_tiled(ffm_mesh *m, int nf, const int *schemes, double k, double lo, double hi, const double *phi_f,
+                                                      const double *const *vf, const double *const *vb, double *out_w, int schemeK, double kK,
+                                                      double loK, double hiK, const double *K, const double *K_b, double *out_phiK)
+{
+    CHECK_M(m);
+    if (nf < 1 || !schemes || !phi_f || !vf || !vb || !out_w || (schemeK != 2 && schemeK != 3) || !K || (m->B && !K_b) || !out_phiK) return FFM_ERR_ARG;
+    FfmFvSegs sg;
+    if (nf > MVT_FLD - 1 || m->A->maxW > 3 || !ffm_tile_fv_segments(m->A, MVT_RUN, &sg)) return FFM_ERR_UNSUPPORTED;
+    MvTile a = {};
+    for (int i = 0; i < MVT_FLD; i++) {
+        const int qq = i < nf ? i : 0;
+        if (i < nf && ((schemes[qq] != 2 && schemes[qq] != 3) || !vf[qq] || (m->B && !vb[qq]))) return FFM_ERR_ARG;
+        a.vf[i] = vf[qq]; a.vb[i] = vb[qq]; a.scheme[i] = schemes[qq];
+    }
+    a.vf[nf] = K; a.vb[nf] = K_b; a.scheme[nf] = schemeK;
+    a.nf = nf; a.phi = phi_f; a.Cx = m->C[0]; a.Cy = m->C[1]; a.Cz = m->C[2]; a.twoByk = 2.0 / std::max(k, 1e-15); a.lo = lo; a.hi = hi; a.out = out_w;
+    a.kTwoByk = 2.0 / std::max(kK, 1e-15); a.kLo = loK; a.kHi = hiK; a.q[0] = out_phiK;
+    a.seg = sg.seg; a.rec = sg.rec;
+    hipLaunchKernelGGL((k_mv_tile<3, MVT_WK>), dim3(sg.nSeg), dim3(256), 0, m->ctx->stream, mview(m), a);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// phi_f*LUST::correction(U_i) of the three components on every internal face, by the face's upwind cell from the gradient it forms in
+// registers (k_mv_tile<MVT_LUST>): what k_lust_source forms per face from the nine gradient arrays, for ffm_fvm_lust_source3_sum.
+extern "C" int ffm_fv_lust_phi_correction3_tiled(ffm_mesh *m, const double *phi_f, const double *const *U, const double *const *U_b,
+                                                 double *const *out_q)
+{
+    CHECK_M(m);
+    if (!phi_f || !U || !U_b || !out_q) return FFM_ERR_ARG;
+    FfmFvSegs sg;
+    if (m->A->maxW > 3 || !ffm_tile_fv_segments(m->A, MVT_RUN, &sg)) return FFM_ERR_UNSUPPORTED;
+    if (!m->Cf[0]) { ffm_set_error("ffm_fv_lust_phi_correction3_tiled: face centres not set (ffm_mesh_set_face_centres)"); return FFM_ERR_ARG; }
+    MvTile a = {};
+    for (int i = 0; i < 3; i++) if (!U[i] || (m->B && !U_b[i]) || !out_q[i]) return FFM_ERR_ARG;
+    for (int i = 0; i < MVT_FLD; i++) { a.vf[i] = U[i < 3 ? i : 0]; a.vb[i] = U_b[i < 3 ? i : 0]; }
+    for (int i = 0; i < 3; i++) a.q[i] = out_q[i];
+    a.nf = 3; a.phi = phi_f; a.Cx = m->C[0]; a.Cy = m->C[1]; a.Cz = m->C[2]; a.Cfx = m->Cf[0]; a.Cfy = m->Cf[1]; a.Cfz = m->Cf[2];
+    a.seg = sg.seg; a.rec = sg.rec;
+    hipLaunchKernelGGL((k_mv_tile<3, MVT_LUST>), dim3(sg.nSeg), dim3(256), 0, m->ctx->stream, mview(m), a);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
@@ -557,6 +654,66 @@ __global__ __launch_bounds__(256) void k_div_phiK(MeshView q, DivPhiK a)
         a.divK[c] = acc / q.V[c];
         a.ddtK[c] = a.rdt * (a.rho[c] * P - a.rho0[c] * a.K0[c]);
         a.ndpdt[c] = -a.dpdt[c];
+    }
+}
+
+// k_div_phiK without its face loop bodies: the products phi_f*Kf come from the face array the tile pass wrote (k_mv_tile<MVT_WK>), summed
+// in k_div_phiK's order -- lower faces (subtracted), upper faces, patch faces
+struct PhiKSum {
+    const double *qf, *Kb, *phib, *K, *rho, *rho0, *K0, *dpdt;
+    double *divK, *ddtK, *ndpdt;
+    double rdt;
+};
+template <int W>
+__global__ __launch_bounds__(256) void k_phiK_sum(MeshView q, PhiKSum a)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci;
+        RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
+        double ql[W], qu[W];
+#pragma unroll
+        for (int s = 0; s < W; s++) { ql[s] = a.qf[L.f[s]]; qu[s] = a.qf[U.f[s]]; }
+        double acc = 0.0;
+#pragma unroll
+        for (int s = 0; s < W; s++) if (L.on[s]) acc = acc - ql[s];
+#pragma unroll
+        for (int s = 0; s < W; s++) if (U.on[s]) acc += qu[s];
+        const int j = q.cellB[c];
+        if (j >= 0) for (int t = q.bcStart[j]; t < q.bcStart[j + 1]; t++) { const int k = q.bcItem[t]; acc += a.phib[k] * a.Kb[k]; }
+        a.divK[c] = acc / q.V[c];
+        a.ddtK[c] = a.rdt * (a.rho[c] * a.K[c] - a.rho0[c] * a.K0[c]);
+        a.ndpdt[c] = -a.dpdt[c];
+    }
+}
+
+// k_lust_source without its face loop bodies: the products phi_f*correction(U_i) come from the three face arrays of k_mv_tile<MVT_LUST>
+struct LustSum {
+    const double *qf[3], *U0[3];
+    double *src[3];
+    const double *rho0;
+    double rdt;
+};
+template <int W>
+__global__ __launch_bounds__(256) void k_lust_sum(MeshView q, LustSum a)
+{
+    CELL_SCHED(ci, q) {
+        const int c = (int)ci;
+        RowEnt<W> L, U; load_lower<W>(q.v, c, L); load_upper<W>(q.v, c, U);
+        const double V = q.V[c], r0 = a.rho0[c];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            const double *__restrict__ qf = a.qf[i];
+            double ql[W], qu[W];
+#pragma unroll
+            for (int s = 0; s < W; s++) { ql[s] = qf[L.f[s]]; qu[s] = qf[U.f[s]]; }
+            double acc = 0.0;
+#pragma unroll
+            for (int s = 0; s < W; s++) if (L.on[s]) acc -= ql[s];
+#pragma unroll
+            for (int s = 0; s < W; s++) if (U.on[s]) acc += qu[s];
+            const double divc = acc / V;
+            a.src[i][c] = a.rdt * r0 * a.U0[i][c] * V - V * divc;
+        }
     }
 }
 
@@ -769,6 +926,38 @@ extern "C" int ffm_fvc_div_phiK_terms(ffm_mesh *m, int scheme, double k, double 
     if (m->A->maxW <= 3) LAUNCH_CELLS(k_div_phiK<3>, mview(m), a);
     else if (m->A->maxW <= 4) LAUNCH_CELLS(k_div_phiK<4>, mview(m), a);
     else LAUNCH_CELLS(k_div_phiK<8>, mview(m), a);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// the same three cell fields from the face products phiK_f = phi_f*Kf of ffm_fv_multivariate_weights_phiK_tiled: one row pass, any row width
+extern "C" int ffm_fvc_div_phiK_sum(ffm_mesh *m, double rDeltaT, const double *phiK_f, const double *phi_b, const double *K, const double *K_b,
+                                    const double *rho, const double *rho0, const double *K0, const double *dpdt, double *divK, double *ddtK,
+                                    double *negDpdt)
+{
+    CHECK_M(m);
+    if (!phiK_f || !K || !rho || !rho0 || !K0 || !dpdt || !divK || !ddtK || !negDpdt || (m->B && (!phi_b || !K_b))) return FFM_ERR_ARG;
+    PhiKSum a;
+    a.qf = phiK_f; a.Kb = K_b; a.phib = phi_b; a.K = K; a.rho = rho; a.rho0 = rho0; a.K0 = K0; a.dpdt = dpdt;
+    a.divK = divK; a.ddtK = ddtK; a.ndpdt = negDpdt; a.rdt = rDeltaT;
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_phiK_sum<W>, mview(m), a));
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// ffm_fvm_lust_source3 from the face products q_f[i] = phi_f*correction(U_i) of ffm_fv_lust_phi_correction3_tiled: one row pass, any row width
+extern "C" int ffm_fvm_lust_source3_sum(ffm_mesh *m, double rDeltaT, const double *rho0, const double *const *U0, const double *const *q_f,
+                                        double *const *source)
+{
+    CHECK_M(m);
+    if (!rho0 || !U0 || !q_f || !source) return FFM_ERR_ARG;
+    LustSum a;
+    for (int i = 0; i < 3; i++) {
+        if (!U0[i] || !q_f[i] || !source[i]) return FFM_ERR_ARG;
+        a.qf[i] = q_f[i]; a.U0[i] = U0[i]; a.src[i] = source[i];
+    }
+    a.rho0 = rho0; a.rdt = rDeltaT;
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_lust_sum<W>, mview(m), a));
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }

@@ -246,6 +246,7 @@ extern "C" int ffm_plume_create_block(ffm_ctx *ctx, int gx, int gy, int gz, cons
     P->mvSelection = getenv("FFM_PLUME_INDEPENDENT_LIMITERS") == nullptr;
     { const char *e = getenv("FFM_PLUME_SEPARATE_H"); P->separateH = e && atoi(e) != 0; }
     if (P->mvSelection) { P->wMv = dalloc(P, nNat); if (fused) for (int j = 0; j < 2; j++) for (int d = 0; d < 3; d++) P->mvG[j][d] = NN(); }
+    if (P->mvSelection && fused && P->oneBlock) { P->phiKf = dalloc(P, nNat); P->KbM = dalloc(P, B); }
     for (int j = 0; j < 4; j++) {
         for (int d = 0; d < 3; d++) P->gM[j][d] = fused ? NN() : nullptr;
         P->spD[j] = fused ? NN() : nullptr; P->spS[j] = fused ? NN() : nullptr; P->suM[j] = fused ? NN() : nullptr;

@@ -61,10 +61,11 @@ struct ffm_plume {
     //   wN[8-10] wFuel, Qdot, Yt: combustion_correct -> species_eqns, radiation_correct, e_eqn | pc_ddtCorr_ops: rho0*U0 | pc_p_rgh_eqn_ops: [8] div
     //   wN[11]   species_eqns_ops: nu_i*wFuel
     //   wF[0]    hydrostatic_init: rhof | u_eqn: muf | alphaEff_f: combustion_correct -> species_eqns, e_eqn | p_corrector: rhorAUf ->
-    //   wF[1]    hydrostatic_init, u_buoyancy, pc_phig_flux_ops: snGrad(rho) | mv_weights_ops: limiter
-    //   wF[2]    hydrostatic_init: phig | u_buoyancy: snGrad(p_rgh) | p_corrector: phig ->
+    //   wF[1]    hydrostatic_init, u_buoyancy, pc_phig_flux_ops: snGrad(rho) | u_sources (fused single block): phi*LUST correction of Ux |
+    //            mv_weights_ops: limiter
+    //   wF[2]    hydrostatic_init: phig | u_buoyancy: snGrad(p_rgh) | u_sources (fused single block): phi*LUST correction of Uy | p_corrector: phig ->
     //   wF[3]    u_eqn (ops): LUST weights -> | scalar_transport, e_K_terms_ops: a field's own weights | p_corrector: phiHbyA ->
-    //   wF[4]    u_buoyancy (ops): reconstruct's argument, then u_source_ops: phi*correction | e_K_terms_ops: phi*Kf | pc_ddtCorr_ops: flux(rho0*U0),
+    //   wF[4]    u_buoyancy (ops): reconstruct's argument, then u_source_ops: phi*correction (fused single block: of Uz) | e_K_terms_ops: phi*Kf | pc_ddtCorr_ops: flux(rho0*U0),
     //            then p_corrector (ops, blocks): p_rghEqn.flux() ->      wF[5]  pc_flux_U (ops, blocks): reconstruct's argument
     //   wB[0]    hydrostatic_init: rhob | e_K_terms: Kb, then (after Kb's last reader) plume_rad_fraction: burner flux | p_corrector: rhorAUfb ->
     //   wB[1-3]  Ub: U_boundary -> the end of the stage that called it (u_eqn, e_K_terms, p_corrector); in between hydrostatic_init: [1] fTop |
@@ -83,6 +84,10 @@ struct ffm_plume {
     // one limiter per field, as round 1 had it; wMv is then null)
     bool mvSelection = true;
     double *wMv = nullptr, *mvG[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    // fvc::div(phi,K) of EEqn on the fused single block: the tile pass of mv_weights also forms phi_f*Kf per face (phiKf [nNat]) from K's
+    // patch values (KbM [B]), and e_K_terms sums them.  Both live from mv_weights over the species solves and radiation_correct to
+    // e_K_terms; phiKValid: this step's mv_weights wrote them (not with weights handed in, one limiter per field, a refused tile form)
+    double *phiKf = nullptr, *KbM = nullptr; bool phiKValid = false;
     bool fused = true;                     // FFM_PLUME_UNFUSED: one kernel per operator (tests compare the two paths)
     bool separateH = false;                // FFM_PLUME_SEPARATE_H: h assembled and solved after the species, never as their fifth system
     int jointSteps = 0;                    // steps in which h was the fifth system of the species' pass and solve (ffm_plume_joint_steps)

@@ -120,8 +120,17 @@ static int u_sources(ffm_plume *P, const double *mub)
         if (ops) FFM_TRY(u_source_ops(P, c));
     }
     if (ops) return FFM_OK;
-    // one gradient pass for the three components, one pass for the LUST correction + the ddt source (ffm_fused.hip)
     const double *uf[3] = {P->U[0], P->U[1], P->U[2]}, *ub[3] = {P->Ub[0], P->Ub[1], P->Ub[2]}, *u0[3] = {P->U0[0], P->U0[1], P->U0[2]};
+    // Single block, no sub-grid model (whose stress divergence and kEqn want the gradients): every face's phi*correction by its upwind cell
+    // on the tile walk, then one row pass for the sums and the ddt source -- no gradient arrays (ffm_fused.hip: k_mv_tile<MVT_LUST>,
+    // k_lust_sum; bit for bit the two passes below, which take over where ffm_tile_fv_segments refuses the box)
+    if (P->oneBlock && !P->turbModel) {
+        double *qf[3] = {P->wF[1], P->wF[2], P->wF[4]};
+        const int rc = ffm_fv_lust_phi_correction3_tiled(m, P->phi, uf, ub, qf);
+        if (rc == FFM_OK) return ffm_fvm_lust_source3_sum(m, P->rdt, P->rho0, u0, qf, P->Usrc);
+        if (rc != FFM_ERR_UNSUPPORTED) return rc;
+    }
+    // one gradient pass for the three components, one pass for the LUST correction + the ddt source (ffm_fused.hip)
     double *ggx[3] = {P->gM[0][0], P->gM[1][0], P->gM[2][0]}, *ggy[3] = {P->gM[0][1], P->gM[1][1], P->gM[2][1]}, *ggz[3] = {P->gM[0][2], P->gM[1][2], P->gM[2][2]};
     FFM_TRY(ffm_fvc_grad_multi(m, 3, uf, ub, ggx, ggy, ggz));
     for (int c = 0; c < 3; c++) { FFM_TRY(HX(P, ggx[c])); FFM_TRY(HX(P, ggy[c])); FFM_TRY(HX(P, ggz[c])); }
@@ -302,9 +311,18 @@ static int mv_weights_ops(ffm_plume *P, const MvFields &f)
 // mvConvection (solver/YEEqn.H:1-10): the common limiter over the five species and h, from the fields as they are now -> P->wMv
 static int mv_weights(ffm_plume *P)
 {
+    P->phiKValid = false;
     if (!P->mvSelection) return FFM_OK;                                  // one limiter per field: the equations evaluate their own
     if (P->mvOverride) { P->mvOverride = false; return FFM_OK; }         // weights of this step were handed in: wMv stays as uploaded
     ffm_mesh *m = P->mesh;
+    // K rides on the tile pass below (fused single block): its patch values first -- U.correctBoundaryConditions() after the momentum solve;
+    // nothing between here and e_K_terms writes U, phi or U's patch conditions -- into a member, Ub's slots being Nb's and hb's next
+    const bool withK = P->fused && P->oneBlock && P->phiKf;
+    if (withK) {
+        FFM_TRY(U_boundary(P));
+        double *Kb = P->KbM; const double *b0 = P->Ub[0], *b1 = P->Ub[1], *b2 = P->Ub[2];
+        forN(P, P->B, [=] __device__(long k) { Kb[k] = 0.5 * ((b0[k] * b0[k] + b1[k] * b1[k]) + b2[k] * b2[k]); });
+    }
     double *Nb = P->wB[1], *hb = P->wB[3];
     MvFields f = {{P->hs, nullptr, nullptr, nullptr, nullptr, P->Y[INERT]}, {hb, nullptr, nullptr, nullptr, nullptr, Nb}};
     for (int i = 0, j = 0; i < NSP; i++) if (i != INERT) {
@@ -319,7 +337,11 @@ static int mv_weights(ffm_plume *P)
     if (!P->fused) return mv_weights_ops(P, f);
     // gradients of the six fields + the common limiter in ONE pass with the cell values staged through LDS on the tile numbering
     // (ffm_fused.hip: k_mv_tile; bit for bit mv_weights_grad_multi, which takes over where ffm_tile_fv_segments refuses the box)
-    const int rc = ffm_fv_multivariate_weights_tiled(m, 6, MV_SCHEMES, 1.0, 0.0, 1.0, P->phi, f.vf, f.vb, P->wMv);
+    // With K as the seventh staged field the pass also leaves phi_f*Kf of fvc::div(phi,K) per face for e_K_terms (`Gauss limitedLinear 1`)
+    const int rc = withK ? ffm_fv_multivariate_weights_phiK_tiled(m, 6, MV_SCHEMES, 1.0, 0.0, 1.0, P->phi, f.vf, f.vb, P->wMv, 2, 1.0, 0.0, 1.0, P->K,
+                                                                  P->KbM, P->phiKf)
+                         : ffm_fv_multivariate_weights_tiled(m, 6, MV_SCHEMES, 1.0, 0.0, 1.0, P->phi, f.vf, f.vb, P->wMv);
+    if (rc == FFM_OK) P->phiKValid = withK;
     return rc == FFM_ERR_UNSUPPORTED ? mv_weights_grad_multi(P, f) : rc;
 }
 
@@ -483,6 +505,9 @@ static int e_K_terms_ops(ffm_plume *P, const double *Kb, const double *kgx, cons
 static int e_K_terms(ffm_plume *P, const KTerms &kt)
 {
     ffm_mesh *m = P->mesh;
+    // this step's mv_weights left phi_f*Kf on the faces (k_mv_tile<MVT_WK>): one row pass sums them -- no grad(K), no limiter here
+    if (P->phiKValid)
+        return ffm_fvc_div_phiK_sum(m, P->rdt, P->phiKf, P->phib, P->K, P->KbM, P->rho, P->rho0, P->K0, P->dpdt, kt.divK, kt.ddtK, kt.ndpdt);
     double *Kb = P->wB[0], *kgx = P->wN[1], *kgy = P->wN[2], *kgz = P->wN[3];
     FFM_TRY(U_boundary(P));     // U.correctBoundaryConditions() after the momentum solve
     const double *b0 = P->Ub[0], *b1 = P->Ub[1], *b2 = P->Ub[2];

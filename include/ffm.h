@@ -360,6 +360,27 @@ int ffm_fv_multivariate_weights(ffm_mesh *m, int nf, const int *schemes, double 
  * case, cells have more than 3 lower / upper neighbours or nf > 6: the caller then runs the two-pass form.                            */
 int ffm_fv_multivariate_weights_tiled(ffm_mesh *m, int nf, const int *schemes, double k, double lo, double hi, const double *phi_f,
                                       const double *const *vf, const double *const *vb, double *out_w);
+/* The same pass with one more staged field K (patch values K_b) that is NOT in the minimum: out_w as above, and out_phiK[e] = phi_f*Kf on
+ * every internal face, Kf interpolated with K's own limitedLinear (schemeK 2) / limitedLinear01 (3) weight of coefficient kK, bounds loK, hiK,
+ * from the gradient the face's upwind cell forms in registers -- per face what ffm_fvc_grad + ffm_fvc_div_phiK_terms form, bit for bit, so
+ * fvc::grad(K) is neither written nor read.  ffm_fvc_div_phiK_sum finishes the three cell fields.  Same refusals, nothing written.   */
+int ffm_fv_multivariate_weights_phiK_tiled(ffm_mesh *m, int nf, const int *schemes, double k, double lo, double hi, const double *phi_f,
+                                           const double *const *vf, const double *const *vb, double *out_w, int schemeK, double kK,
+                                           double loK, double hiK, const double *K, const double *K_b, double *out_phiK);
+/* divK, ddtK, -dpdt of ffm_fvc_div_phiK_terms from the face products phiK_f of the call above (lower faces, upper faces, patch faces, in
+ * that order): one row pass on any mesh                                                                                              */
+int ffm_fvc_div_phiK_sum(ffm_mesh *m, double rDeltaT, const double *phiK_f, const double *phi_b, const double *K, const double *K_b,
+                         const double *rho, const double *rho0, const double *K0, const double *dpdt, double *divK, double *ddtK,
+                         double *negDpdt);
+/* `div(phi,U) Gauss LUST grad(U)`, explicit part, by the same tile walk: out_q[i][e] = phi_f*LUST::correction(U_i) on every internal face,
+ * from grad(U_i) of the face's upwind cell formed in registers (U[3], U_b[3], out_q[3]: host arrays of device pointers).  With
+ * ffm_fvm_lust_source3_sum bit for bit ffm_fvc_grad_multi + ffm_fvm_lust_source3 without the nine gradient arrays.  FFM_ERR_UNSUPPORTED,
+ * nothing written, where ffm_fv_multivariate_weights_tiled refuses.                                                                  */
+int ffm_fv_lust_phi_correction3_tiled(ffm_mesh *m, const double *phi_f, const double *const *U, const double *const *U_b,
+                                      double *const *out_q);
+/* source_c = rDeltaT*rho0*U0_c*V - V*surfaceIntegrate(q_f[c]) from the face products of the call above: one row pass on any mesh */
+int ffm_fvm_lust_source3_sum(ffm_mesh *m, double rDeltaT, const double *rho0, const double *const *U0, const double *const *q_f,
+                             double *const *source);
 
 /* filteredLinear2V k l: the face weights of a VECTOR field, one limiter per face for its three components
  * (`div(phi,U) Gauss filteredLinear2V 0.2 0.05`, cases/wallFireSpread2D/system/fvSchemes:41, cases/pyrolysis1D/system/fvSchemes:39;
