@@ -481,6 +481,199 @@ extern "C" int b1_burner_bcs(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, double t
     return 0;
 }
 
+// ---- the physics handles of include/fireFoamHandles.H and the patch conditions, reductions and included headers around them on ANY
+// mesh -- whole, or one rank's sub-domain with ghost cells (tests/test_foam_handles_decomposed_gpu.py).  Every field stays on the
+// device; host arrays as in b1_demo (cell arrays [N] with the ghost cells, boundary arrays [B] = this rank's faces of every patch).
+//   a  hePsiThermoJanaf: he = Hs(T), then correct() starting its Newton iteration from Tstart
+//      rho = thermo.rho()*rhoFac (so that compressibleContinuityErrs.H has something to report), rho.oldTime() = rho
+//   b  kEqnLES: correctNut() from k0; G of these fields as correct() forms it; divDevRhoReff(U) in a UEqn, solved; correct()
+//   c  eddyDissipationEDC::correct() and the fuel's specie equation with totalFlowRateAdvectiveDiffusive on the inlet and inletOutlet
+//      on the open patches; U with flowRateInletVelocity on the inlet
+//   d  P1 with Marshak walls: one calculate()
+//   e  compressibleCourantNo.H, compressibleContinuityErrs.H, gMin / gMax / gAverage / min / max of two fields, fvc::domainIntegrate
+// The order is chosen so that what is handed back without a solve of its own -- G, the EDC rate, the value fraction, the explicit
+// part of divDevRhoReff -- is a function of the inputs, with no Krylov solve behind it: the k equation comes last of b and c.
+// All Krylov tolerances 1e-10.  Returns the number of solves logged (Yi, Ux, Uy, Uz, k, G).
+struct b1PhysicsData
+{
+    double deltaT, t; int nTable; const double* table; double massFluxFraction;
+    ffm_thermo* th; int nSpecies; const char* const* specieNames;
+    const double* const* Y; const double* const* Yb;
+    const double *T, *Tb, *Tstart, *p, *pb, *fixesT, *rhoFac, *rhoFacB;
+    const double *phiF, *phiB, *U0; const double* const* bcU; const double *inletMask, *inletNf;       // bcU: 3 x {f, ref, refGrad}; inletNf [3][B]
+    const double *k0, *delta; const double* const* bcK; const double *nutZeroGrad, *alphatZeroGrad; double alphaK;
+    int fuel, o2; double s, qFuel; const double* massCoeffs;
+    const double* const* bcY;                                     // {f (-1: inletOutlet), ref, refGrad} of the fuel specie
+    double a, e, sigmaS, Cscatter; const double *E, *emissivity;
+    const double *fa, *fab, *fc, *fcb;                            // the two fields of the reductions: cells, boundary faces
+    // out
+    double *thermoOut, *thermobOut;                               // [4][N], [4][B]: T, psi, mu, alpha
+    double *nut0Out, *nut0bOut;                                   // [2][N], [2][B]: nut, alphat after correctNut() from k0
+    double *wFuelOut, *GOut, *kOut;                               // [N]
+    double *nutOut, *nutbOut;                                     // [2][N], [2][B]: nut, alphat after correct()
+    double *srcOut, *UOut, *UbOut;                                // [3][N], [3][N], [3][B]
+    double *YiOut, *YbOut, *fOut;                                 // [N], [B], [B]
+    double *p1Out;                                                // [2][N] G, Ru
+    double *scalars;                                              // [20], see below
+    int* nIter;                                                   // [6]
+};
+extern "C" int b1_physics(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, const b1PhysicsData* io)
+{
+    const double sigma = 5.670367e-8;
+    fvMesh mesh(ctx, ldu, msh, io->deltaT);
+    Time runTime(io->t, io->deltaT);
+    runTime.link(mesh.deltaT, mesh.timeValue);
+    const solverControls krylov = {FFM_PBICGSTAB, FFM_DILU, 1e-10, 0, 0, 1000, 1};
+    for (const char* n : {"k", "kFinal", "U", "UFinal", "Yi", "YiFinal"}) mesh.solvers[n] = krylov;
+    mesh.solvers["G"] = mesh.solvers["GFinal"] = {FFM_PCG, FFM_DIC, 1e-10, 0, 0, 1000, 1};
+    mesh.divSchemes["div(phi,U)"] = {4, 1, 0, 1};               // Gauss LUST grad(U)
+    mesh.divSchemes["div(phi,k)"] = {2, 1, 0, 1};               // Gauss limitedLinear 1
+    mesh.divSchemes["div(phi,Yi_h)"] = {3, 1, 0, 1};            // Gauss limitedLinear01 1
+    mesh.equationRelaxation["k"] = io->alphaK;
+    const label N = mesh.nCells, B = mesh.nBoundary;
+    const std::vector<double> zeroB(B, 0.0);
+
+    // ---- a: thermo
+    hePsiThermoJanaf thermo(mesh, io->th, io->fixesT);
+    for (int i = 0; i < io->nSpecies; i++) {
+        thermo.comp_.species_.push_back(io->specieNames[i]); thermo.comp_.active_.push_back(true);
+        thermo.comp_.Y_.append(new volScalarField(thermo.comp_.species_.back(), mesh));
+        thermo.comp_.Y_[i].v.assignHost(io->Y[i]); thermo.comp_.Y_[i].b.assignHost(io->Yb[i]);
+    }
+    thermo.p().v.assignHost(io->p); thermo.p().b.assignHost(io->pb);
+    thermo.T().v.assignHost(io->T); thermo.T().b.assignHost(io->Tb);
+    thermo.initHe();
+    thermo.T().v.assignHost(io->Tstart);
+    thermo.correct();
+    {
+        const volScalarField* f[4] = {&thermo.T(), &thermo.psi(), &thermo.mu(), &thermo.alpha()};
+        for (int k = 0; k < 4; k++) { f[k]->v.toHost(io->thermoOut + (size_t)k*N); f[k]->b.toHost(io->thermobOut + (size_t)k*B); }
+    }
+    volScalarField rhoFac("rhoFac", mesh); rhoFac.v.assignHost(io->rhoFac); rhoFac.b.assignHost(io->rhoFacB);
+    volScalarField rho("rho", thermo.rho()*rhoFac);
+    rho.storeOldTime();
+
+    // ---- flux and velocity: flowRateInletVelocity on the inlet, the caller's mixed conditions elsewhere
+    const surfaceScalarField phi(surfaceFromHost(mesh, io->phiF, io->phiB));
+    volVectorField U("U", mesh);
+    mesh.store("rho", rho); mesh.store("phi", phi); mesh.store("U", U);
+    {
+        auto mask = std::make_shared<dField>(ctx, B); mask->assignHost(io->inletMask);
+        Function1Table mdot;
+        for (int i = 0; i < io->nTable; i++) mdot.xy.push_back({io->table[2*i], io->table[2*i + 1]});
+        for (int d = 0; d < 3; d++) {
+            U.v[d].assignHost(io->U0 + (size_t)d*N);
+            U.bc[d] = makeBC(mesh, io->bcU[3*d], io->bcU[3*d + 1], io->bcU[3*d + 2]);
+            U.bc[d]->flowRateMask = mask; U.bc[d]->massFlowRate = mdot;
+            U.bc[d]->flowRateNf = std::make_shared<dField>(ctx, B); U.bc[d]->flowRateNf->assignHost(io->inletNf + (size_t)d*B);
+        }
+    }
+    U.correctBoundaryConditions(); U.storeOldTime();
+
+    // ---- b: turbulence
+    kEqnLES turb(mesh, rho, U, phi, thermo.mu(), thermo.alpha(), io->nutZeroGrad, io->alphatZeroGrad);
+    turb.k_.v.assignHost(io->k0); turb.k_.bc = makeBC(mesh, io->bcK[0], io->bcK[1], io->bcK[2]);
+    turb.k_.correctBoundaryConditions();
+    turb.delta_.v.assignHost(io->delta);
+    turb.correctNut();
+    turb.nut_.v.toHost(io->nut0Out); turb.alphat_.v.toHost(io->nut0Out + N);
+    turb.nut_.b.toHost(io->nut0bOut); turb.alphat_.b.toHost(io->nut0bOut + B);
+    {   // the production term as kEqnLES::correct() forms it
+        std::vector<dField> g; turb.gradU(U, g);
+        const double* gp[9]; for (int k = 0; k < 9; k++) gp[k] = g[k].data();
+        volScalarField G("G", mesh);
+        FFM_FOAM_CHK(ffm_les_keqn_G(mesh.msh, gp, turb.nut_.v.data(), G.v.data()));
+        G.v.toHost(io->GOut);
+    }
+
+    // ---- c: combustion->correct() on the state before the k solve
+    eddyDissipationEDC combustion(thermo, rho, turb, io->fuel, io->o2, io->s, io->qFuel, std::vector<scalar>(io->massCoeffs, io->massCoeffs + io->nSpecies));
+    combustion.correct();
+    combustion.wFuel().v.toHost(io->wFuelOut);
+
+    // ---- the fuel's specie equation
+    {
+        volScalarField& Yi = thermo.comp_.Y_[io->fuel];
+        Yi.bc = makeBC(mesh, io->bcY[0], io->bcY[1], io->bcY[2]);
+        Yi.bc->tfradMask = std::make_shared<dField>(ctx, B); Yi.bc->tfradMask->assignHost(io->inletMask);
+        const volScalarField alphaEff(turb.alphaEff());           // also what totalFlowRateAdvectiveDiffusive looks up
+        Yi.correctBoundaryConditions(); Yi.storeOldTime();
+        fv::convectionScheme<scalar> mvConvection(mesh, phi, mesh.divSchemeOf("div(phi,Yi_h)"));
+        fvScalarMatrix YiEqn
+        (
+            fvm::ddt(rho, Yi)
+          + mvConvection.fvmDiv(phi, Yi)
+          - fvm::laplacian(alphaEff, Yi)
+         ==
+            combustion.R(Yi)
+        );
+        YiEqn.solve(mesh.solver("Yi"));
+        Yi.v.toHost(io->YiOut); Yi.b.toHost(io->YbOut); Yi.bc->f.toHost(io->fOut);
+    }
+
+    // ---- b again: the momentum equation with divDevRhoReff(U) (its explicit part still a function of the inputs), then the k equation
+    {
+        fvVectorMatrix stress(turb.divDevRhoReff(U));
+        stress.ensure();
+        for (int d = 0; d < 3; d++) stress.source[d].toHost(io->srcOut + (size_t)d*N);
+        fvVectorMatrix UEqn
+        (
+            fvm::ddt(rho, U) + fvm::div(phi, U)
+          + stress
+        );
+        UEqn.solve(mesh.solver("U"));
+    }
+    for (int d = 0; d < 3; d++) { U.v[d].toHost(io->UOut + (size_t)d*N); U.b[d].toHost(io->UbOut + (size_t)d*B); }
+    turb.correct();
+    turb.k_.v.toHost(io->kOut);
+    turb.nut_.v.toHost(io->nutOut); turb.alphat_.v.toHost(io->nutOut + N);
+    turb.nut_.b.toHost(io->nutbOut); turb.alphat_.b.toHost(io->nutbOut + B);
+
+    // ---- d: radiation
+    volScalarField Ef("E", mesh); Ef.v.assignHost(io->E);
+    P1 p1(mesh, thermo.T(), 1, io->a, io->e, 0.0, io->sigmaS, io->Cscatter, sigma);
+    p1.emission = [&Ef]() { return Ef; };
+    p1.emissivity().assignHost(io->emissivity);
+    p1.correct();
+    p1.G_.v.toHost(io->p1Out);
+    { const volScalarField Ru("Ru", io->a*p1.G_ - Ef); Ru.v.toHost(io->p1Out + N); }
+
+    // ---- e: scalars.  [0] CoNum [1] meanCoNum [2] sumLocalContErr [3] globalContErr [4] cumulativeContErr [5] Rp = 4 e sigma
+    //      [6..10] gMin, gMax, gAverage, min, max of the field whose extreme sits on a boundary face; [11..15] of the one whose extreme
+    //      sits in a cell; [16] domainIntegrate of the first; [17] gSum of the first (gAverage's numerator)
+    double* sc = io->scalars;
+    {
+        #include "compressibleCourantNo.H"
+        sc[0] = CoNum; sc[1] = meanCoNum;
+    }
+    {
+        // the header keeps sum local and global to itself (it prints them): its two expressions again, then the header itself,
+        // which adds the global error to cumulativeContErr
+        const dimensionedScalar totalMass = fvc::domainIntegrate(rho);
+        sc[2] = (fvc::domainIntegrate(mag(rho - thermo.rho()))/totalMass).value();
+        sc[3] = (fvc::domainIntegrate(rho - thermo.rho())/totalMass).value();
+        scalar cumulativeContErr = 0.25;
+        #include "compressibleContinuityErrs.H"
+        sc[4] = cumulativeContErr;
+    }
+    sc[5] = 4.0*io->e*sigma;
+    {
+        volScalarField fa("fa", mesh), fc("fc", mesh);
+        fa.v.assignHost(io->fa); fa.b.assignHost(io->fab); fc.v.assignHost(io->fc); fc.b.assignHost(io->fcb);
+        const volScalarField* f[2] = {&fa, &fc};
+        for (int k = 0; k < 2; k++) {
+            double* o = sc + 6 + 5*k;
+            o[0] = gMin(*f[k]); o[1] = gMax(*f[k]); o[2] = gAverage(*f[k]); o[3] = min(*f[k]).value(); o[4] = max(*f[k]).value();
+        }
+        sc[16] = fvc::domainIntegrate(fa).value();
+        sc[17] = gSum(fa);
+    }
+    FFM_FOAM_CHK(ffm_ctx_sync(ctx));
+    int n = 0;
+    for (const solverPerformance& sp : mesh.log) { if (n < 6) io->nIter[n] = sp.nIterations; n++; }
+    return n;
+}
+
 // the Function1 entry `key` of patch `patch` in a field file as (x, y) pairs, and the patch's massFluxFraction
 extern "C" int b1_read_function1(const char* path, const char* patch, const char* key, double* xy, int cap, double* massFluxFraction)
 {

@@ -108,6 +108,7 @@ def lib():
         "ffm_ldu_bind_coeffs_native_d": ([vp, dp, dp, dp, C.c_int], C.c_int),
         "ffm_ldu_set_interfaces": ([vp, C.c_int, ip, C.POINTER(ip), C.POINTER(hp), C.POINTER(hp), ip], C.c_int),
         "ffm_ldu_set_global_cells": ([vp, C.c_long], C.c_int),
+        "ffm_ldu_global_cells": ([vp], C.c_long),
         "ffm_spmv": ([vp, dp, dp], C.c_int),
         "ffm_tmul": ([vp, dp, dp], C.c_int),
         "ffm_sumA": ([vp, dp], C.c_int),

@@ -180,6 +180,7 @@ extern "C" int ffm_ldu_get_face_map(const ffm_ldu *A, int *callerToNative)
     return FFM_OK;
 }
 extern "C" int ffm_ldu_set_global_cells(ffm_ldu *A, long g) { if (!A || g < A->nOwned) return FFM_ERR_ARG; A->globalCells = g; return FFM_OK; }
+extern "C" long ffm_ldu_global_cells(const ffm_ldu *A) { return A ? A->globalCells : (long)FFM_ERR_ARG; }
 
 int ffm_ldu_work(ffm_ldu *A, int idx, double **out)
 {

@@ -230,6 +230,8 @@ int ffm_ldu_set_interfaces(ffm_ldu *ldu, int nPatches, const int *patchSizes,
                            const double *const *intCoeffs,
                            const int *neighbRank);
 int ffm_ldu_set_global_cells(ffm_ldu *ldu, long globalCells);
+/* the count set above; the owned cells of this rank until it is set (gAverage divides by it) */
+long ffm_ldu_global_cells(const ffm_ldu *ldu);
 /* Pair tags of the point-to-point messages of one exchange (kind 0: the processor patches of ffm_ldu_set_interfaces, kind 1:
  * the neighbour entries of ffm_ldu_set_ghost_exchange): tags[i] is a label both ranks give to the two entries that exchange
  * with each other.  Messages are posted in ascending tag order, so two ranks that share several patches (cyclic / periodic

@@ -247,6 +247,61 @@ def test_reductions(O, ctx):
     assert ctx.gSum(xd) == ctx.gSum(xd)      # deterministic (no atomics)
 
 
+def test_reduction_edges(O, ctx, ffm):
+    """k_reduce1 / k_reduce2 (csrc/ffm_ctx.hip) behind gSum, gSumProd, gSumMag, gMin, gMax -- every convergence decision, the Courant
+    number and setDeltaT read them -- at the sizes where the launch changes shape: no element, one, around a wavefront, around one
+    block, around the full grid (the grid-stride loop wraps from RED_THREADS*RED_BLOCKS on) and two wraps plus a ragged tail.
+
+    Sums: against math.fsum within n eps sum|x_i y_i|, the a-priori bound of recursive summation in ANY order (Higham, Accuracy and
+    Stability of Numerical Algorithms, eq. 4.4, with eps = 2u also covering the rounding of the products), on data that cancels to
+    sum(x) ~ 1e-6 sum|x|, where a lost or doubled element is far outside the bound; two calls give the same bits.
+    gMin / gMax: exact, with the extreme in the first element, in the last and at the start of the tail beyond the last full block;
+    no element gives the kernel's identity +-DBL_MAX.
+    NaN: the kernels reduce with fmin / fmax, which return the other operand when one is a NaN -- a NaN in the field is IGNORED
+    and the extreme of the remaining values comes back.  This DIFFERS from OpenFOAM, whose min(a, b) is `a < b ? a : b`: every
+    comparison with a NaN is false, so its running minimum becomes the NaN and then restarts from the element after it (gMin
+    there is the minimum of what follows the last NaN, or the NaN itself when it comes last).  The sums propagate the NaN."""
+    import math
+    import os
+    import re
+    import sys
+    src = open(os.path.join(os.path.dirname(ffm.libpath()), "..", "csrc", "ffm_internal.hpp")).read()
+    T = int(re.search(r"constexpr int RED_THREADS = (\d+);", src).group(1)); G = int(re.search(r"constexpr int RED_BLOCKS = (\d+);", src).group(1))
+    eps = np.finfo(np.float64).eps
+    sizes = [0, 1, 63, 64, 65, T - 1, T + 1, T * G - 1, T * G + 1, 2 * T * G + 3]
+    assert sizes[-1] > 2 * T * G and all(n % T for n in sizes[1:])
+    for n in sizes:
+        r = 2 * O.hash_u(31, np.arange(n)) - 1
+        y = 0.5 + O.hash_u(32, np.arange(n))
+        if n >= 64:
+            r = r - r.mean() + 1e-6 * np.abs(r).mean()                     # heavy cancellation
+            assert abs(math.fsum(r)) < 2e-6 * np.abs(r).sum()
+        x = r / y                                                          # ... of the products x*y as well
+        xd, yd = ctx.to_device(r), ctx.to_device(y)
+        x2 = ctx.to_device(x)
+        for got, again, want, scale in ((ctx.gSum(xd), ctx.gSum(xd), math.fsum(r), np.abs(r).sum()),
+                                        (ctx.gSumProd(x2, yd), ctx.gSumProd(x2, yd), math.fsum(x * y), np.abs(x * y).sum()),
+                                        (ctx.gSumMag(xd), ctx.gSumMag(xd), math.fsum(np.abs(r)), np.abs(r).sum())):
+            print("n %d: |sum - fsum| %.3e, bound %.3e" % (n, abs(got - want), n * eps * scale))
+            assert abs(got - want) <= n * eps * scale, n
+            assert got == again, n
+        if n == 0:
+            assert ctx.gMin(xd) == sys.float_info.max and ctx.gMax(xd) == -sys.float_info.max
+            continue
+        for pos in sorted({0, n - 1, n - n % T}):
+            lo, hi = r.copy(), r.copy()
+            lo[pos], hi[pos] = -5.0, 5.0
+            assert ctx.gMin(ctx.to_device(lo)) == -5.0 and ctx.gMax(ctx.to_device(hi)) == 5.0, (n, pos)
+            assert ctx.gMax(ctx.to_device(lo)) == lo.max() and ctx.gMin(ctx.to_device(hi)) == hi.min(), (n, pos)
+    n = T + 1
+    v = 2 * O.hash_u(33, np.arange(n)) - 1
+    for pos in (0, 70, n - 1):
+        w = v.copy(); w[pos] = np.nan
+        wd = ctx.to_device(w)
+        assert ctx.gMin(wd) == np.nanmin(w) and ctx.gMax(wd) == np.nanmax(w), pos
+        assert math.isnan(ctx.gSum(wd))
+
+
 def test_dataflow_sweeps_bit_exact(O, ffm, ctx, monkeypatch):
     """Level-scheduled matrices -- unstructured meshes, GAMG's coarse levels, FFM_SWEEP=levels -- take the dataflow sweeps: ONE
     launch in which every cell waits for the values it needs (csrc/ffm_solve.hip: k_flow_sweep; chunks of 256 cells by ticket,

@@ -1,5 +1,5 @@
 """One rank of a decomposed run of examples/b1_demo.C (the Foam layer of include/ffmFoam.H on a sub-domain with ghost cells),
-all ranks sharing cuda:0 through the host (gloo) transport.   usage: foam_rank.py rank world port nx ny nz partitioner outdir"""
+all ranks sharing cuda:0 through the host (gloo) transport.   usage: foam_rank.py rank world port nx ny nz partitioner outdir [fvdom|physics]"""
 import os
 import sys
 
@@ -27,6 +27,12 @@ if len(sys.argv) > 9 and sys.argv[9] == "fvdom":
     (I, G, qp), cells, its = foam_case.run_b1_fvdom(ffm, ctx, m, T, Tb, E, emis, sub=sub, part=part)
     np.savez(os.path.join(outdir, "rank%d.npz" % rank), cells=cells, I=I, G=G, its=np.array(its), nGhost=sub.nGhost,
              **{"pos_" + k: v[0] for k, v in qp.items()}, **{"qin_" + k: v[1] for k, v in qp.items()})
+    ctx.close()
+    sys.exit(0)
+if len(sys.argv) > 9 and sys.argv[9] == "physics":
+    # the physics handles, patch conditions and reductions on this rank's sub-domain: tests/test_foam_handles_decomposed_gpu.py
+    res = foam_case.run_b1_physics(ffm, ctx, m, foam_case.physics_inputs(O, m), sub=sub, part=part)
+    np.savez(os.path.join(outdir, "rank%d.npz" % rank), nGhost=sub.nGhost, **res)
     ctx.close()
     sys.exit(0)
 res, cells, nit = foam_case.run_b1_demo(ffm, ctx, m, foam_case.inputs(O, m), sub=sub, part=part)
