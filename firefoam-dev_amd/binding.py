@@ -128,6 +128,9 @@ def lib():
         "ffm_ldu_offdiag_epoch": ([vp], C.c_ulong),
         "ffm_ldu_tile_coef_read": ([vp, C.c_int, hp], C.c_int),
         "ffm_ldu_tile_gathers": ([vp], C.c_long),
+        "ffm_ldu_tile_code_bytes": ([vp, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)], C.c_int),
+        "ffm_tile_share_codes": ([C.c_int, C.POINTER(C.c_long), ip, C.POINTER(C.c_ushort), C.c_long, C.c_int, C.c_long, C.POINTER(C.c_uint),
+                                  C.POINTER(C.c_ushort), C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)], C.c_int),
         "ffm_debug_pool_poison": ([vp, C.c_int], C.c_int),
         "ffm_bench_spmv": ([vp, dp, dp, C.c_int, hp], C.c_int),
         "ffm_bench_precond": ([vp, C.c_int, dp, dp, C.c_int, hp], C.c_int),
@@ -700,6 +703,14 @@ class lduMatrix:
     def tile_gathers(self):
         """gather passes this matrix has launched to fill those arrays (ffm_ldu_tile_gathers)"""
         return int(lib().ffm_ldu_tile_gathers(self.h))
+
+    def tile_code_bytes(self, which):
+        """(unique, total) bytes of the tile plan's neighbour codes (ffm_ldu_tile_code_bytes): the blocks the plan keeps and the blocks
+        its entries refer to; which = 0 forward sweep, 1 backward sweep, 2 tiled Amul.  FFM_TILE_CODE_SHARE=0, read when the matrix
+        is made, gives every entry a block of its own (unique == total); 1 / 2 share the sweeps' / the Amul's blocks only"""
+        u, t = C.c_long(), C.c_long()
+        _check(lib().ffm_ldu_tile_code_bytes(self.h, which, C.byref(u), C.byref(t)), "ffm_ldu_tile_code_bytes")
+        return u.value, t.value
 
     @property
     def offdiag_epoch(self):

@@ -86,3 +86,8 @@ struct LduLayout {
 int ffm_ldu_analysis(int nOwn, int nGhost, int F, const int *l, const int *u, const int *groupHint, int forceMode, LduAnalysis &a);
 int ffm_ldu_layout(const LduAnalysis &a, int nOwn, int nGhost, int F, LduLayout &L);
 bool ffm_tile_feasible(int nOwn, int F, const int *l, const int *u);
+
+// ---- content sharing of the tile plans' neighbour-code blocks (ffm_tile_share.cpp) ----
+int ffm_tile_share(std::vector<unsigned short> &codes, const std::vector<long> &start, const std::vector<int> &len, bool share, long padShorts,
+                   std::vector<unsigned short> &pool, std::vector<unsigned> &off, long *uniqueBytes, long *totalBytes, const char *what);
+bool ffm_tile_share_enabled(int reader);      // reader: 1 the sweeps, 2 the tiled Amul (FFM_TILE_CODE_SHARE)

@@ -47,10 +47,14 @@ static_assert(T_PM >= 2 && T_PM < T_PF, "read-ahead distances");
 struct TileDir {            // one sweep direction (device arrays)
     int nEnt = 0, nPub = 0;
     int *grpEnt = nullptr;      // [G+1] entries of each group
-    int4 *rec = nullptr;        // [nEnt + pad] {first cell, cells | externals << 16, first mailbox slot, first extSrc index}
+    int4 *rec = nullptr;        // [nEnt + pad] {first cell, cells | externals << 16, first mailbox slot, byte offset of the entry's code block in `code`}
+    int *extOff = nullptr;      // [nEnt + pad] first extSrc index of every entry (read by the mail wave only)
     int *extSrc = nullptr;      // mailbox slot of every external reference, entry by entry
-    unsigned short *code = nullptr;   // [4*nOwn] per cell: 3 neighbour codes = the LDS slot holding the neighbour's value when the cell is computed
-                                      // (ring slot (nb - group start) mod T_RING, or T_RING + parity(entry)*T_XMAX + external index; T_NONE: no neighbour), publish slot | T_NONE
+    unsigned short *code = nullptr;   // pool of code blocks, one block = the cells of an entry in ascending order, 4 shorts per cell: 3 neighbour codes = the LDS
+                                      // slot holding the neighbour's value when the cell is computed (ring slot (nb - group start) mod T_RING, or T_RING +
+                                      // parity(entry)*T_XMAX + external index; T_NONE: no neighbour), publish slot | T_NONE.  No code depends on the cell's
+                                      // absolute position, so entries with equal blocks share one (ffm_tile_share.cpp; FFM_TILE_CODE_SHARE=0: one block each; 1 / 2: only the sweeps' / the Amul's pool shared)
+    long codeUnique = 0, codeTotal = 0;     // bytes of the pool's blocks / of all entries' blocks (host)
     int *src = nullptr;         // [3*nOwn] native coefficient index of each neighbour slot (-1: none)
     double *coefU = nullptr, *coefL = nullptr;        // [3*nOwn] gathered upper / lower coefficients (lazily allocated)
     unsigned long epochU = ~0ul, epochL = ~0ul;
@@ -69,8 +73,10 @@ struct ffm_tile_plan {
     bool amulUsable = false;
     bool gsTables = false;          // the upper-neighbour and tail tables below exist (Gauss-Seidel sweeps, Amul tail)
     std::vector<int> grpEntHost;    // forward entries of each group (host copy)
-    int4 *arec = nullptr;           // [nEnt + pad] {first cell, cells | externals << 16, first index into aext, 0}
-    uint4 *acode = nullptr;         // [nOwn] 8 x 16 bit: 3 lower codes, 3 upper codes (A_* encoding below), 2 spare
+    int4 *arec = nullptr;           // [nEnt + pad] {first cell, cells | externals << 16, first index into aext, byte offset of the entry's code block in acode}
+    uint4 *acode = nullptr;         // pool of code blocks (shared between equal entries as TileDir::code), per cell 8 x 16 bit: 3 lower codes, 3 upper codes
+                                    // (A_* encoding below), 2 spare
+    long acodeUnique = 0, acodeTotal = 0;
     int2 *aext = nullptr;           // per external reference {cell whose x is needed, native index of the coefficient or -1}
     // owned upper neighbours of every cell: the neighbour cell of slot k (the upper coefficients are the backward direction's)
     int *upNbrCell = nullptr;
@@ -102,7 +108,7 @@ bool ffm_tile_fv_segments(ffm_ldu *A, int runLength, FfmFvSegs *out)
 
 static void free_dir(TileDir &d)
 {
-    hipFree(d.grpEnt); hipFree(d.rec); hipFree(d.extSrc); hipFree(d.code); hipFree(d.src); hipFree(d.coefU); hipFree(d.coefL);
+    hipFree(d.grpEnt); hipFree(d.rec); hipFree(d.extOff); hipFree(d.extSrc); hipFree(d.code); hipFree(d.src); hipFree(d.coefU); hipFree(d.coefL);
     d = TileDir();
 }
 void ffm_tile_free(ffm_ldu *A)
@@ -118,6 +124,21 @@ void ffm_tile_free(ffm_ldu *A)
 bool ffm_tile_usable(const ffm_ldu *A) { return A->tile && A->tile->usable; }
 
 template <class T> static int upv(ffm_ctx *c, T **d, const std::vector<T> &v) { return ffm_upload_vec(c, d, v); }
+
+// The per-cell codes (S shorts per cell) cut into the blocks of the entries `rec` and kept once per distinct content: rec[e].w becomes the
+// byte offset of entry e's block in `pool` (its former value goes to wOut).  The pool ends in one entry's worth of padding, so that a
+// record of the read-ahead padding (offset 0, no cells) and the idle lanes, which read position 0 of their entry, always have a block.
+static int share_blocks(std::vector<unsigned short> &code, std::vector<int4> &rec, int S, const char *what, std::vector<unsigned short> &pool,
+                        long *uniqueBytes, long *totalBytes, std::vector<int> *wOut)
+{
+    std::vector<long> start(rec.size());
+    std::vector<int> len(rec.size());
+    for (size_t e = 0; e < rec.size(); e++) { start[e] = (long)S * rec[e].x; len[e] = S * (rec[e].y & 0xFFFF); }
+    std::vector<unsigned> off;
+    FFM_TRY(ffm_tile_share(code, start, len, ffm_tile_share_enabled(S == 4 ? 1 : 2), (long)S * T_ENT, pool, off, uniqueBytes, totalBytes, what));
+    for (size_t e = 0; e < rec.size(); e++) { if (wOut) (*wOut)[e] = rec[e].w; rec[e].w = (int)off[e]; }
+    return FFM_OK;
+}
 
 // Build one direction.  fwd: neighbours = lower entries (cells with smaller index); bwd: upper slots.  Neighbours that are
 // ghost cells are dropped (block-Jacobi sweeps ignore them); the remaining ones keep their order, which is the order of
@@ -215,11 +236,16 @@ static int build_dir(ffm_ldu *A, bool fwd, const std::vector<int> &lvl, const st
     if (bad == 1) { ffm_set_error("internal: tile plan references an unpublished cell"); return FFM_ERR_ADDR; }
     if (bad) { ffm_set_error("internal: tile plan external count mismatch"); return FFM_ERR_ADDR; }
     D.nEnt = (int)rec.size(); D.nPub = nPub;
+    // the code blocks of the entries go to the pool; the record keeps the block's offset where it kept the first extSrc index
+    std::vector<int> extOff(rec.size());
+    std::vector<unsigned short> pool;
+    FFM_TRY(share_blocks(code, rec, 4, fwd ? "tile: forward code sharing" : "tile: backward code sharing", pool, &D.codeUnique, &D.codeTotal, &extOff));
     if (recOut) *recOut = rec;
     if (grpEntOut) *grpEntOut = grpEnt;
-    for (int k = 0; k < 2 * T_PF + 2; k++) rec.push_back(make_int4(0, 0, 0, 0));      // read-ahead padding
+    for (int k = 0; k < 2 * T_PF + 2; k++) { rec.push_back(make_int4(0, 0, 0, 0)); extOff.push_back(0); }      // read-ahead padding
     for (int k = 0; k < T_THREADS; k++) extSrc.push_back(0);
-    FFM_TRY(upv(A->ctx, &D.grpEnt, grpEnt)); FFM_TRY(upv(A->ctx, &D.rec, rec)); FFM_TRY(upv(A->ctx, &D.extSrc, extSrc)); FFM_TRY(upv(A->ctx, &D.code, code)); FFM_TRY(upv(A->ctx, &D.src, src));
+    FFM_TRY(upv(A->ctx, &D.grpEnt, grpEnt)); FFM_TRY(upv(A->ctx, &D.rec, rec)); FFM_TRY(upv(A->ctx, &D.extOff, extOff)); FFM_TRY(upv(A->ctx, &D.extSrc, extSrc));
+    FFM_TRY(upv(A->ctx, &D.code, pool)); FFM_TRY(upv(A->ctx, &D.src, src));
     return FFM_OK;
 }
 
@@ -227,7 +253,7 @@ static int build_dir(ffm_ldu *A, bool fwd, const std::vector<int> &lvl, const st
 // y = A x for a symmetric matrix on the tile numbering.  One workgroup streams through one group entry by entry (the
 // forward sweep's entries); x and the upper coefficients of the entries [e-3, e+3] live in LDS rings, so a row finds its
 // neighbours' x and, for its lower faces, the owner's coefficient there: every coefficient, x, diag is read from memory
-// once (56 B per cell + 16 B of codes).  Neighbours outside the window or in another group ("externals", tile faces) are
+// once (56 B per cell; the 16 B of codes come from the pool of entry blocks).  Neighbours outside the window or in another group ("externals", tile faces) are
 // fetched by the mail wave from x / the native coefficient array.  Faces towards ghost cells come last in a row's face
 // order and are added afterwards by k_amul_tail, so the sum of every row runs in the reference's face order.
 constexpr int A_RING = 1024;            // cells in the x / coefficient rings (power of two; >= 8 entries of 256)
@@ -313,11 +339,13 @@ static int build_amul(ffm_ldu *A, const std::vector<int> &grpOfCell, const std::
         }
         arec[e] = make_int4(c0, cnt | (t << 16), extOff, 0);
     }
+    std::vector<unsigned short> pool;
+    FFM_TRY(share_blocks(code, arec, 8, "tile: amul code sharing", pool, &T->acodeUnique, &T->acodeTotal, nullptr));
     for (int k = 0; k < 2 * A_PF + 2; k++) arec.push_back(make_int4(0, 0, 0, 0));
     for (int k = 0; k < 2 * A_XMAX; k++) aext.push_back(make_int2(0, -1));
     FFM_TRY(upv(A->ctx, &T->arec, arec)); FFM_TRY(upv(A->ctx, &T->aext, aext));
-    FFM_HIP(hipMalloc((void **)&T->acode, sizeof(unsigned short) * 8 * std::max<size_t>(nOwn, 1)));
-    FFM_TRY(ffm_h2d(A->ctx, T->acode, code.data(), sizeof(unsigned short) * code.size()));
+    FFM_HIP(hipMalloc((void **)&T->acode, sizeof(unsigned short) * pool.size()));
+    FFM_TRY(ffm_h2d(A->ctx, T->acode, pool.data(), sizeof(unsigned short) * pool.size()));
     // segments: enough workgroups to fill the chip, each long enough to amortise the A_WIN entries read twice at either end
     {
         const std::vector<int> &grpEntH = T->grpEntHost;
@@ -364,7 +392,7 @@ int ffm_tile_build(ffm_ldu *A, const std::vector<int> &lev, const std::vector<in
 // ------------------------------------------------------------------ device ---
 struct TileView {
     int G;
-    const int *grpCell, *grpEnt, *extSrc;
+    const int *grpCell, *grpEnt, *extOff, *extSrc;
     const int4 *rec;
     const uint2 *code;
     unsigned int *ticket;      // [0] ticket counter, [1] abort word
@@ -463,9 +491,10 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const doubl
         const unsigned lane = tid - (unsigned)T_THREADS;
         int4 qrec[PF];                  // record of entry e + 2*PF .. (slot = (e - e0) % PF)
         unsigned qne[PF], qxi[PF];      // externals and this lane's mailbox slot of entry e + PF ..
+        unsigned qxo[PF];               // first extSrc index, with the record
         double qxv[PF][NF];             // mailbox values of entry e + T_PM ..
-#define Q_REC(k, e) { qrec[k] = t.rec[min((e), e1)]; }
-#define Q_IDX(k, e) { const int4 R_ = qrec[k]; qne[k] = ((e) < e1) ? ((unsigned)R_.y >> 16) : 0u; qxi[k] = (unsigned)t.extSrc[(unsigned)R_.w + (lane < qne[k] ? lane : 0u)]; }
+#define Q_REC(k, e) { const int e_ = min((e), e1); qrec[k] = t.rec[e_]; qxo[k] = (unsigned)t.extOff[e_]; }
+#define Q_IDX(k, e) { const int4 R_ = qrec[k]; qne[k] = ((e) < e1) ? ((unsigned)R_.y >> 16) : 0u; qxi[k] = (unsigned)t.extSrc[qxo[k] + (lane < qne[k] ? lane : 0u)]; }
 #define Q_MAIL(k) { _Pragma("unroll") for (int i_ = 0; i_ < NF; i_++) qxv[k][i_] = t_ld(&m.mail[i_][lane < qne[k] ? qxi[k] : 0u]); }
 #define Q_PUT(k, e) {                                                                                    \
         if (lane < qne[k]) {                                                                              \
@@ -516,9 +545,10 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile(TileView t, const doubl
 #define T_FETCH(k, e, R_) {                                                                             \
         const unsigned cnt_ = ((e) < e1) ? ((unsigned)R_.y & 0xFFFFu) : 0u;                              \
         const bool ok_ = tid < cnt_;                                                                     \
-        const unsigned cc_ = ok_ ? (ASC ? (unsigned)R_.x + tid : (unsigned)R_.x + cnt_ - 1u - tid) : gs; \
+        const unsigned ps_ = ok_ ? (ASC ? tid : cnt_ - 1u - tid) : 0u;      /* position in the entry's code block; idle lanes: its first cell */ \
+        const unsigned cc_ = ok_ ? (unsigned)R_.x + ps_ : gs;                                            \
         const unsigned o8_ = cc_ * 8u, o24_ = cc_ * 24u;        /* 32-bit byte offsets: arrays < 4 GiB (host check) */  \
-        pq[k] = *(const uint2 *)((const char *)t.code + o8_);                                            \
+        pq[k] = *(const uint2 *)((const char *)t.code + ((unsigned)R_.w + ps_ * 8u));                    \
         { const T3 v_ = *(const T3 *)((const char *)ca + o24_); pa[k][0] = v_.a; pa[k][1] = v_.b; pa[k][2] = v_.c; }     \
         if (TWO) { const T3 v_ = *(const T3 *)((const char *)cb + o24_); pb[k][0] = v_.a; pb[k][TWO ? 1 : 0] = v_.b; pb[k][TWO ? 2 : 0] = v_.c; } \
         _Pragma("unroll") for (int i_ = 0; i_ < NF; i_++) {                                              \
@@ -646,9 +676,10 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_gs(TileView t, double *
         const unsigned lane = tid - (unsigned)T_THREADS;
         int4 qrec[PF];                // record of entry e + 2*PF .. (slot = (e - e0) % PF)
         unsigned qne[PF], qxi[PF];  // externals and this lane's mailbox slot of entry e + PF ..
+        unsigned qxo[PF];           // first extSrc index, with the record
         double qxv[PF];               // mailbox value of entry e + T_PM ..
-#define Q_REC(k, e) { qrec[k] = t.rec[min((e), e1)]; }
-#define Q_IDX(k, e) { const int4 R_ = qrec[k]; qne[k] = ((e) < e1) ? ((unsigned)R_.y >> 16) : 0u; qxi[k] = (unsigned)t.extSrc[(unsigned)R_.w + (lane < qne[k] ? lane : 0u)]; }
+#define Q_REC(k, e) { const int e_ = min((e), e1); qrec[k] = t.rec[e_]; qxo[k] = (unsigned)t.extOff[e_]; }
+#define Q_IDX(k, e) { const int4 R_ = qrec[k]; qne[k] = ((e) < e1) ? ((unsigned)R_.y >> 16) : 0u; qxi[k] = (unsigned)t.extSrc[qxo[k] + (lane < qne[k] ? lane : 0u)]; }
 #define Q_MAIL(k) { qxv[k] = t_ld(&mail[lane < qne[k] ? qxi[k] : 0u]); }
 #define Q_PUT(k, e) {                                                                                    \
         if (lane < qne[k]) {                                                                              \
@@ -694,9 +725,10 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_gs(TileView t, double *
 #define T_FETCH(k, e, R_) {                                                                             \
         const unsigned cnt_ = ((e) < e1) ? ((unsigned)R_.y & 0xFFFFu) : 0u;                              \
         const bool ok_ = tid < cnt_;                                                                     \
-        const unsigned cc_ = ok_ ? (ASC ? (unsigned)R_.x + tid : (unsigned)R_.x + cnt_ - 1u - tid) : gs; \
+        const unsigned ps_ = ok_ ? (ASC ? tid : cnt_ - 1u - tid) : 0u;      /* position in the entry's code block; idle lanes: its first cell */ \
+        const unsigned cc_ = ok_ ? (unsigned)R_.x + ps_ : gs;                                            \
         const unsigned o8_ = cc_ * 8u, o24_ = cc_ * 24u;        /* 32-bit byte offsets: arrays < 4 GiB (host check) */  \
-        pq[k] = *(const uint2 *)((const char *)t.code + o8_);                                            \
+        pq[k] = *(const uint2 *)((const char *)t.code + ((unsigned)R_.w + ps_ * 8u));                    \
         { const T3 v_ = *(const T3 *)((const char *)ca + o24_); pa[k][0] = v_.a; pa[k][1] = v_.b; pa[k][2] = v_.c; }     \
         if (TWO) { const T3 v_ = *(const T3 *)((const char *)cb + o24_); pb[k][0] = v_.a; pb[k][TWO ? 1 : 0] = v_.b; pb[k][TWO ? 2 : 0] = v_.c; } \
         pd[k] = *(const double *)((const char *)dg + o8_);                                               \
@@ -763,7 +795,7 @@ __global__ void k_tile_fill(long n, unsigned long long *p, unsigned long long v,
 
 static TileView tview(const ffm_ldu *A, const TileDir &d)
 {
-    TileView t; t.G = A->tile->G; t.grpCell = A->grpCell; t.grpEnt = d.grpEnt; t.extSrc = d.extSrc; t.rec = d.rec;
+    TileView t; t.G = A->tile->G; t.grpCell = A->grpCell; t.grpEnt = d.grpEnt; t.extOff = d.extOff; t.extSrc = d.extSrc; t.rec = d.rec;
     t.code = (const uint2 *)d.code; t.ticket = A->sweepTicket;
     return t;
 }
@@ -832,6 +864,17 @@ extern "C" int ffm_ldu_tile_coef_read(ffm_ldu *A, int which, double *out_h)
     return ffm_d2h(A->ctx, out_h, p, sizeof(double) * (size_t)T_W * A->nOwned);
 }
 extern "C" long ffm_ldu_tile_gathers(const ffm_ldu *A) { return A ? (long)A->tileGathers : -1; }
+// bytes of neighbour codes the plan keeps (the pool's blocks) and bytes its entries refer to (what per-cell arrays would hold);
+// which: 0 forward sweep, 1 backward sweep, 2 tiled Amul (0 / 0 where the matrix has no ring plan for it)
+extern "C" int ffm_ldu_tile_code_bytes(const ffm_ldu *A, int which, long *uniqueBytes, long *totalBytes)
+{
+    if (!A || !uniqueBytes || !totalBytes || which < 0 || which > 2) return FFM_ERR_ARG;
+    if (!ffm_tile_usable(A)) { ffm_set_error("ffm_ldu_tile_code_bytes: the matrix has no tile plan"); return FFM_ERR_UNSUPPORTED; }
+    const ffm_tile_plan *T = A->tile;
+    *uniqueBytes = which == 0 ? T->f.codeUnique : which == 1 ? T->b.codeUnique : T->acodeUnique;
+    *totalBytes = which == 0 ? T->f.codeTotal : which == 1 ? T->b.codeTotal : T->acodeTotal;
+    return FFM_OK;
+}
 
 static void tile_fill(ffm_ldu *A, double *p, long n)
 {
@@ -1068,7 +1111,7 @@ __global__ __launch_bounds__(T_THREADS + 64) void k_tile_amul(AmulView t, const 
         const bool ok_ = tid < cnt_;                                                                     \
         const unsigned cc_ = ok_ ? (unsigned)(R_).x + tid : gs;                                          \
         const unsigned o8_ = cc_ * 8u;                                                                   \
-        pq[k] = *(const uint4 *)((const char *)t.code + cc_ * 16u);                                      \
+        pq[k] = *(const uint4 *)((const char *)t.code + ((unsigned)(R_).w + (ok_ ? tid : 0u) * 16u));     /* the entry's code block; idle lanes: its first cell */ \
         { const T3 v_ = *(const T3 *)((const char *)bc + cc_ * 24u); pb[k][0] = v_.a; pb[k][1] = v_.b; pb[k][2] = v_.c; } \
         pd[k] = *(const double *)((const char *)diag + o8_);                                             \
         px[k] = *(const double *)((const char *)x + o8_);                                                \

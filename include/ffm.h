@@ -206,6 +206,19 @@ unsigned long ffm_ldu_offdiag_epoch(const ffm_ldu *ldu);
  * the matrix has launched to fill them (the *_direct assembly entry points below fill them without one)                        */
 int ffm_ldu_tile_coef_read(ffm_ldu *ldu, int which, double *out_h);
 long ffm_ldu_tile_gathers(const ffm_ldu *ldu);
+/* The neighbour codes of the tile plan (16-bit LDS slots and cell distances, per cell and entry) are kept once per distinct entry
+ * block: entries whose blocks are equal byte for byte share one.  which: 0 forward sweep, 1 backward sweep, 2 tiled Amul;
+ * *uniqueBytes: the blocks the plan keeps, *totalBytes: the blocks its entries refer to (what one array per cell would hold).
+ * FFM_TILE_CODE_SHARE=0 in the environment when the matrix is created gives every entry a block of its own (unique == total);
+ * 1 shares the sweeps' blocks only, 2 the tiled Amul's only (A/B runs of one reader), unset or 3 both.
+ * FFM_ERR_UNSUPPORTED without a tile plan.                                                                                      */
+int ffm_ldu_tile_code_bytes(const ffm_ldu *ldu, int which, long *uniqueBytes, long *totalBytes);
+/* test support: the sharing itself on host arrays (no device).  Block i = codes[start[i], start[i] + len[i]) in shorts.  share != 0:
+ * pool_out receives every distinct block once, in the order of first appearance; share == 0: pool_out is a copy of codes.  Then
+ * padShorts shorts of 0xFFFF.  offset_out[i]: byte offset of block i in pool_out (0 for an empty block); *uniqueShorts: shorts of
+ * the pool's blocks; *poolShorts: shorts written, padding included; FFM_ERR_ARG if poolCapacity (shorts) is too small.         */
+int ffm_tile_share_codes(int nBlocks, const long *start, const int *len, const unsigned short *codes, long nCodes, int share, long padShorts,
+                         unsigned int *offset_out, unsigned short *pool_out, long poolCapacity, long *uniqueShorts, long *poolShorts);
 
 /* processor patches (lduInterface / interfaceBouCoeffs / interfaceIntCoeffs):
  * face i of patch p couples cell faceCells[p][i] (caller numbering) with face i
