@@ -871,6 +871,121 @@ extern "C" int b1_p1(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, double a, double
     return nSolves;
 }
 
+// ---- greyMeanAbsorptionEmissionCoeffs of a radiationProperties file as include/ffmDictionary.H reads it (no GPU): out = EhrrCoeff, then
+// per sub-dictionary in FILE order Tcommon, invTemp, Tlow, Thigh, loTcoeffs[6], hiTcoeffs[6]; names = the sub-dictionaries' keywords and,
+// last, the lookUpTableFileName token (`none` where absent), blank-separated.  Returns the number of species, or a negative number.
+extern "C" int b1_read_greymean(const char* path, double* out, int cap, char* names, int namesCap)
+{
+    const dictionaryFile f(path);
+    const dictionaryFile::node& co = f.top.subDict("greyMeanAbsorptionEmissionCoeffs");
+    std::string nm; int n = 0, o = 0;
+    if (cap < 1) return -1;
+    out[o++] = co.number("EhrrCoeff", -1);
+    for (const word& key : co.toc()) {
+        const dictionaryFile::entry* e = co.find(key);
+        if (!e || !e->sub) continue;
+        if (o + 16 > cap) return -1;
+        const dictionaryFile::node& d = *e->sub;
+        out[o++] = d.number("Tcommon", -1); out[o++] = d.number("invTemp", -1); out[o++] = d.number("Tlow", -1); out[o++] = d.number("Thigh", -1);
+        const std::vector<scalar> lo = d.numberList("loTcoeffs"), hi = d.numberList("hiTcoeffs");
+        if (lo.size() != 6 || hi.size() != 6) return -2;
+        for (scalar x : lo) out[o++] = x;
+        for (scalar x : hi) out[o++] = x;
+        nm += key + " "; n++;
+    }
+    nm += co.token("lookUpTableFileName", "none");
+    std::strncpy(names, nm.c_str(), namesCap - 1); names[namesCap - 1] = 0;
+    return n;
+}
+
+// what the class layer's greyMeanAbsorptionEmission says to this file's lookUpTableFileName (override "" = as the file has it): the
+// FatalError message it would stop with, or nothing where it accepts the file.  Returns the message's length (no GPU, nothing is built).
+extern "C" int b1_greymean_table_refusal(const char* path, const char* lookUpTableOverride, char* msg, int cap)
+{
+    const dictionaryFile f(path);
+    const word r = greyMeanAbsorptionEmission::lookUpTableRefusal(f.top.subDict("greyMeanAbsorptionEmissionCoeffs"), lookUpTableOverride);
+    std::strncpy(msg, r.c_str(), cap - 1); msg[cap - 1] = 0;
+    return (int)r.size();
+}
+
+// ---- the greyMeanAbsorptionEmission handle (include/fireFoamHandles.H) on any mesh, alone and as the absorptionEmissionModel of fvDOM or
+// P1: the model is built from the dictionary file dictPath (its greyMeanAbsorptionEmissionCoeffs; lookUpTableOverride "" = as the file
+// says), the blank-separated species list with W, and host fields Y [nSpecies][N], p, T (cells), Tb (boundary faces), Qdot.
+//   aOut [N + B]: aCont() cells, then patch values; EOut [N]: ECont(); flagOut: whether a T left a species' range.
+//   model 1: fvDOM (nPhi, nTheta, ordered ray solves, maxIter 1, emissivity_b), model 2: P1 (sigma_s = C = 0, G by PCG + DIC to GTol), model 0:
+//   neither.  hooks 1: the model's aCont / eCont / ECont are the handle's absorption / emission providers; hooks 2: providers that return
+//   the UNIFORM fields aConst, eConst and E = Qdot; hooks 0: unset -- the constants aConst, eConst, and E = Qdot (fvDOM: RadFraction 1; P1:
+//   its emission provider, as b1_p1).  nCalls calls of correct(), then Sh(thermo, he) with Cpv = the field Cp.
+//   IOut [nRay][N] (fvDOM), GOut [N], GbOut / qrOut [B] (P1: G_b, qr; fvDOM: qin, qr), iters [nCalls] (P1: PCG iterations; fvDOM: iterations
+//   of calculate), shOut [2 N]: diag and source[0] of the matrix Sh returns.  Returns nRay (fvDOM), the number of solves (P1) or 0.
+// tests/test_greymean_foam_gpu.py.
+extern "C" int b1_greymean(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, const char* dictPath, const char* lookUpTableOverride, const char* speciesNames,
+                           const double* W, const double* const* Y, const double* p, const double* T, const double* Tb, const double* Qdot, const double* he,
+                           const double* Cp, const double* emissivity, int model, int hooks, double aConst, double eConst, int nPhi, int nTheta, int nCalls,
+                           double GTol, double* aOut, double* EOut, int* flagOut, double* IOut, double* GOut, double* GbOut, double* qrOut, int* iters,
+                           double* shOut)
+{
+    const double sigma = 5.670367e-8;
+    fvMesh mesh(ctx, ldu, msh, 1.0);
+    mesh.divSchemes["div(Ji,Ii_h)"] = {0, 1, 0, 1};
+    mesh.solvers["G"] = mesh.solvers["GFinal"] = {FFM_PCG, FFM_DIC, GTol, 0, 0, 1000, 1};
+    const label N = mesh.nCells, B = mesh.nBoundary;
+    std::vector<word> species; { std::istringstream is(speciesNames); word w; while (is >> w) species.push_back(w); }
+    const std::vector<scalar> Wv(W, W + species.size());
+    PtrList<volScalarField> Yf;
+    for (size_t i = 0; i < species.size(); i++) { Yf.append(new volScalarField(species[i], mesh)); Yf[(label)i].v.assignHost(Y[i]); }
+    volScalarField pf("p", mesh), Tf("T", mesh), Qf("Qdot", mesh), hf("h", mesh), Cpf("Cp", mesh);
+    pf.v.assignHost(p); Tf.v.assignHost(T); Tf.b.assignHost(Tb); Qf.v.assignHost(Qdot); hf.v.assignHost(he); Cpf.v.assignHost(Cp);
+    surfaceScalarField phi(mesh);
+    mesh.store("phi", phi); mesh.store("Qdot", Qf);
+    const dictionaryFile dict(dictPath);
+    greyMeanAbsorptionEmission ae(mesh, species, Wv, Yf, pf, Tf, dict.top.subDict("greyMeanAbsorptionEmissionCoeffs"), lookUpTableOverride);
+    {
+        const volScalarField a(ae.aCont()), E(ae.ECont());
+        a.v.toHost(aOut); a.b.toHost(aOut + N); E.v.toHost(EOut);
+        *flagOut = ae.temperatureOutOfRange() ? 1 : 0;
+    }
+    perfectGasConstCpThermo thermo(mesh, 8314.47, 1005.0, 298.15);
+    auto aFn = [&]() { return hooks == 1 ? ae.aCont() : uniformField("a", mesh, aConst); };
+    auto eFn = [&]() { return hooks == 1 ? ae.eCont() : uniformField("e", mesh, eConst); };
+    auto EFn = [&]() { return hooks == 1 ? ae.ECont() : Qf; };
+    auto shOf = [&](const fvScalarMatrix& Mc) {
+        fvScalarMatrix M(Mc); M.ensure();
+        M.diag.toHost(shOut); M.source[0].toHost(shOut + N);
+    };
+    int ret = 0;
+    if (model == 1) {
+        std::vector<double> zeroB(B, 0.0);
+        fvDOM dom(mesh, Tf, nPhi, nTheta, 1, aConst, sigma, 1.0, 1.0, zeroB.data());
+        dom.setIteration(1, 0.0);
+        dom.setOrderedSolves(true);
+        dom.emissivity().assignHost(emissivity);
+        dom.Cpv = [&]() { return Cpf; };
+        if (hooks) { dom.absorption = aFn; dom.emission = EFn; }
+        for (int c = 0; c < nCalls; c++) { dom.correct(); iters[c] = dom.lastIterations_; }
+        for (label i = 0; i < dom.nRay(); i++) dom.I_[i].v.toHost(IOut + (size_t)i*N);
+        dom.G_.v.toHost(GOut); dom.qin_.toHost(GbOut); dom.qr_.toHost(qrOut);
+        shOf(dom.Sh(thermo, hf));
+        ret = dom.nRay();
+    } else if (model == 2) {
+        P1 p1(mesh, Tf, 1, aConst, eConst, 0.0, 0.0, 0.0, sigma);
+        p1.emissivity().assignHost(emissivity);
+        p1.Cpv = [&]() { return Cpf; };
+        p1.emission = EFn;
+        if (hooks) { p1.absorption = aFn; p1.eCont = eFn; }
+        for (int c = 0; c < nCalls; c++) {
+            mesh.log.clear();
+            p1.correct();
+            iters[c] = mesh.log.empty() ? -1 : mesh.log.back().nIterations;
+            ret += (int)mesh.log.size();
+        }
+        p1.G_.v.toHost(GOut); p1.G_.b.toHost(GbOut); p1.qr_.toHost(qrOut);
+        shOf(p1.Sh(thermo, hf));
+    }
+    FFM_FOAM_CHK(ffm_ctx_sync(ctx));
+    return ret;
+}
+
 // ---- Time::setDeltaT / operator++ of include/ffmFoam.H (Time::adjustDeltaT with writeControl adjustableRunTime) stepped n times with the
 // wished deltaT of every step: the adjusted deltaT, the time and the write index after every step (tests/test_abi_cpu.py)
 extern "C" int b1_time_sequence(double deltaT0, double writeInterval, int n, const double* wish, double* dtOut, double* tOut, int* writeIndexOut)

@@ -9,7 +9,7 @@ fallback: every compute entry point needs libffm.so and a GPU.
 """
 from .binding import (  # noqa: F401
     Context, lduMatrix, FfmError, lib, build, libpath, SOLVERS, PRECONDS, tile_hint_from_centres,
-    renumber_levels, check_layout, exported_symbols, declared_symbols, Plume, fvMesh, PyrolysisPanel, GAMG, Thermo, ray_schedule, ray_octant, flow_levels, flow_stages, FlowOrder,
+    renumber_levels, check_layout, exported_symbols, declared_symbols, Plume, fvMesh, PyrolysisPanel, GAMG, Thermo, GreyMean, ray_schedule, ray_octant, flow_levels, flow_stages, FlowOrder,
 )
 from . import hexmesh  # noqa: F401
 from . import decompose  # noqa: F401

@@ -177,6 +177,13 @@ def lib():
         "ffm_thermo_step_d": ([vp, C.c_long, C.POINTER(vp), dp, dp, dp, dp, dp, dp, dp], C.c_int),
         "ffm_thermo_species": ([vp, C.POINTER(C.c_int), hp], C.c_int),
         "ffm_thermo_destroy": ([vp], C.c_int),
+        "ffm_greymean_create": ([vp, C.c_int, hp, C.c_int, ip, ip] + [hp] * 5 + [C.c_double, C.POINTER(vp)], C.c_int),
+        "ffm_greymean_destroy": ([vp], C.c_int),
+        "ffm_greymean_a_d": ([vp, C.c_long, C.POINTER(vp), dp, dp, dp, dp], C.c_int),
+        "ffm_greymean_E_d": ([vp, C.c_long, dp, dp], C.c_int),
+        "ffm_radiation_sh_greymean_d": ([vp, C.c_long, C.POINTER(vp), dp, dp, C.c_double, dp, dp, dp, dp, C.c_double, dp, dp, dp, dp], C.c_int),
+        "ffm_fvdom_ray_assemble_v_d": ([vp, hp, C.c_double, dp, C.c_double] + [dp] * 9, C.c_int),
+        "ffm_radiation_sh_v_d": ([vp, C.c_long, dp, dp, C.c_double] + [dp] * 5 + [C.c_double, dp, dp], C.c_int),
         "ffm_edc_correct_d": ([vp, C.c_long] + [dp] * 6 + [C.c_double] * 7 + [dp, dp], C.c_int),
         "ffm_les_keqn_nut_d": ([vp, C.c_long, C.c_double, C.c_double, dp, dp, dp, dp, dp], C.c_int),
         "ffm_gamg_face_area_pair_weights": ([C.c_int, hp, hp], C.c_int),
@@ -291,6 +298,7 @@ def lib():
         "ffm_plume_set_radiation_ordering": ([vp, C.c_int], C.c_int),
         "ffm_plume_set_radiation_thermo": ([vp, C.c_int], C.c_int),
         "ffm_plume_set_radiation_p1": ([vp, C.c_int] + [C.c_double] * 4, C.c_int),
+        "ffm_plume_set_absorption_emission": ([vp, vp], C.c_int),
         "ffm_plume_ray_system": ([vp, C.c_int, C.c_int, hp, hp, hp, hp], C.c_int),
         "ffm_ray_schedule": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, hp, ip, C.c_int], C.c_int),
         "ffm_ray_octant": ([hp], C.c_int),
@@ -990,6 +998,14 @@ class Plume:
         _check(lib().ffm_plume_set_radiation_p1(self.h, int(solverFreq), float(absorption), float(Ehrr1), float(Ehrr2), float(wallEmissivity)),
                "ffm_plume_set_radiation_p1")
 
+    def set_absorption_emission(self, model):
+        """greyMeanAbsorptionEmission (a GreyMean over the plume's five species, borrowed: keep it open) as the step's absorption /
+        emission model, or None for the constant (ffm_plume_set_absorption_emission).  Needs set_radiation + set_radiation_model or
+        set_radiation_p1 first; refused (FfmError) on a block of a decomposed box and for other molecular weights than the selected
+        thermo package's.  Fields aRad, ShSu, ShSp become readable"""
+        _check(lib().ffm_plume_set_absorption_emission(self.h, None if model is None else model.h), "ffm_plume_set_absorption_emission")
+        self._absem = model
+
     def ray_system(self, ray, fused):
         """(diag, upper, lower, source) of one ray's system by the operator chain or by the one-pass kernel (ffm_plume_ray_system; tests)"""
         d, s_ = np.empty(self.nCells), np.empty(self.nCells)
@@ -1103,6 +1119,58 @@ class Thermo:
     def close(self):
         if getattr(self, "h", None):
             lib().ffm_thermo_destroy(self.h)
+            self.h = None
+
+
+class GreyMean:
+    """greyMeanAbsorptionEmission of the gas phase on the device (ffm_greymean_*).  species: all species of the mixture in the order of
+    the Y lists, W: {specie: molecular weight}; coeffs: {specie: dict(Tcommon, invTemp, Tlow, Thigh, loTcoeffs[6], hiTcoeffs[6])} of the
+    participating species, summed in the order `order` (default: the dict's own, i.e. the file order of a case's sub-dictionaries)"""
+
+    def __init__(self, ctx, species, W, coeffs, EhrrCoeff, order=None):
+        self.ctx, self.n = ctx, len(species)
+        part = list(coeffs) if order is None else list(order)
+        col = lambda k: np.ascontiguousarray([float(coeffs[s][k]) for s in part], np.float64)
+        icol = lambda v: np.ascontiguousarray(v, np.int32)
+        idx, inv = icol([species.index(s) for s in part]), icol([1 if coeffs[s]["invTemp"] else 0 for s in part])
+        lo = np.ascontiguousarray([np.asarray(coeffs[s]["loTcoeffs"], float) for s in part]).reshape(-1)
+        hi = np.ascontiguousarray([np.asarray(coeffs[s]["hiTcoeffs"], float) for s in part]).reshape(-1)
+        if lo.size != 6 * len(part) or hi.size != 6 * len(part):
+            raise FfmError("GreyMean: loTcoeffs / hiTcoeffs hold six numbers per specie")
+        Wa = np.ascontiguousarray([float(W[s]) for s in species], np.float64)
+        ipp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        h = C.c_void_p()
+        _check(lib().ffm_greymean_create(ctx.h, self.n, _hp(Wa), len(part), ipp(idx), ipp(inv), _hp(col("Tcommon")), _hp(col("Tlow")),
+                                         _hp(col("Thigh")), _hp(lo), _hp(hi), float(EhrrCoeff), C.byref(h)), "ffm_greymean_create")
+        self.h = h
+
+    def _Y(self, Y):
+        self._keep = Y
+        return (C.c_void_p * self.n)(*[y.data_ptr() for y in Y])
+
+    def a(self, Y, p, T, out, flag=None):
+        """out = aCont(); flag: a torch int32 tensor of one entry, raised where T leaves a participating species' [Tlow, Thigh]"""
+        self.ctx._ready()
+        P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(lib().ffm_greymean_a_d(self.h, T.numel(), self._Y(Y), P(p), P(T), P(out), P(flag)), "ffm_greymean_a_d")
+        self.ctx.sync()
+
+    def E(self, Qdot, out):
+        self.ctx._ready()
+        _check(lib().ffm_greymean_E_d(self.h, Qdot.numel(), C.c_void_p(Qdot.data_ptr()), C.c_void_p(out.data_ptr())), "ffm_greymean_E_d")
+        self.ctx.sync()
+
+    def sh(self, Y, p, T, sigma, G, he, Qdot, Cp, CpConst, su, sp, a_out=None, flag=None):
+        """radiation->Sh with this model in one pass (ffm_radiation_sh_greymean_d): su, sp and, where given, a_out"""
+        self.ctx._ready()
+        P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(lib().ffm_radiation_sh_greymean_d(self.h, T.numel(), self._Y(Y), P(p), P(T), float(sigma), P(G), P(he), P(Qdot), P(Cp), float(CpConst),
+                                                 P(a_out), P(su), P(sp), P(flag)), "ffm_radiation_sh_greymean_d")
+        self.ctx.sync()
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ffm_greymean_destroy(self.h)
             self.h = None
 
 

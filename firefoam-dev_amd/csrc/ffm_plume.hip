@@ -276,6 +276,7 @@ extern "C" int ffm_plume_destroy(ffm_plume *P)
     for (int a = 0; a < 3; a++) { hipFree(P->radCm[a]); hipFree(P->radFm[a]); }
     hipFree(P->radHaloCells);
     hipFree(P->thermoFail); if (P->thermoFailH) hipHostFree(P->thermoFailH);
+    hipFree(P->gmFlag); if (P->gmFlagH) hipHostFree(P->gmFlagH);
     ffm_mesh_destroy(P->mesh); ffm_ldu_destroy(P->A);
     delete P;
     return FFM_OK;
@@ -526,7 +527,7 @@ extern "C" int ffm_plume_get_field(ffm_plume *P, const char *name, double *out)
     else if (n == "mu") src = P->mu; else if (n == "alpha") src = P->alpha; else if (n == "Cp") src = P->Cp;      // (null while the stand-in thermo is on)
     else if (n == "wFuel") src = P->wFuelOwn; else if (n == "Qdot") src = P->QdotOwn;      // (null while both are scratch slots: no model of theirs on)
     else if (n == "k") src = P->kSgs; else if (n == "nut") src = P->nut; else if (n == "alphat") src = P->alphat;      // (null while the model is off)
-    else if (n == "G") src = P->radG(); else if (n == "ShSu") src = P->radHaveSh ? P->radShSu : nullptr; else if (n == "ShSp") src = P->radHaveSh ? P->radShSp : nullptr; else if (n == "radE") src = P->radE;      // (ShSu, ShSp: null before the first radiation->Sh pass)
+    else if (n == "G") src = P->radG(); else if (n == "ShSu") src = P->radHaveSh ? P->radShSu : nullptr; else if (n == "ShSp") src = P->radHaveSh ? P->radShSp : nullptr; else if (n == "radE") src = P->radE; else if (n == "aRad") src = (P->gm && P->gmHaveA) ? P->aRad : nullptr;      // (ShSu, ShSp: null before the first radiation->Sh pass)
     else if (n.size() > 1 && n[0] == 'I' && isdigit((unsigned char)n[1])) { const int i = atoi(n.c_str() + 1); if (i < (int)P->I.size()) src = P->I[i]; }
     else for (int i = 0; i < NSP; i++) if (n == SPN[i]) src = P->Y[i];
     if (!src) { ffm_set_error("unknown field %s", name); return FFM_ERR_ARG; }

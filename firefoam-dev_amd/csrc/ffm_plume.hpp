@@ -117,6 +117,11 @@ struct ffm_plume {
     // coefficient, emission E = RadFraction*Qdot with the radScaling of constRadFractionEmission::ECont
     bool radCoupled = false; double radA = 0.1, Ehrr1 = 0.0, Ehrr2 = 0.0;
     double *radE = nullptr, *radShSu = nullptr, *radShSp = nullptr; bool radHaveG = false;
+    // greyMeanAbsorptionEmission in place of the constant a and of RadFraction*Qdot (ffm_plume_set_absorption_emission): the borrowed
+    // handle, a of the cells (current at every radiation->correct() and every radiation->Sh) and its zero-gradient patch copy (P1), the
+    // temperature-range flag on the device and its pinned host copy
+    ffm_greymean *gm = nullptr; double *aRad = nullptr, *aRadB = nullptr; bool gmHaveA = false;
+    int *gmFlag = nullptr, *gmFlagH = nullptr;
     bool radHaveSh = false;                // radShSu / radShSp hold a source pass ("ShSu", "ShSp" are readable)
     // fvDOM::updateG as one pass (ffm_fvdom_G_d): the rays' pointers and solid angles on the device, for radTabRays rays
     double **radIdd = nullptr, *radOmegaD = nullptr; int radTabRays = 0;
@@ -222,6 +227,17 @@ static inline int thermo_flag_check(ffm_plume *P)
     hipMemsetAsync(P->thermoFail, 0, sizeof(int), P->ctx->stream);
     ffm_set_error("thermo::T: maximum number of iterations exceeded");
     return FFM_ERR_ARG;
+}
+// the same for greyMeanAbsorptionEmission's temperature-range flag: the reference only warns (absorptionCoeffs::checkT), so does this
+static inline void absem_flag_fetch(ffm_plume *P)
+{ if (P->gm) hipMemcpyAsync(P->gmFlagH, P->gmFlag, sizeof(int), hipMemcpyDeviceToHost, P->ctx->stream); }
+static inline void absem_flag_check(ffm_plume *P)
+{
+    if (!P->gm || !*P->gmFlagH) return;
+    *P->gmFlagH = 0;
+    hipMemsetAsync(P->gmFlag, 0, sizeof(int), P->ctx->stream);
+    ffm_set_error("greyMeanAbsorptionEmission: a temperature left a participating species' [Tlow, Thigh] in step %d", P->stepNo);
+    fprintf(stderr, "--> ffm WARNING: %s\n", ffm_last_error());
 }
 static inline void mul(ffm_plume *P, double *o, const double *a, const double *b, long n) { forN(P, n, [=] __device__(long i) { o[i] = a[i] * b[i]; }); }
 

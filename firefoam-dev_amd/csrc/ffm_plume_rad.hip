@@ -1,5 +1,6 @@
 // ffm_plume_rad.hip -- the radiation models of the plume case: the fvDOM stand-in (the rays' set-up), P1, radiation->correct() and the radiation setters.
 #include "ffm_plume.hpp"
+#include "ffm_greymean.hpp"
 
 // ---- fvDOM stand-in: radiation->correct() of solver/YEEqn.H:80 -------------------------------------------------------
 // per ray i (direction dAve_i, solid angle omega_i; fvDOM.C:55-90, radiativeIntensityRay.C:126-143):
@@ -30,6 +31,7 @@ static int ray_assemble_ops(ffm_plume *P, int i, const double *Ee)
     const double *bx = ffm_mesh_geom(m, 6), *by = ffm_mesh_geom(m, 7), *bz = ffm_mesh_geom(m, 8);
     double *J = P->radJ, *w = P->radW, *Jb = P->radJb, *f = P->radF, *ref = P->radRef, *su = P->radSrc;
     const double *T = P->T; const double KA = P->radA;
+    const double *aF = P->gm ? P->aRad : nullptr;                 // greyMeanAbsorptionEmission: a[c]*omega and a[c]*sigma per cell
     const double d0 = P->rayD[3 * i], d1 = P->rayD[3 * i + 1], d2 = P->rayD[3 * i + 2], omega = P->rayOmega[i];
     forN(P, nNat, [=] __device__(long e) { const double j = (d0 * sx[e] + d1 * sy[e]) + d2 * sz[e]; J[e] = j; w[e] = j >= 0 ? 1.0 : 0.0; });
     forN(P, B, [=] __device__(long k) { const double j = (d0 * bx[k] + d1 * by[k]) + d2 * bz[k]; Jb[k] = j; f[k] = 1.0 - (j >= 0 ? 1.0 : 0.0); });
@@ -37,10 +39,11 @@ static int ray_assemble_ops(ffm_plume *P, int i, const double *Ee)
     FFM_TRY(ffm_fvm_boundary_coeffs(m, Jb, nullptr, -1, f, ref, P->zeroB, P->ic[0], P->bc[0]));
     double *dg = P->diag; const double kO = KA * omega, cS = 1.0 / M_PI * omega, kS = KA * SIGMA_SB;
     forN(P, N, [=] __device__(long c) {
-        dg[c] = dg[c] + V[c] * kO;
+        const double kOc = aF ? aF[c] * omega : kO, kSc = aF ? aF[c] * SIGMA_SB : kS;
+        dg[c] = dg[c] + V[c] * kOc;
         const double t = T[c];
         // 1/pi*omega*(k sigma T^4 [+ E/4]) (radiativeIntensityRay.C:286-300)
-        su[c] = Ee ? V[c] * (cS * (kS * ((t * t) * (t * t)) + Ee[c] / 4.0)) : V[c] * (cS * (kS * ((t * t) * (t * t))));
+        su[c] = Ee ? V[c] * (cS * (kSc * ((t * t) * (t * t)) + Ee[c] / 4.0)) : V[c] * (cS * (kSc * ((t * t) * (t * t))));
     });
     return ffm_fvm_add_boundary(m, P->ic[0], P->bc[0], P->diag, su, nullptr, P->dWork, P->sWork);
 }
@@ -121,6 +124,16 @@ static int radiation_correct_staged(ffm_plume *P, const double *Ee)
     return rad_update_G(P);
 }
 
+// greyMeanAbsorptionEmission at a radiation->correct(): a of the cells once (ffm_greymean_a_d) and E = EhrrCoeff*Qdot; the RadFraction
+// reduction over the burner patch and its host read-back drop out in this mode
+static int absem_correct(ffm_plume *P)
+{
+    FFM_TRY(ffm_greymean_a_d(P->gm, P->N, P->Y, P->p, P->T, P->aRad, P->gmFlag));
+    FFM_TRY(ffm_greymean_E_d(P->gm, P->N, P->Qdot, P->radE));
+    P->gmHaveA = true;
+    return FFM_OK;
+}
+
 // ---- P1 in place of the rays (ffm_plume_set_radiation_p1): P1::calculate() of P1.C:213-258 -------------------------------------
 // gamma = 1/(3 a + a0) (no scattering), fvm::laplacian(gamma, G) - fvm::Sp(a, G) == -4 a sigma T^4 - E with E = RadFraction*Qdot,
 // MarshakRadiation with the one wall emissivity on every patch at the zero-gradient patch values of T, PCG + DIC at the `G` entry's
@@ -129,27 +142,35 @@ static int radiation_correct_staged(ffm_plume *P, const double *Ee)
 static int p1_correct(ffm_plume *P)
 {
     ffm_mesh *m = P->mesh; const int N = P->N;
-    double frac = 0.0;
-    FFM_TRY(plume_rad_fraction(P, &frac));
     double *E = P->radE; const double *Qd = P->Qdot;
-    forN(P, N, [=] __device__(long c) { E[c] = frac * Qd[c]; });
+    const double *aF = nullptr, *aB = nullptr;                    // greyMeanAbsorptionEmission: a = e as a cell field, its patch values the adjacent cells'
+    if (P->gm) {
+        FFM_TRY(absem_correct(P));
+        aF = P->aRad; aB = P->aRadB;
+        zg(P, P->aRadB, P->aRad);
+    } else {
+        double frac = 0.0;
+        FFM_TRY(plume_rad_fraction(P, &frac));
+        forN(P, N, [=] __device__(long c) { E[c] = frac * Qd[c]; });
+    }
     zg(P, P->p1Tb, P->T);
     const double a = P->radA;
     if (P->fused) {
-        FFM_TRY(ffm_p1_assemble_d(m, 0.0, SIGMA_SB, nullptr, a, nullptr, nullptr, a, E, P->T, P->p1Tb, P->p1EmisB, P->upper, P->dWork, P->sWork,
+        FFM_TRY(ffm_p1_assemble_d(m, 0.0, SIGMA_SB, aF, a, aB, aF, a, E, P->T, P->p1Tb, P->p1EmisB, P->upper, P->dWork, P->sWork,
                                   P->p1GammaB, P->p1F, P->p1Ref));
     } else {
-        FFM_TRY(ffm_p1_gamma_d(P->ctx, N, nullptr, a, 0.0, P->p1GammaC));
-        FFM_TRY(ffm_p1_gamma_d(P->ctx, P->B, nullptr, a, 0.0, P->p1GammaB));
+        FFM_TRY(ffm_p1_gamma_d(P->ctx, N, aF, a, 0.0, P->p1GammaC));
+        FFM_TRY(ffm_p1_gamma_d(P->ctx, P->B, aB, a, 0.0, P->p1GammaB));
         FFM_TRY(ffm_fvc_interpolate(m, nullptr, P->p1GammaC, P->p1GammaF));
         FFM_TRY(ffm_fvm_transport(m, 0.0, nullptr, nullptr, nullptr, P->p1GammaF, +1, P->diag, P->upper, nullptr));
         FFM_TRY(ffm_p1_marshak_coeffs_d(m, SIGMA_SB, P->p1GammaB, P->p1Tb, P->p1EmisB, P->p1F, P->p1Ref));
         FFM_TRY(ffm_fvm_boundary_coeffs(m, nullptr, P->p1GammaB, +1, P->p1F, P->p1Ref, P->zeroB, P->ic[0], P->bc[0]));
         const double *V = ffm_mesh_geom(m, 0), *T = P->T; double *dg = P->diag, *su = P->p1Su;
         forN(P, N, [=] __device__(long c) {
-            dg[c] = dg[c] - V[c] * a;
+            const double ac = aF ? aF[c] : a;
+            dg[c] = dg[c] - V[c] * ac;
             const double t = T[c];
-            su[c] = 0.0 + V[c] * ((-(4.0 * ((a * SIGMA_SB) * ((t * t) * (t * t))))) - E[c]);
+            su[c] = 0.0 + V[c] * ((-(4.0 * ((ac * SIGMA_SB) * ((t * t) * (t * t))))) - E[c]);
         });
         FFM_TRY(ffm_fvm_add_boundary(m, P->ic[0], P->bc[0], P->diag, su, nullptr, P->dWork, P->sWork));
     }
@@ -204,7 +225,8 @@ int radiation_correct(ffm_plume *P)
     if (!onePass && !P->radStaged) forN(P, N, [=] __device__(long c) { G[c] = 0.0; });
     forN(P, B, [=] __device__(long k) { ref[k] = Ib; });
     const double *Ee = nullptr;
-    if (P->radCoupled) {      // absorptionEmission->ECont(): E = RadFraction*Qdot (constRadFractionEmission.C, radScaling)
+    if (P->gm) { FFM_TRY(absem_correct(P)); Ee = P->radE; }
+    else if (P->radCoupled) {      // absorptionEmission->ECont(): E = RadFraction*Qdot (constRadFractionEmission.C, radScaling)
         double frac = 0.0;
         FFM_TRY(plume_rad_fraction(P, &frac));
         double *E = P->radE; const double *Qd = P->Qdot;
@@ -215,8 +237,10 @@ int radiation_correct(ffm_plume *P)
     const int nRay = (int)P->rayOmega.size();
     for (int i = 0; i < nRay; i++) {
         const double omega = P->rayOmega[i];
-        if (onePass) FFM_TRY(ffm_fvdom_ray_assemble_d(P->mesh, &P->rayD[3 * i], omega, P->radA, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr, P->upper, P->lower,
-                                                      P->dWork, P->sWork));
+        if (onePass && P->gm) FFM_TRY(ffm_fvdom_ray_assemble_v_d(P->mesh, &P->rayD[3 * i], omega, P->aRad, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr, P->upper,
+                                                                 P->lower, P->dWork, P->sWork));
+        else if (onePass) FFM_TRY(ffm_fvdom_ray_assemble_d(P->mesh, &P->rayD[3 * i], omega, P->radA, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr, P->upper, P->lower,
+                                                           P->dWork, P->sWork));
         else FFM_TRY(ray_assemble_ops(P, i, Ee));
         char nm[16]; snprintf(nm, sizeof(nm), "I%d", i);
         const int flip = P->radOrdered ? ray_flip_axis(P, i) : -1;
@@ -255,8 +279,11 @@ extern "C" int ffm_plume_ray_system(ffm_plume *P, int ray, int fused, double *di
     double *ref = P->radRef;
     forN(P, P->B, [=] __device__(long k) { ref[k] = Ib; });
     const double *Ee = P->radCoupled ? P->radE : nullptr;
-    if (fused) FFM_TRY(ffm_fvdom_ray_assemble_d(P->mesh, &P->rayD[3 * ray], P->rayOmega[ray], P->radA, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr,
-                                                P->upper, P->lower, P->dWork, P->sWork));
+    if (P->gm && !P->gmHaveA) { ffm_set_error("ffm_plume_ray_system: greyMeanAbsorptionEmission is on and has not been evaluated yet (step first)"); return FFM_ERR_ARG; }
+    if (fused && P->gm) FFM_TRY(ffm_fvdom_ray_assemble_v_d(P->mesh, &P->rayD[3 * ray], P->rayOmega[ray], P->aRad, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr,
+                                                           P->upper, P->lower, P->dWork, P->sWork));
+    else if (fused) FFM_TRY(ffm_fvdom_ray_assemble_d(P->mesh, &P->rayD[3 * ray], P->rayOmega[ray], P->radA, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr,
+                                                     P->upper, P->lower, P->dWork, P->sWork));
     else FFM_TRY(ray_assemble_ops(P, ray, Ee));
     std::vector<double> c(P->N), fu(std::max<long>(P->nNat, 1)), fl(std::max<long>(P->nNat, 1));
     FFM_TRY(ffm_d2h(P->ctx, c.data(), P->dWork, sizeof(double) * P->N));
@@ -464,5 +491,36 @@ extern "C" int ffm_plume_set_radiation_model(ffm_plume *P, double absorption, do
     if (!P->radE) { P->radE = dalloc(P, P->N); P->radShSu = dalloc(P, P->N); P->radShSp = dalloc(P, P->N); }
     if (!P->radE || !P->radShSu || !P->radShSp) return FFM_ERR_HIP;
     P->radA = absorption; P->Ehrr1 = Ehrr1; P->Ehrr2 = Ehrr2; P->radCoupled = true;
+    return FFM_OK;
+}
+
+// greyMeanAbsorptionEmission in place of the constant absorption coefficient and of constRadFractionEmission's E (see include/ffm.h).
+// The handle is borrowed, as ffm_plume_set_thermo's is; NULL: the constant again, the step of a handle that never had the model.
+extern "C" int ffm_plume_set_absorption_emission(ffm_plume *P, ffm_greymean *gm)
+{
+    if (!P) return FFM_ERR_ARG;
+    if (!gm) { P->gm = nullptr; P->gmHaveA = false; return FFM_OK; }
+    if (!P->oneBlock) { ffm_set_error("ffm_plume_set_absorption_emission: a block of a decomposed box (the model runs on a single block only)"); return FFM_ERR_UNSUPPORTED; }
+    if (!((P->radFreq > 0 || P->p1Freq > 0) && P->radCoupled)) {
+        ffm_set_error("ffm_plume_set_absorption_emission: needs ffm_plume_set_radiation with ffm_plume_set_radiation_model, or ffm_plume_set_radiation_p1, first");
+        return FFM_ERR_UNSUPPORTED;
+    }
+    // the model's species are the plume's, with the molecular weights of the selected thermo package (the stand-in's WMOL)
+    double W[NSP]; int nS = NSP;
+    if (P->thermo) FFM_TRY(ffm_thermo_species(P->thermo, &nS, nullptr));
+    if (P->thermo && nS == NSP) FFM_TRY(ffm_thermo_species(P->thermo, &nS, W)); else for (int i = 0; i < NSP; i++) W[i] = WMOL[i];
+    bool same = gm->t.n == NSP && nS == NSP;
+    for (int i = 0; same && i < NSP; i++) same = gm->t.W[i] == W[i];
+    if (!same) { ffm_set_error("ffm_plume_set_absorption_emission: the model's species or molecular weights are not the %s", P->thermo ? "thermo package's" : "plume's"); return FFM_ERR_ARG; }
+    PL_HIP(hipSetDevice(P->ctx->device));
+    if (!P->aRad) {
+        P->aRad = dalloc(P, P->N); P->aRadB = dalloc(P, P->B);
+        if (!P->aRad || !P->aRadB) return FFM_ERR_HIP;
+        PL_HIP(hipMalloc((void **)&P->gmFlag, sizeof(int)));
+        PL_HIP(hipMemsetAsync(P->gmFlag, 0, sizeof(int), P->ctx->stream));
+        PL_HIP(hipHostMalloc((void **)&P->gmFlagH, sizeof(int), hipHostMallocDefault));
+        *P->gmFlagH = 0;
+    }
+    P->gm = gm; P->gmHaveA = false;
     return FFM_OK;
 }

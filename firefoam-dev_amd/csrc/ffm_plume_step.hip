@@ -525,6 +525,20 @@ static int e_radiation_source(ffm_plume *P, const double **shSu, const double **
 {
     *shSu = *shSp = nullptr;
     if (!(P->radCoupled && P->radHaveG)) return FFM_OK;
+    if (P->gm) {
+        // greyMeanAbsorptionEmission: a follows T and Y every step (Rp() / Ru() call aCont() afresh), E = EhrrCoeff*Qdot.  Fused: one pass
+        // with a in registers; per-operator: the three entry points it restates, the same bytes
+        double *su = P->radShSu, *sp = P->radShSp; const double *Cpv = P->thermo ? P->Cp : nullptr;
+        if (P->fused) FFM_TRY(ffm_radiation_sh_greymean_d(P->gm, P->N, P->Y, P->p, P->T, SIGMA_SB, P->radG(), P->hs, P->Qdot, Cpv, CP, P->aRad, su, sp, P->gmFlag));
+        else {
+            FFM_TRY(ffm_greymean_a_d(P->gm, P->N, P->Y, P->p, P->T, P->aRad, P->gmFlag));
+            FFM_TRY(ffm_greymean_E_d(P->gm, P->N, P->Qdot, P->radE));
+            FFM_TRY(ffm_radiation_sh_v_d(P->ctx, P->N, P->aRad, P->aRad, SIGMA_SB, P->radE, P->radG(), P->T, P->hs, Cpv, CP, su, sp));
+        }
+        P->gmHaveA = true; P->radHaveSh = true;
+        *shSu = su; *shSp = sp;
+        return FFM_OK;
+    }
     double frac = 0.0;
     FFM_TRY(plume_rad_fraction(P, &frac));
     const double Rp = 4.0 * P->radA * SIGMA_SB, KA = P->radA;
@@ -863,7 +877,9 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     FFM_TRY(mv_weights(P));
     bool spOffDiagBound;
     const bool radNow = (P->radFreq > 0 && P->stepNo % P->radFreq == 0) || (P->p1Freq > 0 && P->stepNo % P->p1Freq == 0);
-    const bool jointYh = P->fused && P->mvSelection && !P->stecklerSolvers && P->oneBlock && !radNow && !P->separateH;
+    // (with greyMeanAbsorptionEmission h keeps its own EEqn in every step: radiation->Sh reads a of the species the Yi equations have just
+    // solved, solver/YEEqn.H:43-60 before :101, which the five lock-step systems, assembled together, cannot give it)
+    const bool jointYh = P->fused && P->mvSelection && !P->stecklerSolvers && P->oneBlock && !radNow && !P->separateH && !P->gm;
     FFM_TRY(species_eqns(P, &spOffDiagBound, jointYh));
     if (radNow) { FFM_TRY(radiation_correct(P)); spOffDiagBound = false; }     // radiation->correct(), solver/YEEqn.H:80: its ray solves bind other coefficients
     if (!jointYh) FFM_TRY(e_eqn(P, spOffDiagBound));
@@ -874,6 +890,8 @@ extern "C" int ffm_plume_step(ffm_plume *P)
     mul(P, P->rho, P->psi, P->p, P->N);
     P->time += P->dt; P->stepNo++;
     thermo_flag_fetch(P);           // thermo::T's iteration-limit flag travels with the synchronisation that closes the step
+    absem_flag_fetch(P);
     PL_HIP(hipStreamSynchronize(P->ctx->stream));
+    absem_flag_check(P);
     return thermo_flag_check(P);
 }

@@ -6,6 +6,7 @@
 // (1 - e) of the radiation the OTHER rays deposit on it (their qin), which is what fvDOM::calculate iterates on
 // (fvDOM/fvDOM.C:547-584; cases/wallFireSpread2D/constant/radiationProperties:39-46: maxIter 5, convergence 1e-3).
 #include "ffm_mesh.hpp"
+#include "ffm_greymean.hpp"
 
 // one thread per boundary face k; ray arrays are [nRay][B].  Order of the Ir sum: rays 0 .. nRay-1, the ray's own qin counted as
 // the zero it was reset to (radiativeIntensityRay::correct: qin_.boundaryFieldRef() = 0 before the matrix is built).
@@ -69,8 +70,10 @@ extern "C" int ffm_fvdom_sum_rays_d(ffm_mesh *m, int nRay, const double *all, do
 //   Ji, w (faces) | Jb, f (boundary) | ffm_fvm_transport | ffm_fvm_boundary_coeffs | diag += V k omega, source | ffm_fvm_add_boundary
 // leaves in upper / lower / diag / source, every term rounded as there (so the coefficients are those of the chain bit for
 // bit), from one walk over the rows: a row forms Ji of its own faces in registers, the owner writes the face coefficients.
-template <int W>
-__global__ void k_ray_assemble(MeshView q, double d0, double d1, double d2, double kO, double cS, double kS,
+// FIELD: the absorption coefficient is the cell field aF (an absorptionEmissionModel's aCont()) and kO, kS arrive as omega and
+// sigma: the row forms a[c]*omega and a[c]*sigma, the products the host forms once for a constant.
+template <int W, bool FIELD>
+__global__ void k_ray_assemble(MeshView q, double d0, double d1, double d2, double kO, double cS, double kS, const double *__restrict__ aF,
                                const double *__restrict__ T, const double *__restrict__ E, const double *__restrict__ refB,
                                const double *__restrict__ bDelta, double *__restrict__ Jf, double *__restrict__ wf,
                                double *__restrict__ upper, double *__restrict__ lower, double *__restrict__ diag,
@@ -100,8 +103,9 @@ __global__ void k_ray_assemble(MeshView q, double d0, double d1, double d2, doub
             if (wf) wf[e] = w;
         }
         const double Vc = q.V[c], t = T[c];
-        double d = dDiv + Vc * kO;
-        double s = E ? Vc * (cS * (kS * ((t * t) * (t * t)) + E[c] / 4.0)) : Vc * (cS * (kS * ((t * t) * (t * t))));
+        const double kOc = FIELD ? aF[c] * kO : kO, kSc = FIELD ? aF[c] * kS : kS;
+        double d = dDiv + Vc * kOc;
+        double s = E ? Vc * (cS * (kSc * ((t * t) * (t * t)) + E[c] / 4.0)) : Vc * (cS * (kSc * ((t * t) * (t * t))));
         const int jb = q.cellB[c];
         if (jb >= 0) for (int it = q.bcStart[jb]; it < q.bcStart[jb + 1]; it++) {
             const int k = q.bcItem[it];
@@ -120,8 +124,20 @@ extern "C" int ffm_fvdom_ray_assemble_d(ffm_mesh *m, const double *dAve3, double
 {
     if (!m || !dAve3 || !T || !upper || !lower || !diag || !source || (m->B && !ref_b)) return FFM_ERR_ARG;
     const double kO = absorption * omega, cS = 1.0 / M_PI * omega, kS = absorption * sigma;
-    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS(k_ray_assemble<W>, mview(m), dAve3[0], dAve3[1], dAve3[2], kO, cS, kS, T, E, ref_b, m->bDelta, J_f, w_f,
-                                            upper, lower, diag, source));
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_ray_assemble<W, false>), mview(m), dAve3[0], dAve3[1], dAve3[2], kO, cS, kS, nullptr, T, E, ref_b, m->bDelta,
+                                            J_f, w_f, upper, lower, diag, source));
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+// the same system with the absorption coefficient as a cell field: kO = a[c]*omega, kS = a[c]*sigma per row
+extern "C" int ffm_fvdom_ray_assemble_v_d(ffm_mesh *m, const double *dAve3, double omega, const double *a_d, double sigma, const double *T,
+                                          const double *E, const double *ref_b, double *J_f, double *w_f, double *upper, double *lower,
+                                          double *diag, double *source)
+{
+    if (!m || !dAve3 || !a_d || !T || !upper || !lower || !diag || !source || (m->B && !ref_b)) return FFM_ERR_ARG;
+    const double cS = 1.0 / M_PI * omega;
+    FFM_DISPATCH_W(m->A->maxW, LAUNCH_CELLS((k_ray_assemble<W, true>), mview(m), dAve3[0], dAve3[1], dAve3[2], omega, cS, sigma, a_d, T, E, ref_b, m->bDelta,
+                                            J_f, w_f, upper, lower, diag, source));
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }
@@ -178,6 +194,71 @@ extern "C" int ffm_radiation_sh_d(ffm_ctx *ctx, long n, double absorption, doubl
     FFM_HIP(hipSetDevice(ctx->device));
     hipLaunchKernelGGL(k_radiation_sh, dim3(sgrid(n)), dim3(256), 0, ctx->stream, n, absorption, 4.0 * absorption * sigma, radFraction, G_d, T_d, he_d,
                        Qdot_d, Cp_d, CpConst, su_d, sp_d);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+
+// The same with an absorptionEmissionModel's fields (fvDOM.C:588 Rp = 4 e sigma, :612 Ru = a G - E): sp and su in the order of
+// k_radiation_sh.  a and e may be one array (no __restrict__ on them).
+__device__ __forceinline__ void radiation_sh_cell(double a, double e, double sigma, double E, double G, double t, double he, double cp,
+                                                  double &su, double &sp)
+{
+    const double T3 = t * t * t, Rp = 4.0 * e * sigma;
+    const double Ru = a * G - E;
+    sp = 4.0 * Rp * T3 / cp;
+    su = Ru - Rp * T3 * (t - 4.0 * he / cp);
+}
+__global__ void k_radiation_sh_v(long n, const double *a, const double *e, double sigma, const double *__restrict__ E,
+                                 const double *__restrict__ G, const double *__restrict__ T, const double *__restrict__ he,
+                                 const double *__restrict__ Cp, double CpConst, double *__restrict__ su, double *__restrict__ sp)
+{
+    GRID_STRIDE(c, n) {
+        double u, p;
+        radiation_sh_cell(a[c], e[c], sigma, E[c], G[c], T[c], he[c], Cp ? Cp[c] : CpConst, u, p);
+        su[c] = u; sp[c] = p;
+    }
+}
+extern "C" int ffm_radiation_sh_v_d(ffm_ctx *ctx, long n, const double *a_d, const double *e_d, double sigma, const double *E_d, const double *G_d,
+                                    const double *T_d, const double *he_d, const double *Cp_d, double CpConst, double *su_d, double *sp_d)
+{
+    if (!ctx || n < 0 || !a_d || !e_d || !E_d || !G_d || !T_d || !he_d || !su_d || !sp_d) return FFM_ERR_ARG;
+    if (n == 0) return FFM_OK;
+    FFM_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_radiation_sh_v, dim3(sgrid(n)), dim3(256), 0, ctx->stream, n, a_d, e_d, sigma, E_d, G_d, T_d, he_d, Cp_d, CpConst, su_d, sp_d);
+    FFM_HIP(hipGetLastError());
+    return FFM_OK;
+}
+// The per-step form with greyMeanAbsorptionEmission: a = e of the cell evaluated in registers (greymean_a: ffm_greymean_a_d's
+// expression), E = EhrrCoeff*Qdot, then su and sp as above -- bit for bit ffm_greymean_a_d, ffm_greymean_E_d, ffm_radiation_sh_v_d,
+// without the write and re-read of a and E and in one launch.  a is written once where asked for.
+__global__ __launch_bounds__(256) void k_radiation_sh_greymean(long n, GreyMeanTable t, GreyMeanPtrs y, double sigma, const double *__restrict__ p,
+                                                               const double *__restrict__ T, const double *__restrict__ G,
+                                                               const double *__restrict__ he, const double *__restrict__ Qdot,
+                                                               const double *__restrict__ Cp, double CpConst, double *__restrict__ aOut,
+                                                               double *__restrict__ su, double *__restrict__ sp, int *flag)
+{
+    bool outside = false;
+    GRID_STRIDE(c, n) {
+        const double tc = T[c];
+        const double a = greymean_a(t, y, c, p[c], tc, outside);
+        const double E = t.EhrrCoeff * Qdot[c];
+        double u, s;
+        radiation_sh_cell(a, a, sigma, E, G[c], tc, he[c], Cp ? Cp[c] : CpConst, u, s);
+        if (aOut) aOut[c] = a;
+        su[c] = u; sp[c] = s;
+    }
+    if (flag && outside) *flag = 1;
+}
+extern "C" int ffm_radiation_sh_greymean_d(ffm_greymean *gm, long n, const double *const *Y_d, const double *p_d, const double *T_d, double sigma,
+                                           const double *G_d, const double *he_d, const double *Qdot_d, const double *Cp_d, double CpConst,
+                                           double *a_out_d, double *su_d, double *sp_d, int *flag_d)
+{
+    if (!gm || n < 0 || !Y_d || !p_d || !T_d || !G_d || !he_d || !Qdot_d || !su_d || !sp_d) return FFM_ERR_ARG;
+    GreyMeanPtrs y; FFM_TRY(greymean_ptrs(gm, Y_d, y));
+    if (n == 0) return FFM_OK;
+    FFM_HIP(hipSetDevice(gm->ctx->device));
+    hipLaunchKernelGGL(k_radiation_sh_greymean, dim3(sgrid(n)), dim3(256), 0, gm->ctx->stream, n, gm->t, y, sigma, p_d, T_d, G_d, he_d, Qdot_d, Cp_d,
+                       CpConst, a_out_d, su_d, sp_d, flag_d);
     FFM_HIP(hipGetLastError());
     return FFM_OK;
 }

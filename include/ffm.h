@@ -617,6 +617,20 @@ int ffm_fvdom_ray_assemble_d(ffm_mesh *mesh, const double *dAve3, double omega, 
 int ffm_radiation_sh_d(ffm_ctx *ctx, long n, double absorption, double sigma, double radFraction, const double *G_d, const double *T_d,
                        const double *he_d, const double *Qdot_d, const double *Cp_d /* nullable */, double CpConst, double *su_d,
                        double *sp_d);
+/* The field forms of the two passes above, for an absorptionEmissionModel whose a, e and E are cell fields (greyMeanAbsorptionEmission
+ * below; the P1 entry points already take such fields).
+ * ffm_fvdom_ray_assemble_v_d: ffm_fvdom_ray_assemble_d -- the same kernel, a template switch -- with a_d[c]*omega and a_d[c]*sigma per
+ *   cell in place of the host-formed absorption*omega and absorption*sigma.  With a_d[c] == x everywhere it writes bit for bit what the
+ *   scalar form writes for absorption = x, and for any a_d the bits of the operator chain with V[c]*(a[c]*omega) and (a[c]*sigma)*T^4.
+ * ffm_radiation_sh_v_d: Rp = 4.0*e*sigma, Ru = a*G - E per cell, then sp and su exactly as ffm_radiation_sh_d; a_d and e_d may be the
+ *   same array.  Uniform a = e = x and E = radFraction*Qdot give the scalar form's bits.  FFM_ERR_ARG (nothing written): a NULL
+ *   context or array (Cp_d excepted), n < 0; n == 0 is a no-op. */
+int ffm_fvdom_ray_assemble_v_d(ffm_mesh *mesh, const double *dAve3, double omega, const double *a_d, double sigma, const double *T,
+                               const double *E, const double *ref_b, double *J_f, double *w_f, double *upper, double *lower,
+                               double *diag, double *source);
+int ffm_radiation_sh_v_d(ffm_ctx *ctx, long n, const double *a_d, const double *e_d, double sigma, const double *E_d, const double *G_d,
+                         const double *T_d, const double *he_d, const double *Cp_d /* nullable */, double CpConst, double *su_d,
+                         double *sp_d);
 /* fvDOM::updateG, cell part (fvDOM/fvDOM.C:697-718): G[c] = ((0 + I_0[c] omega_0) + I_1[c] omega_1) + ... in ray-index order,
  * accumulated in a register: every ray is read once and G written once -- bitwise what nRay passes G = G + I_i*omega_i over a zeroed
  * G leave.  I_dd: DEVICE array of nRay device pointers, omega_d: device [nRay].  Any nRay >= 1; n == 0 is a no-op.  FFM_ERR_ARG: a
@@ -761,6 +775,7 @@ int ffm_solve_ordered_staged_d(ffm_ldu *ldu, const ffm_flow_order *o, double *ps
  * the order of solver/fireFoam.C:97-119.  bench.py's workload.                */
 typedef struct ffm_plume ffm_plume;
 typedef struct ffm_thermo ffm_thermo;      /* the thermo package below (ffm_thermo_create): ffm_plume_set_thermo borrows one */
+typedef struct ffm_greymean ffm_greymean;  /* greyMeanAbsorptionEmission below (ffm_greymean_create): ffm_plume_set_absorption_emission borrows one */
 int ffm_plume_create(ffm_ctx *ctx, int nx, int ny, int nz, double h, double deltaT, ffm_plume **out);
 /* one rank's block [lo,hi) of the global box; nbrRank[6] = rank across the -x,+x,-y,+y,-z,+z side or -1
  * (physical boundary).  Needs ffm_comm_init / ffm_comm_init_host when any neighbour exists.            */
@@ -869,6 +884,24 @@ int ffm_plume_set_radiation_thermo(ffm_plume *plume, int on);
  * or wallEmissivity outside [0, 1].  Unpinned by reference data: the reference ships no output of a P1 run; the check is tests/plume_p1_ref.py.
  * Not here: decomposed boxes, per-patch emissivities, MarshakRadiationFixedTemperature, coefficient models other than the constant. */
 int ffm_plume_set_radiation_p1(ffm_plume *plume, int solverFreq, double absorption, double Ehrr1, double Ehrr2, double wallEmissivity);
+/* greyMeanAbsorptionEmission (ffm_greymean_create below) as the step's absorptionEmissionModel, in place of the constant absorption
+ * coefficient and of E = RadFraction*Qdot; gm NULL (the default): the constant again -- the step then issues exactly the launches of a
+ * handle that never had the model.  The handle is borrowed, as ffm_plume_set_thermo's is.  Needs ffm_plume_set_radiation with
+ * ffm_plume_set_radiation_model, or ffm_plume_set_radiation_p1, first (FFM_ERR_UNSUPPORTED otherwise); the model's species must be the
+ * plume's five with the molecular weights of the selected thermo package, or the stand-in's (FFM_ERR_ARG).  With it on:
+ *   radiation->correct() evaluates a once (ffm_greymean_a_d) and E = EhrrCoeff*Qdot (ffm_greymean_E_d); the RadFraction reduction over
+ *     the burner patch and its host read-back drop out.  Every ray is assembled with the field (fused: ffm_fvdom_ray_assemble_v_d; per
+ *     operator: the chain with V*(a*omega) and (a*sigma)*T^4 per cell); P1 passes a_d = e_d = a and its zero-gradient patch copy a_b to
+ *     ffm_p1_assemble_d, and to the chain;
+ *   radiation->Sh of EVERY step comes from ffm_radiation_sh_greymean_d (fused) or from ffm_greymean_a_d, ffm_greymean_E_d,
+ *     ffm_radiation_sh_v_d (per operator): a is current every step, as Rp() / Ru() are upstream.  h keeps its separate EEqn in every
+ *     step while the model is on, also in the steps without a correct() where it is otherwise the fifth lock-step system: Sh reads a
+ *     of the species the Yi equations have just solved (solver/YEEqn.H:43-60 before :101), and five systems assembled together would
+ *     give it the old ones.  Fused and per-operator steps are byte for byte equal.
+ * Fields aRad (a of the last evaluation), ShSu, ShSp.  The temperature-range flag is read with the step's closing synchronisation; the
+ * reference only warns (absorptionCoeffs::checkT), so the step prints a warning, leaves the text in ffm_last_error and goes on.
+ * FFM_ERR_UNSUPPORTED with a message: a block of a decomposed box.  Unpinned by reference data (tests/plume_greymean_ref.py). */
+int ffm_plume_set_absorption_emission(ffm_plume *plume, ffm_greymean *gm /* NULL: the constant, default */);
 /* How the rays are solved on a block of a decomposed box.  0 (default): every ray is a block-Jacobi PBiCGStab + DILU solve over
  * all ranks.  1: the staged, direction-ordered sweep -- the ranks walk the ticks of ffm_ray_schedule; in a tick a rank assembles
  * at most one ray (ffm_fvdom_ray_assemble_d), moves the inflow from its upstream neighbours' ghost values into the source
@@ -1027,6 +1060,43 @@ int ffm_edc_correct_d(ffm_ctx *ctx, long n, const double *rho_d, const double *k
                       double C_Stiff, double qFuel, double *wFuel_d, double *Qdot_d);
 int ffm_les_keqn_nut_d(ffm_ctx *ctx, long n, double Ck, double Prt, const double *k_d, const double *delta_d, const double *rho_d,
                        double *nut_d, double *alphat_d);
+
+/* ------------------------------------------------------- greyMeanAbsorptionEmission (gas phase) */
+/* The reference's second gas absorption/emission model (packages/thermophysicalModels/radiation/submodels/absorptionEmissionModel/
+ * greyMeanAbsorptionEmission/greyMeanAbsorptionEmission.C:177-314; coefficient set: cases/pyrolysis1D/constant/radiationProperties:58-146):
+ * a polynomial in T or 1/T per participating species, weighted by the species' partial pressure in atm; e = a; E = EhrrCoeff*Qdot.
+ * Per cell, in exactly this operation order and without FMA contraction:
+ *   invWt = ((0 + Y_0/W_0) + Y_1/W_1) + ...          over ALL nSpecies, in index order (formed once; the reference recomputes it per
+ *                                                     participating species with the same operations, hence the same bits)
+ *   a = 0; for the participating species j = 0 .. nPart-1, s = specie[j]:
+ *     Xk = Y_s/(W_s*invWt);  Xipi = Xk*(p/101325.0);  b = T < Tcommon_j ? lo_j : hi_j  (T == Tcommon takes hi);  Ti = invTemp_j ? 1.0/T : T
+ *     a += Xipi*(((((b5*Ti + b4)*Ti + b3)*Ti + b2)*Ti + b1)*Ti + b0)
+ * p/101325.0 is upstream OpenFOAM's paToAtm, restated from knowledge: the function is not in the reference tree.
+ * SUMMATION ORDER: the caller's list order.  The reference walks a HashTable<label>, whose order follows upstream's string hash; that
+ * hash is not in the reference tree and cannot be reproduced here.  The difference is the rounding of a sum of at most 8 terms; this
+ * order is UNPINNED BY REFERENCE DATA (the reference ships no output of a run with this model).
+ * Not built: the lookUpTableFileName branch (species from a mixture-fraction table), which needs an `ft` field no case here solves.
+ *
+ * ffm_greymean_create: W[nSpecies] of all species of the mixture in the order of Y_d; specie[nPart] (indices into that list, distinct),
+ *   invTemp[nPart], Tcommon / Tlow / Thigh[nPart], lo / hi [nPart][6] = loTcoeffs / hiTcoeffs (b0 .. b5).  nSpecies <= 8 (the thermo
+ *   table's limit), 1 <= nPart <= 8.  Anything else: FFM_ERR_ARG, nothing created.  The table travels by value in the kernel arguments.
+ * ffm_greymean_a_d: a_d[0..n) as above; Y_d: a HOST array of nSpecies device pointers, as for ffm_thermo_*_d.  flag_d (nullable; a
+ *   device int the caller owns and clears) is set to 1 by a plain store when a T lies outside [Tlow, Thigh] of a participating species --
+ *   the reference only warns (absorptionCoeffs::checkT).  It is only ever raised; the caller reads it at its next synchronisation.
+ *   n == 0 is a no-op; NULL arguments (flag_d excepted) or n < 0: FFM_ERR_ARG, nothing written.
+ * ffm_greymean_E_d: E = EhrrCoeff*Qdot, Qdot per volume (the reference's dimEnergy/dimTime/dimVolume branch).
+ * ffm_radiation_sh_greymean_d: radiation->Sh of one step with this model in ONE pass: a of the cell in registers, E = EhrrCoeff*Qdot,
+ *   su and sp as ffm_radiation_sh_v_d with e = a; a written to a_out_d where that is given.  Bit for bit ffm_greymean_a_d, then
+ *   ffm_greymean_E_d, then ffm_radiation_sh_v_d(a, a, sigma, E, ...), without the write and re-read of a and E. */
+int ffm_greymean_create(ffm_ctx *ctx, int nSpecies, const double *W, int nPart, const int *specie, const int *invTemp, const double *Tcommon,
+                        const double *Tlow, const double *Thigh, const double *lo, const double *hi, double EhrrCoeff, ffm_greymean **out);
+int ffm_greymean_destroy(ffm_greymean *gm);
+int ffm_greymean_a_d(ffm_greymean *gm, long n, const double *const *Y_d, const double *p_d, const double *T_d, double *a_d,
+                     int *flag_d /* nullable */);
+int ffm_greymean_E_d(ffm_greymean *gm, long n, const double *Qdot_d, double *E_d);
+int ffm_radiation_sh_greymean_d(ffm_greymean *gm, long n, const double *const *Y_d, const double *p_d, const double *T_d, double sigma,
+                                const double *G_d, const double *he_d, const double *Qdot_d, const double *Cp_d /* nullable */, double CpConst,
+                                double *a_out_d /* nullable */, double *su_d, double *sp_d, int *flag_d /* nullable */);
 
 /* turbulence->divDevRhoReff(U) (solver/UEqn.H:12), explicit part: out[j] = component j of fvc::div(gamma*dev2(T(fvc::grad(U)))),
  * Gauss linear, from the nine cell gradients g[3*i + j] = d_i U_j (ffm_fvc_grad_multi of the three components), gamma = rho*nuEff
