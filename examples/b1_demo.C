@@ -317,6 +317,25 @@ extern "C" int b1_solve_sequence(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, ffm_
     return n;
 }
 
+// constantAbsorptionEmission whose E is a field the driver holds (the drivers below take E, or Qdot, from the host)
+class fieldEmission : public constantAbsorptionEmission
+{
+    const volScalarField& Ef_;
+public:
+    fieldEmission(const fvMesh& mesh, scalar a, scalar e, const volScalarField& E) : constantAbsorptionEmission(mesh, a, e, 0.0), Ef_(E) {}
+    volScalarField ECont() const { return Ef_; }
+};
+// a model that is no constant model and returns uniform fields: b1_greymean's hooks 2
+class uniformFieldsModel : public radiation::absorptionEmissionModel
+{
+    const fvMesh& mesh_; scalar a_, e_; const volScalarField& Ef_;
+public:
+    uniformFieldsModel(const fvMesh& mesh, scalar a, scalar e, const volScalarField& E) : mesh_(mesh), a_(a), e_(e), Ef_(E) {}
+    volScalarField aCont() const { return uniformField("a", mesh_, a_); }
+    volScalarField eCont() const { return uniformField("e", mesh_, e_); }
+    volScalarField ECont() const { return Ef_; }
+};
+
 // The order in which pimpleControl walks one time step (no device work): for every pass of the innermost loop one int
 //   outer*10000 + corrector*100 + nonOrthogonal*10 + finalInnerIter, then -1 at the end of each outer pass.
 extern "C" int b1_pimple_sequence(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, int nOuter, int nCorr, int nNonOrth, int* out, int cap)
@@ -631,8 +650,7 @@ extern "C" int b1_physics(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, const b1Phy
 
     // ---- d: radiation
     volScalarField Ef("E", mesh); Ef.v.assignHost(io->E);
-    P1 p1(mesh, thermo.T(), 1, io->a, io->e, 0.0, io->sigmaS, io->Cscatter, sigma);
-    p1.emission = [&Ef]() { return Ef; };
+    P1 p1(mesh, thermo.T(), 1, io->sigmaS, io->Cscatter, sigma, std::make_shared<fieldEmission>(mesh, io->a, io->e, Ef));
     p1.emissivity().assignHost(io->emissivity);
     p1.correct();
     p1.G_.v.toHost(io->p1Out);
@@ -792,7 +810,7 @@ static int b1_fvdom_run(bool ordered, ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh,
     surfaceScalarField phi(mesh);
     mesh.store("phi", phi); mesh.store("Qdot", Qdot);
     std::vector<double> zeroB(B, 0.0);
-    fvDOM dom(mesh, Tf, nPhi, nTheta, 1, a, 5.670367e-8, 1.0, 1.0, zeroB.data());
+    fvDOM dom(mesh, Tf, nPhi, nTheta, 1, 5.670367e-8, std::make_shared<constRadFractionEmission>(mesh, a, 1.0, 1.0, zeroB.data()));
     dom.setIteration(maxIter, tolerance);
     dom.setOrderedSolves(ordered);
     dom.emissivity().assignHost(emissivity);
@@ -830,7 +848,7 @@ extern "C" int b1_fvdom_ordered(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, int e
 
 // ---- the P1 handle (include/fireFoamHandles.H) on any mesh: nCalls calls of radiation->correct() (solverFreq 1) with a given temperature
 // field (cells + boundary faces), constant a, e, scatter constants sigma_s, C, wall emissivities and -- where E is given -- the emission as
-// a cell field through the handle's emission provider (NULL: E = 0); G by PCG + DIC to GTol, relTol 0, from G = 0.  Out: G [N], G_b, qr [B],
+// a cell field through the handle's absorptionEmissionModel (fieldEmission above; NULL: E = 0); G by PCG + DIC to GTol, relTol 0, from G = 0.  Out: G [N], G_b, qr [B],
 // iters[nCalls] = PCG iterations of every call.  sysClass / sysFused (both or neither; [nNative + 2 N]: upper, diag, source): the system
 // as the class layer's operators leave it for the solver, and as ffm_p1_assemble_d does from the same fields.  Returns the number of
 // solves logged.  tests/test_p1_foam_gpu.py compares with tests/p1_ref.py.
@@ -844,8 +862,9 @@ extern "C" int b1_p1(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, double a, double
     const label N = mesh.nCells, B = mesh.nBoundary, nNat = mesh.nInternalNative;
     volScalarField Tf("T", mesh); Tf.v.assignHost(T); Tf.b.assignHost(Tb);
     volScalarField Ef("E", mesh); if (E) Ef.v.assignHost(E);
-    P1 p1(mesh, Tf, 1, a, e, 0.0, sigmaS, Cscatter, sigma);
-    if (E) p1.emission = [&Ef]() { return Ef; };
+    std::shared_ptr<radiation::absorptionEmissionModel> ae;
+    if (E) ae = std::make_shared<fieldEmission>(mesh, a, e, Ef); else ae = std::make_shared<constantAbsorptionEmission>(mesh, a, e, 0.0);
+    P1 p1(mesh, Tf, 1, sigmaS, Cscatter, sigma, ae);
     p1.emissivity().assignHost(emissivity);
     int nSolves = 0;
     for (int c = 0; c < nCalls; c++) {
@@ -913,9 +932,9 @@ extern "C" int b1_greymean_table_refusal(const char* path, const char* lookUpTab
 // says), the blank-separated species list with W, and host fields Y [nSpecies][N], p, T (cells), Tb (boundary faces), Qdot.
 //   aOut [N + B]: aCont() cells, then patch values; EOut [N]: ECont(); flagOut: whether a T left a species' range.
 //   model 1: fvDOM (nPhi, nTheta, ordered ray solves, maxIter 1, emissivity_b), model 2: P1 (sigma_s = C = 0, G by PCG + DIC to GTol), model 0:
-//   neither.  hooks 1: the model's aCont / eCont / ECont are the handle's absorption / emission providers; hooks 2: providers that return
-//   the UNIFORM fields aConst, eConst and E = Qdot; hooks 0: unset -- the constants aConst, eConst, and E = Qdot (fvDOM: RadFraction 1; P1:
-//   its emission provider, as b1_p1).  nCalls calls of correct(), then Sh(thermo, he) with Cpv = the field Cp.
+//   neither.  hooks 1: the model is the handle's absorptionEmissionModel; hooks 2: a model that returns the UNIFORM fields aConst, eConst
+//   and E = Qdot (uniformFieldsModel above); hooks 0: the layer's constant models with aConst, eConst, and E = Qdot (fvDOM:
+//   constRadFractionEmission, RadFraction 1; P1: fieldEmission, as b1_p1).  nCalls calls of correct(), then Sh(thermo, he) with Cpv = the field Cp.
 //   IOut [nRay][N] (fvDOM), GOut [N], GbOut / qrOut [B] (P1: G_b, qr; fvDOM: qin, qr), iters [nCalls] (P1: PCG iterations; fvDOM: iterations
 //   of calculate), shOut [2 N]: diag and source[0] of the matrix Sh returns.  Returns nRay (fvDOM), the number of solves (P1) or 0.
 // tests/test_greymean_foam_gpu.py.
@@ -939,16 +958,20 @@ extern "C" int b1_greymean(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, const char
     surfaceScalarField phi(mesh);
     mesh.store("phi", phi); mesh.store("Qdot", Qf);
     const dictionaryFile dict(dictPath);
-    greyMeanAbsorptionEmission ae(mesh, species, Wv, Yf, pf, Tf, dict.top.subDict("greyMeanAbsorptionEmissionCoeffs"), lookUpTableOverride);
+    const auto ae = std::make_shared<greyMeanAbsorptionEmission>(mesh, species, Wv, Yf, pf, Tf, dict.top.subDict("greyMeanAbsorptionEmissionCoeffs"), lookUpTableOverride);
     {
-        const volScalarField a(ae.aCont()), E(ae.ECont());
+        const volScalarField a(ae->aCont()), E(ae->ECont());
         a.v.toHost(aOut); a.b.toHost(aOut + N); E.v.toHost(EOut);
-        *flagOut = ae.temperatureOutOfRange() ? 1 : 0;
+        *flagOut = ae->temperatureOutOfRange() ? 1 : 0;
     }
     perfectGasConstCpThermo thermo(mesh, 8314.47, 1005.0, 298.15);
-    auto aFn = [&]() { return hooks == 1 ? ae.aCont() : uniformField("a", mesh, aConst); };
-    auto eFn = [&]() { return hooks == 1 ? ae.eCont() : uniformField("e", mesh, eConst); };
-    auto EFn = [&]() { return hooks == 1 ? ae.ECont() : Qf; };
+    // the model of fvDOM (e = a) or P1: hooks 0 the layer's constant model of that radiation model, 1 greyMean, 2 the uniform fields
+    typedef std::shared_ptr<radiation::absorptionEmissionModel> modelPtr;
+    auto modelOf = [&](scalar e, modelPtr constants) -> modelPtr {
+        if (hooks == 1) return ae;
+        if (hooks == 2) return std::make_shared<uniformFieldsModel>(mesh, aConst, e, Qf);
+        return constants;
+    };
     auto shOf = [&](const fvScalarMatrix& Mc) {
         fvScalarMatrix M(Mc); M.ensure();
         M.diag.toHost(shOut); M.source[0].toHost(shOut + N);
@@ -956,23 +979,20 @@ extern "C" int b1_greymean(ffm_ctx* ctx, ffm_ldu* ldu, ffm_mesh* msh, const char
     int ret = 0;
     if (model == 1) {
         std::vector<double> zeroB(B, 0.0);
-        fvDOM dom(mesh, Tf, nPhi, nTheta, 1, aConst, sigma, 1.0, 1.0, zeroB.data());
+        fvDOM dom(mesh, Tf, nPhi, nTheta, 1, sigma, modelOf(aConst, std::make_shared<constRadFractionEmission>(mesh, aConst, 1.0, 1.0, zeroB.data())));
         dom.setIteration(1, 0.0);
         dom.setOrderedSolves(true);
         dom.emissivity().assignHost(emissivity);
         dom.Cpv = [&]() { return Cpf; };
-        if (hooks) { dom.absorption = aFn; dom.emission = EFn; }
         for (int c = 0; c < nCalls; c++) { dom.correct(); iters[c] = dom.lastIterations_; }
         for (label i = 0; i < dom.nRay(); i++) dom.I_[i].v.toHost(IOut + (size_t)i*N);
         dom.G_.v.toHost(GOut); dom.qin_.toHost(GbOut); dom.qr_.toHost(qrOut);
         shOf(dom.Sh(thermo, hf));
         ret = dom.nRay();
     } else if (model == 2) {
-        P1 p1(mesh, Tf, 1, aConst, eConst, 0.0, 0.0, 0.0, sigma);
+        P1 p1(mesh, Tf, 1, 0.0, 0.0, sigma, modelOf(eConst, std::make_shared<fieldEmission>(mesh, aConst, eConst, Qf)));
         p1.emissivity().assignHost(emissivity);
         p1.Cpv = [&]() { return Cpf; };
-        p1.emission = EFn;
-        if (hooks) { p1.absorption = aFn; p1.eCont = eFn; }
         for (int c = 0; c < nCalls; c++) {
             mesh.log.clear();
             p1.correct();

@@ -184,9 +184,9 @@ struct snippetSolver
             mesh.divSchemes["div(Ji,Ii_h)"] = {cs->radDivScheme, 1, 0, 1};
             if (cs->wallFireSelection) { solverControls g; g.solver = FFM_GAMG; g.preconditioner = FFM_DILU; g.tolerance = 1e-4; g.relTol = 0; mesh.solvers["Ii"] = mesh.solvers["IiFinal"] = g; }   // fvSolution:160-170
             else mesh.solvers["Ii"] = mesh.solvers["IiFinal"] = {FFM_PBICGSTAB, FFM_DILU, 1e-4, 0, 0, 1000, 1};
-            fvDOM* dom = new fvDOM(mesh, T, cs->radNPhi, cs->radNTheta, cs->radiationFreq, cs->kAbs, cs->sigmaSB, cs->radEhrr1, cs->radEhrr2, cs->radMlrMask);
+            fvDOM* dom = new fvDOM(mesh, T, cs->radNPhi, cs->radNTheta, cs->radiationFreq, cs->sigmaSB,
+                                   std::make_shared<constRadFractionEmission>(mesh, cs->kAbs, cs->radEhrr1, cs->radEhrr2, cs->radMlrMask, cs->radMlrMask2));
             dom->setIteration(cs->radMaxIter, cs->radTolerance);
-            if (cs->radMlrMask2) dom->setSecondMlrMask(cs->radMlrMask2);
             if (cs->radEmissivity) dom->emissivity().assignHost(cs->radEmissivity);
             const scalar Cp = cs->Cp;
             dom->Cpv = [this, Cp]() { return uniformField("Cpv", mesh, Cp); };

@@ -175,7 +175,8 @@ struct stecklerSolver
             mesh.solvers["Ii"] = ii;
             mesh.divSchemes["div(Ji,Ii_h)"] = {0, 1, 0, 1};                               // Gauss upwind (fvSchemes:60)
             mesh.store("Qdot", Qdot);
-            radiation = autoPtr<radiation::radiationModel>(new fvDOM(mesh, T, 2, 4, cs->radiationFreq, 0.0, cs->sigmaSB, 0.5, 0.22, cs->mlrMask));
+            radiation = autoPtr<radiation::radiationModel>(new fvDOM(mesh, T, 2, 4, cs->radiationFreq, cs->sigmaSB,
+                                                                       std::make_shared<constRadFractionEmission>(mesh, 0.0, 0.5, 0.22, cs->mlrMask)));
         }
         else radiation = autoPtr<radiation::radiationModel>(new noRadiation());
     }

@@ -115,7 +115,7 @@ extern "C" int ffm_plume_create_block(ffm_ctx *ctx, int gx, int gy, int gz, cons
         FFM_TRY(ffm_ldu_create_hint(ctx, (int)nOwn, (int)nGhost, F, l2.data(), u2.data(), hintNew.data(), &P->A));
     }
     if (!P->A->identity) { ffm_set_error("plume: renumbered mesh is not native"); return FFM_ERR_ADDR; }
-    if (nGhost == 0) { P->hL2 = l2; P->hU2 = u2; P->hOldToNew = oldToNew; P->hFd2 = fd2; }      // for the direction-ordered ray solves (a decomposed block rebuilds them if the staged sweep is asked for: plume_host_addressing)
+    if (nGhost == 0) { P->hL2 = l2; P->hU2 = u2; P->hOldToNew = oldToNew; }      // for the direction-ordered ray solves (a decomposed block rebuilds them if the staged sweep is asked for: plume_host_addressing)
     for (int q = 0; q < 6; q++) P->nbrRank[q] = nbrRank[q];
     for (int q = 0; q < 7; q++) P->gOff[q] = gOff[q];
     FFM_TRY(ffm_ldu_set_global_cells(P->A, (long)gx * gy * gz));

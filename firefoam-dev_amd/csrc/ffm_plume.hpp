@@ -101,7 +101,8 @@ struct ffm_plume {
     // direction-ordered ray solves (single block): for the flip of axis a, radCm[a][c] = cell that takes c's place and
     // radFm[a][e] = native face that takes e's place (bit-complemented where owner and neighbour change roles); the permuted
     // system has the sparsity of A and is triangular for every ray whose minority-sign axis is a, so DILU solves it exactly
-    std::vector<int> hL2, hU2, hOldToNew; std::vector<signed char> hFd2;
+    // (solve_ray gathers it into radDB .. radLB).  hL2, hU2, hOldToNew: the renumbered addressing on the host the maps are made from
+    std::vector<int> hL2, hU2, hOldToNew;
     int *radCm[3] = {nullptr, nullptr, nullptr}, *radFm[3] = {nullptr, nullptr, nullptr};
     double *radDB = nullptr, *radSB = nullptr, *radPsiB = nullptr, *radUB = nullptr, *radLB = nullptr;
     bool radOrdered = false;               // single block with the flip maps: every ray is one exact DILU application
@@ -112,6 +113,8 @@ struct ffm_plume {
     int nbrRank[6] = {-1, -1, -1, -1, -1, -1}, gOff[7] = {0, 0, 0, 0, 0, 0, 0}, blkGrid[3] = {1, 1, 1}, blkAt[3] = {0, 0, 0};
     int *radHaloCells = nullptr; int nRadHaloCells = 0; double *radGhostBuf = nullptr;
     std::vector<int> radTick, radNbrTick[6];
+    // the rays, G, and the per-operator assembly's face and patch arrays; radRef [B] is the black inflow at the ambient temperature,
+    // filled where it is allocated (ffm_plume_set_radiation) and only read after that
     std::vector<double *> I; double *G = nullptr, *radJ = nullptr, *radW = nullptr, *radJb = nullptr, *radF = nullptr, *radRef = nullptr, *radSrc = nullptr;
     // the reference's absorption / emission model and radiation->Sh (ffm_plume_set_radiation_model): constant absorption
     // coefficient, emission E = RadFraction*Qdot with the radScaling of constRadFractionEmission::ECont
@@ -128,8 +131,8 @@ struct ffm_plume {
     // ffm_plume_set_radiation_thermo: the rays and radiation->Sh accepted together with the thermo package (Sh then reads the Cp field)
     bool radThermo = false;
     // P1 in place of the rays (ffm_plume_set_radiation_p1; off: p1Freq 0, every pointer null): its G (the rays keep theirs), the patch
-    // arrays gamma_b, valueFraction, refValue, G_b, qr, T_b [B], and -- the per-operator form only -- gamma on cells and faces, su
-    int p1Freq = 0; double p1Emis = 1.0;
+    // arrays gamma_b, valueFraction, refValue, G_b, qr, T_b, the wall emissivity [B], and -- the per-operator form only -- gamma on cells and faces, su
+    int p1Freq = 0;
     double *p1G = nullptr, *p1GammaB = nullptr, *p1F = nullptr, *p1Ref = nullptr, *p1Gb = nullptr, *p1Qr = nullptr, *p1Tb = nullptr, *p1EmisB = nullptr;
     double *p1GammaC = nullptr, *p1GammaF = nullptr, *p1Su = nullptr, *p1Sn = nullptr;
     bool p1HaveQr = false;

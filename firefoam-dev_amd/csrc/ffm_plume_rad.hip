@@ -47,6 +47,16 @@ static int ray_assemble_ops(ffm_plume *P, int i, const double *Ee)
     });
     return ffm_fvm_add_boundary(m, P->ic[0], P->bc[0], P->diag, su, nullptr, P->dWork, P->sWork);
 }
+// the system of ray i in one pass (ffm_fvdom_ray_assemble_v_d with greyMean's a of the cells, else ffm_fvdom_ray_assemble_d) or by
+// the operator chain above: the same bytes
+static int ray_assemble(ffm_plume *P, int i, const double *Ee, bool onePass)
+{
+    if (!onePass) return ray_assemble_ops(P, i, Ee);
+    if (P->gm) return ffm_fvdom_ray_assemble_v_d(P->mesh, &P->rayD[3 * i], P->rayOmega[i], P->aRad, SIGMA_SB, P->T, Ee, P->radRef, nullptr, nullptr, P->upper,
+                                                 P->lower, P->dWork, P->sWork);
+    return ffm_fvdom_ray_assemble_d(P->mesh, &P->rayD[3 * i], P->rayOmega[i], P->radA, SIGMA_SB, P->T, Ee, P->radRef, nullptr, nullptr, P->upper, P->lower,
+                                    P->dWork, P->sWork);
+}
 
 // fvDOM::updateG over the cells (ghost cells included: every rank holds its neighbours' rays there) in one pass
 static int rad_update_G(ffm_plume *P)
@@ -65,6 +75,25 @@ static int ray_flip_axis(const ffm_plume *P, int i)
     return -1;
 }
 
+// The solve of a ray's system in dWork, sWork, upper, lower: as it stands (flip < 0), or with the first n cells renamed by the flip of
+// that axis -- same sparsity, triangular -- gathered into radDB/SB/PsiB/UB/LB, solved, and the solution scattered back into Ii.
+// solve(diag, upper, lower, psi, source) is the caller's.
+template <class Solve> static int solve_ray(ffm_plume *P, int flip, int n, double *Ii, Solve solve)
+{
+    if (flip < 0) return solve(P->dWork, P->upper, P->lower, Ii, P->sWork);
+    const int *cm = P->radCm[flip], *fm = P->radFm[flip];
+    const double *dW = P->dWork, *sW = P->sWork, *up = P->upper, *lo = P->lower;
+    double *dB = P->radDB, *sB = P->radSB, *pB = P->radPsiB, *uB = P->radUB, *lB = P->radLB;
+    forN(P, n, [=] __device__(long c) { const int s = cm[c]; dB[c] = dW[s]; sB[c] = sW[s]; pB[c] = Ii[s]; });
+    forN(P, P->nNat, [=] __device__(long e) {
+        const int q = fm[e];
+        if (q >= 0) { uB[e] = up[q]; lB[e] = lo[q]; } else { uB[e] = lo[~q]; lB[e] = up[~q]; }
+    });
+    FFM_TRY(solve(dB, uB, lB, pB, sB));
+    forN(P, n, [=] __device__(long c) { Ii[cm[c]] = pB[c]; });
+    return FFM_OK;
+}
+
 // The staged sweep of the rays over the blocks of a decomposed box (ffm_plume_set_radiation_ordering 1).  The ticks come from
 // ffm_ray_schedule and are the same in number on every rank.  In a tick a rank solves at most one ray: its upstream neighbours
 // solved that ray in earlier ticks and their values sit in the ghost cells, so the ghost inflow moves into the source and what
@@ -74,7 +103,7 @@ static int ray_flip_axis(const ffm_plume *P, int i)
 // waits for another outside that exchange.
 static int radiation_correct_staged(ffm_plume *P, const double *Ee)
 {
-    ffm_mesh *m = P->mesh; const int nOwn = P->nOwn; const long nNat = P->nNat;
+    ffm_mesh *m = P->mesh; const int nOwn = P->nOwn;
     const int nTicks = (int)P->radTick.size();
     const bool timing = getenv("FFM_TIMING") != nullptr;          // wall time of the ticks' exchanges (ghost exchange + the copies into the rays' ghost layers)
     double tExch = 0.0;
@@ -85,23 +114,10 @@ static int radiation_correct_staged(ffm_plume *P, const double *Ee)
                                              P->upper, P->lower, P->dWork, P->sWork));
             FFM_TRY(ffm_fvdom_fold_ghost_inflow_d(m, P->nRadHaloCells, P->radHaloCells, P->I[i], P->upper, P->lower, P->sWork));
             SolveLog L; memset(&L, 0, sizeof(L)); snprintf(L.name, sizeof(L.name), "I%d", i);
-            const int flip = ray_flip_axis(P, i);
-            if (flip < 0) {
-                FFM_TRY(ffm_ldu_bind_coeffs_native_d(P->A, P->dWork, P->upper, P->lower, 0));
-                FFM_TRY(ffm_solve_triangular_rows_d(P->A, P->I[i], P->sWork, &L.perf));
-            } else {
-                const int *cm = P->radCm[flip], *fm = P->radFm[flip];
-                const double *dW = P->dWork, *sW = P->sWork, *up = P->upper, *lo = P->lower; double *Ii = P->I[i];
-                double *dB = P->radDB, *sB = P->radSB, *pB = P->radPsiB, *uB = P->radUB, *lB = P->radLB;
-                forN(P, nOwn, [=] __device__(long c) { const int s = cm[c]; dB[c] = dW[s]; sB[c] = sW[s]; pB[c] = Ii[s]; });
-                forN(P, nNat, [=] __device__(long e) {
-                    const int q = fm[e];
-                    if (q >= 0) { uB[e] = up[q]; lB[e] = lo[q]; } else { uB[e] = lo[~q]; lB[e] = up[~q]; }
-                });
-                FFM_TRY(ffm_ldu_bind_coeffs_native_d(P->A, dB, uB, lB, 0));
-                FFM_TRY(ffm_solve_triangular_rows_d(P->A, pB, sB, &L.perf));
-                forN(P, nOwn, [=] __device__(long c) { Ii[cm[c]] = pB[c]; });
-            }
+            FFM_TRY(solve_ray(P, ray_flip_axis(P, i), nOwn, P->I[i], [&](const double *d, const double *up, const double *lo, double *psi, const double *src) {
+                FFM_TRY(ffm_ldu_bind_coeffs_native_d(P->A, d, up, lo, 0));
+                return ffm_solve_triangular_rows_d(P->A, psi, src, &L.perf);
+            }));
             P->log.push_back(L);
             if (!L.perf.converged) {
                 ffm_set_error("plume radiation: the staged solve of ray %d left sum|residual| above 1e-10 sum|source| (normalised %g): its rows are not triangular in the renamed order", i, L.perf.finalResidual);
@@ -133,6 +149,17 @@ static int absem_correct(ffm_plume *P)
     P->gmHaveA = true;
     return FFM_OK;
 }
+// absorptionEmission->ECont() of this radiation->correct() into radE: greyMean's, else constRadFractionEmission's RadFraction*Qdot
+// (constRadFractionEmission.C, radScaling)
+static int rad_emission(ffm_plume *P)
+{
+    if (P->gm) return absem_correct(P);
+    double frac = 0.0;
+    FFM_TRY(plume_rad_fraction(P, &frac));
+    double *E = P->radE; const double *Qd = P->Qdot;
+    forN(P, P->N, [=] __device__(long c) { E[c] = frac * Qd[c]; });
+    return FFM_OK;
+}
 
 // ---- P1 in place of the rays (ffm_plume_set_radiation_p1): P1::calculate() of P1.C:213-258 -------------------------------------
 // gamma = 1/(3 a + a0) (no scattering), fvm::laplacian(gamma, G) - fvm::Sp(a, G) == -4 a sigma T^4 - E with E = RadFraction*Qdot,
@@ -142,17 +169,10 @@ static int absem_correct(ffm_plume *P)
 static int p1_correct(ffm_plume *P)
 {
     ffm_mesh *m = P->mesh; const int N = P->N;
-    double *E = P->radE; const double *Qd = P->Qdot;
+    const double *E = P->radE;
     const double *aF = nullptr, *aB = nullptr;                    // greyMeanAbsorptionEmission: a = e as a cell field, its patch values the adjacent cells'
-    if (P->gm) {
-        FFM_TRY(absem_correct(P));
-        aF = P->aRad; aB = P->aRadB;
-        zg(P, P->aRadB, P->aRad);
-    } else {
-        double frac = 0.0;
-        FFM_TRY(plume_rad_fraction(P, &frac));
-        forN(P, N, [=] __device__(long c) { E[c] = frac * Qd[c]; });
-    }
+    FFM_TRY(rad_emission(P));
+    if (P->gm) { aF = P->aRad; aB = P->aRadB; zg(P, P->aRadB, P->aRad); }
     zg(P, P->p1Tb, P->T);
     const double a = P->radA;
     if (P->fused) {
@@ -208,7 +228,7 @@ extern "C" int ffm_plume_set_radiation_p1(ffm_plume *P, int solverFreq, double a
     if (!P->radE || !P->radShSu || !P->radShSp) return FFM_ERR_HIP;
     double *eb = P->p1EmisB; const double eps = wallEmissivity;
     forN(P, P->B, [=] __device__(long k) { eb[k] = eps; });
-    P->radA = absorption; P->Ehrr1 = Ehrr1; P->Ehrr2 = Ehrr2; P->radCoupled = true; P->p1Emis = wallEmissivity;
+    P->radA = absorption; P->Ehrr1 = Ehrr1; P->Ehrr2 = Ehrr2; P->radCoupled = true;
     P->p1Freq = solverFreq;
     return FFM_OK;
 }
@@ -216,51 +236,24 @@ extern "C" int ffm_plume_set_radiation_p1(ffm_plume *P, int solverFreq, double a
 int radiation_correct(ffm_plume *P)
 {
     if (P->p1Freq > 0) return p1_correct(P);
-    const int N = P->N, B = P->B; const long nNat = P->nNat;
-    const double Ib = SIGMA_SB * ((TREF * TREF) * (TREF * TREF)) / M_PI;
+    const int N = P->N;
     // the fused step on one block: every ray assembled in one pass, G formed once after the last ray.  The per-operator step, and
     // the block-Jacobi solves of a decomposed box, keep the operator chain and add each ray to G as it is solved -- the same bytes
     const bool onePass = P->fused && P->oneBlock;
-    double *G = P->G, *ref = P->radRef;
+    double *G = P->G;
     if (!onePass && !P->radStaged) forN(P, N, [=] __device__(long c) { G[c] = 0.0; });
-    forN(P, B, [=] __device__(long k) { ref[k] = Ib; });
     const double *Ee = nullptr;
-    if (P->gm) { FFM_TRY(absem_correct(P)); Ee = P->radE; }
-    else if (P->radCoupled) {      // absorptionEmission->ECont(): E = RadFraction*Qdot (constRadFractionEmission.C, radScaling)
-        double frac = 0.0;
-        FFM_TRY(plume_rad_fraction(P, &frac));
-        double *E = P->radE; const double *Qd = P->Qdot;
-        forN(P, N, [=] __device__(long c) { E[c] = frac * Qd[c]; });
-        Ee = E;
-    }
+    if (P->gm || P->radCoupled) { FFM_TRY(rad_emission(P)); Ee = P->radE; }
     if (P->radStaged) { FFM_TRY(radiation_correct_staged(P, Ee)); P->radHaveG = true; return FFM_OK; }
     const int nRay = (int)P->rayOmega.size();
     for (int i = 0; i < nRay; i++) {
-        const double omega = P->rayOmega[i];
-        if (onePass && P->gm) FFM_TRY(ffm_fvdom_ray_assemble_v_d(P->mesh, &P->rayD[3 * i], omega, P->aRad, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr, P->upper,
-                                                                 P->lower, P->dWork, P->sWork));
-        else if (onePass) FFM_TRY(ffm_fvdom_ray_assemble_d(P->mesh, &P->rayD[3 * i], omega, P->radA, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr, P->upper, P->lower,
-                                                           P->dWork, P->sWork));
-        else FFM_TRY(ray_assemble_ops(P, i, Ee));
+        FFM_TRY(ray_assemble(P, i, Ee, onePass));
         char nm[16]; snprintf(nm, sizeof(nm), "I%d", i);
-        const int flip = P->radOrdered ? ray_flip_axis(P, i) : -1;
-        if (flip < 0) {
-            FFM_TRY(solve_named(P, nm, FFM_PBICGSTAB, FFM_DILU, 1e-4, 0.0, P->dWork, P->upper, P->lower, P->I[i], P->sWork, false, true));
-        } else {
-            // the same system with the cells renamed by the flip of that axis: same sparsity, triangular
-            const int *cm = P->radCm[flip], *fm = P->radFm[flip];
-            const double *dW = P->dWork, *sW = P->sWork, *up = P->upper, *lo = P->lower; double *Ii = P->I[i];
-            double *dB = P->radDB, *sB = P->radSB, *pB = P->radPsiB, *uB = P->radUB, *lB = P->radLB;
-            forN(P, N, [=] __device__(long c) { const int s = cm[c]; dB[c] = dW[s]; sB[c] = sW[s]; pB[c] = Ii[s]; });
-            forN(P, nNat, [=] __device__(long e) {
-                const int t = fm[e];
-                if (t >= 0) { uB[e] = up[t]; lB[e] = lo[t]; } else { uB[e] = lo[~t]; lB[e] = up[~t]; }
-            });
-            FFM_TRY(solve_named(P, nm, FFM_PBICGSTAB, FFM_DILU, 1e-4, 0.0, dB, uB, lB, pB, sB, false, true));
-            forN(P, N, [=] __device__(long c) { Ii[cm[c]] = pB[c]; });
-        }
+        FFM_TRY(solve_ray(P, P->radOrdered ? ray_flip_axis(P, i) : -1, N, P->I[i], [&](const double *d, const double *up, const double *lo, double *psi, const double *src) {
+            return solve_named(P, nm, FFM_PBICGSTAB, FFM_DILU, 1e-4, 0.0, d, up, lo, psi, src, false, true);
+        }));
         FFM_TRY(HX(P, P->I[i]));
-        const double *Ii = P->I[i];
+        const double *Ii = P->I[i]; const double omega = P->rayOmega[i];
         if (!onePass) forN(P, N, [=] __device__(long c) { G[c] = G[c] + Ii[c] * omega; });
     }
     if (onePass) FFM_TRY(rad_update_G(P));
@@ -275,16 +268,9 @@ extern "C" int ffm_plume_ray_system(ffm_plume *P, int ray, int fused, double *di
 {
     if (!P || !diag || !upper || !lower || !source || !P->G || ray < 0 || ray >= (int)P->rayOmega.size()) return FFM_ERR_ARG;
     PL_HIP(hipSetDevice(P->ctx->device));
-    const double Ib = SIGMA_SB * ((TREF * TREF) * (TREF * TREF)) / M_PI;
-    double *ref = P->radRef;
-    forN(P, P->B, [=] __device__(long k) { ref[k] = Ib; });
     const double *Ee = P->radCoupled ? P->radE : nullptr;
     if (P->gm && !P->gmHaveA) { ffm_set_error("ffm_plume_ray_system: greyMeanAbsorptionEmission is on and has not been evaluated yet (step first)"); return FFM_ERR_ARG; }
-    if (fused && P->gm) FFM_TRY(ffm_fvdom_ray_assemble_v_d(P->mesh, &P->rayD[3 * ray], P->rayOmega[ray], P->aRad, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr,
-                                                           P->upper, P->lower, P->dWork, P->sWork));
-    else if (fused) FFM_TRY(ffm_fvdom_ray_assemble_d(P->mesh, &P->rayD[3 * ray], P->rayOmega[ray], P->radA, SIGMA_SB, P->T, Ee, ref, nullptr, nullptr,
-                                                     P->upper, P->lower, P->dWork, P->sWork));
-    else FFM_TRY(ray_assemble_ops(P, ray, Ee));
+    FFM_TRY(ray_assemble(P, ray, Ee, fused != 0));
     std::vector<double> c(P->N), fu(std::max<long>(P->nNat, 1)), fl(std::max<long>(P->nNat, 1));
     FFM_TRY(ffm_d2h(P->ctx, c.data(), P->dWork, sizeof(double) * P->N));
     for (int k = 0; k < P->nOwn; k++) diag[P->newToOld[k]] = c[k];
@@ -428,7 +414,8 @@ extern "C" int ffm_plume_set_radiation(ffm_plume *P, int solverFreq, int nPhi, i
     }
     if (!P->G) {
         P->G = dalloc(P, P->N); P->radSrc = dalloc(P, P->N); P->radJ = dalloc(P, P->nNat); P->radW = dalloc(P, P->nNat);
-        P->radJb = dalloc(P, P->B); P->radF = dalloc(P, P->B); P->radRef = dalloc(P, P->B);
+        // black inflow at the ambient temperature: the rays' refValue, written here and nowhere else
+        P->radJb = dalloc(P, P->B); P->radF = dalloc(P, P->B); P->radRef = dfill(P, P->B, SIGMA_SB * ((TREF * TREF) * (TREF * TREF)) / M_PI);
         if (!P->G || !P->radSrc || !P->radJ || !P->radW || !P->radJb || !P->radF || !P->radRef) return FFM_ERR_HIP;
     }
     // the rays' pointers and solid angles for ffm_fvdom_G_d
